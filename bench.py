@@ -7,10 +7,18 @@ self-query), top-10.  One step = parallel_top_k_similarity_search for the whole 
 the local search on every GPU (int8 MFMA candidate filter + exact f32 rescore of the
 candidates, certified), the RCCL all-gather of the partial lists and the root's merge.
 `value` = queries/s over the whole 10M corpus (the same total work at every N).  At N = 1
-this is the north-star shape (batched 10M); the same run also reports configs[1] (the first
-1M rows, 1000 queries) and the single-query p50 over the full corpus (configs[3]).
+this is the north-star shape (batched 10M).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, settles the clocks, warms up, times the K steps and prints the headline
+line (`value`, `ms_per_step` and what the timed steps alone give).  --full adds, after the
+timed steps, every side measurement and check: the filter's roofline and the per-stage kernel
+passes, the local-search / exchange split, the single-query p50 over the full corpus
+(configs[3]), configs[1] (the first 1M rows, 1000 queries), the oracle parity spot-check
+(--verify) and the CPU baseline.  --dump-outputs DIR writes the last timed step's results
+(what the caller of the search received: indices.npy as float64, distances.npy as float32,
+counts.npy as float64); the inputs are seeded, so two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   N > 1: launched by torch.distributed.run (one rank per GPU), or, without WORLD_SIZE in
   the environment, bench.py starts the N rank processes itself (before any GPU call).
   --comm host: the exchange over gloo instead of RCCL (ranks may then share a GPU: a
@@ -65,6 +73,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement and check (roofline and per-stage "
+                         "kernel passes, local-search split, p50, configs[1], oracle parity, CPU baseline); a plain "
+                         "run times the steps and prints the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (rank 0) to DIR/indices.npy, distances.npy, counts.npy")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3")
     ap.add_argument("--rows", type=int, default=None, help="override the corpus rows (tests)")
     ap.add_argument("--queries", type=int, default=None)
@@ -90,6 +104,8 @@ def parse():
                     help="N > 1: deadline of each collective phase (setup, the step loops, barriers); a "
                          "rank past it exits non-zero instead of blocking in a collective")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
     rows, q, k, dt, sc, label = CONFIGS[a.config]
     a.rows_total = a.rows if a.rows is not None else rows
     a.queries = a.queries if a.queries is not None else q
@@ -107,6 +123,15 @@ def _error_line(args, msg, **extra):
            "unit": "queries/s", "n_gpus": args.gpus, "error": msg}
     out.update(extra)
     print(json.dumps(out), flush=True)
+
+
+def dump_outputs(path, idx, dist, cnt):
+    """--dump-outputs: what the caller of the timed search received in the last timed step (the
+    root's lists), one .npy per array.  Row indices are below 2^53, exact in float64."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "indices.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "distances.npy"), dist.astype(np.float32))
+    np.save(os.path.join(path, "counts.npy"), cnt.astype(np.float64))
 
 
 def spawn_ranks(args):
@@ -274,14 +299,15 @@ def run_c1(args):
         bsr.load_index_from_vstore(index, vs, 0, 1)
         torch.cuda.synchronize()
         load_ms = (time.perf_counter() - t0) * 1e3
-        # CPU path's decode of the same file (the reference's read_parquet + Vec<Vec<f32>>)
-        t0 = time.perf_counter()
-        vs2 = bsr.get_global_vstore(vdir, False)
-        dec = vs2.get_many_array(None, dim=D)
-        cpu_decode_ms = (time.perf_counter() - t0) * 1e3
-        vs2.close()
+        if args.full:
+            # CPU path's decode of the same file (the reference's read_parquet + Vec<Vec<f32>>)
+            t0 = time.perf_counter()
+            vs2 = bsr.get_global_vstore(vdir, False)
+            dec = vs2.get_many_array(None, dim=D)
+            cpu_decode_ms = (time.perf_counter() - t0) * 1e3
+            vs2.close()
+            assert np.array_equal(dec, rows_h)
         vs.close()
-    assert np.array_equal(dec, rows_h)
     lib = bsr.lib()
     oi = np.empty((Q, K), np.uint64)
     od = np.empty((Q, K), np.float32)
@@ -306,6 +332,25 @@ def run_c1(args):
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
     res_i, res_d, res_c = oi.copy(), od.copy(), oc.copy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res_i, res_d, res_c)
+    out = {
+        "metric": "queries/sec + p50 latency, 768-d top-10 over N vectors @1/2/4/8 GPU",
+        "value": round(Q / (ms * 1e-3), 2), "unit": "queries/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32", "filter_dtype": "i8", "full": args.full,
+        "data": "synthetic U(-1,1) f32 rows (seed 42) written to the reference's parquet store, 32 queries "
+                "(seed 43, query 0 = row 0), HBM-resident",
+        "config": {"workload": args.label, "rows_total": N, "queries": Q, "top_k": K, "dim": D,
+                   "parallelism": "1 GPU"},
+        "parquet_load_ms": round(load_ms, 3),
+        "parquet_load_note": "open global.parquet + decode + H2D + row norms + int8 operand (bsr_index_load_vstore); "
+                             "once per store, outside the timed searches",
+    }
+    if not args.full:  # a plain run: the headline figure only
+        print(json.dumps(out), flush=True)
+        index.close()
+        return 0
     prof = kernel_timing_pass(index, step, args.steps)
     lat = []
     for _ in range(max(args.p50_iters, 20)):
@@ -319,18 +364,7 @@ def run_c1(args):
     oracle.parallel_top_k(rows_h, q_h, K, size=4, threads=4)
     cpu_s = time.perf_counter() - t1
     ems = prof.gemm_emit_ms / max(prof.gemm_emit_launches, 1)
-    out = {
-        "metric": "queries/sec + p50 latency, 768-d top-10 over N vectors @1/2/4/8 GPU",
-        "value": round(Q / (ms * 1e-3), 2), "unit": "queries/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32", "filter_dtype": "i8",
-        "data": "synthetic U(-1,1) f32 rows (seed 42) written to the reference's parquet store, 32 queries "
-                "(seed 43, query 0 = row 0), HBM-resident",
-        "config": {"workload": args.label, "rows_total": N, "queries": Q, "top_k": K, "dim": D,
-                   "parallelism": "1 GPU"},
-        "parquet_load_ms": round(load_ms, 3),
-        "parquet_load_note": "open global.parquet + decode + H2D + row norms + int8 operand (bsr_index_load_vstore); "
-                             "once per store, outside the timed searches",
+    out.update({
         "p50_ms": round(statistics.median(lat), 4),
         "filter_avg_launch_ms": round(ems, 5),
         "parity_all_queries": {"queries": Q, "indices_equal": ok_i, "distance_bits_equal": ok_d,
@@ -340,7 +374,7 @@ def run_c1(args):
                          "sample": f"all {Q} queries over the {N} rows, oracle with P = 4 rank threads "
                                    "(configs[0]'s mpiexec -n 4); parquet decode excluded, reported as decode_ms",
                          "decode_ms": round(cpu_decode_ms, 3), "nproc": os.cpu_count(), "cpu_model": cpu_model()},
-    }
+    })
     print(json.dumps(out), flush=True)
     index.close()
     return 0 if (ok_i and ok_d) else 1
@@ -431,6 +465,17 @@ def main():
         if watchdog:
             watchdog.arm(label, args.collective_timeout)
 
+    def finish(timeout=None):
+        """Every rank done: the last barrier, then the communicator, the index and the group closed."""
+        if watchdog:
+            watchdog.disarm()
+        barrier(timeout=timeout)
+        if comm:
+            comm.close()
+        index.close()
+        if dist:
+            dist.destroy_process_group()
+
     D, Q, K = args.dim, args.queries, args.k
     n_total = args.rows_total * (P if args.scaling == "weak" else 1)
     iv = bsr.interval_by_rank(rank, P, n_total)
@@ -449,9 +494,9 @@ def main():
         shard = shard.to(torch.bfloat16)
     torch.cuda.synchronize()
     index.load(shard[:n_local] if n_local else np.zeros((0, D), np.float32), start)
-    # configs[1] side measurement (N = 1, default config): the first 1M rows of the corpus
+    # configs[1] side measurement (--full, N = 1, default config): the first 1M rows of the corpus
     ix1 = None
-    if world == 1 and args.config == "c3" and not args.no_configs1 and n_local >= 1_000_000:
+    if args.full and world == 1 and args.config == "c3" and not args.no_configs1 and n_local >= 1_000_000:
         ix1 = bsr.Index(D, max_k=64, device=device, flags=bsr.BSR_FLAG_PROFILE | fflag)
         ix1.load(shard[:1_000_000], 0)
     del shard
@@ -552,6 +597,63 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     st = index.last_stats()
     res_i, res_d, res_c = oi.copy(), od.copy(), oc.copy()  # the last timed step's result (root)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res_i, res_d, res_c)
+
+    def headline():
+        """The result line's fields that the timed steps alone give (every field of a plain run)."""
+        return {
+            "metric": "queries/sec + p50 latency, 768-d top-10 over N vectors @1/2/4/8 GPU",
+            "value": round(Q / (ms_per_step * 1e-3), 2),
+            "unit": "queries/s",
+            "n_gpus": world,
+            "loopback": None if not loop else {
+                "ranks": P, "replayed_allgathers": comm.loopback_stats()[0] if comm else 0,
+                "missed_allgathers": comm.loopback_stats()[1] if comm else 0, "recorded_calls_per_search": lb_calls,
+                "note": (f"ONE process on one GPU timing rank 0's step of a {P}-rank run: its shard "
+                         f"({n_local} rows), every all-gather one device kernel where ncclAllGather sits "
+                         "(no host wait), the other ranks' contributions replayed from a real "
+                         f"{P}-rank run of this batch (host transport). value = queries / this step: a "
+                         "per-rank step projection without the collectives' latency, not a scaling "
+                         "measurement")},
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle_ms": args.settle_ms,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f32",
+            "filter_dtype": args.filter,
+            "full": args.full,
+            "data": f"synthetic U(-1,1) {'bf16' if corpus_bf16 else 'f32'} corpus generated on device (seed 42), "
+                    f"{Q} queries (seed 43, query 0 = row 0), HBM-resident",
+            "config": {
+                "workload": args.label + ("" if args.rows is None else f" (rows overridden: {n_total})"),
+                "rows_total": n_total, "rows_per_gpu_rank0": n_local, "queries": Q, "top_k": K, "dim": D,
+                "parallelism": (f"corpus sharded over {world} GPU(s) (interval_by_rank)" +
+                                ("" if world == 1 else f" + {args.comm.upper()} all-gather of the partial lists"
+                                                       " + root merge")) if not loop else
+                               f"rank 0 of {P} (interval_by_rank), loopback communicator: emulated all-gathers",
+                "filter": "int8 MFMA (v_mfma_i32_16x16x64_i8) candidates, " + (
+                    f"exact sequential-f32 rescore of k'={st.n_candidates} per query, certified (DESIGN.md §4)"
+                    if st.n_candidates else
+                    "emission threshold selected from every rank's sample (all-gathered), exact sequential-f32 "
+                    "rescore of every emitted row, the merged lists certified on every rank (DESIGN.md §6)"),
+            },
+            "fallback_queries_per_step_rank0": stats_fb / args.steps,
+            "rescued_queries_per_step_rank0": stats_rescued / args.steps,
+            "candidates_per_query": st.n_candidates,  # (0: global threshold, every emitted row rescored)
+            "self_query_rank1": bool(res_i[0, 0] == 0 and res_d[0, 0] == 0.0),
+            "emitted_per_query_rank0": round(st.n_emitted / max(Q, 1), 1),
+            "row_ebound": round(float(st.row_ebound), 6),
+        }
+
+    if not args.full:  # a plain run: the headline figure only, no side measurement or check
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        finish()
+        return
     prof = kernel_timing_pass(index, step, args.steps)  # (every rank: each search is a collective)
     # per-stage breakdown from a separate profiled pass (every stage evented)
     index.set_profile(2)
@@ -674,44 +776,8 @@ def main():
                     "algorithmic_ops_per_launch": flops, "avg_launch_ms": round(emit_ms, 5),
                     "launch_timing": LAUNCH_TIMING,
                     "note": "rank 0's shard; ops = 2 * queries * shard rows * dim (int8 multiply-adds)"}
-        out = {
-            "metric": "queries/sec + p50 latency, 768-d top-10 over N vectors @1/2/4/8 GPU",
-            "value": round(Q / (ms_per_step * 1e-3), 2),
-            "unit": "queries/s",
-            "n_gpus": world,
-            "loopback": None if not loop else {
-                "ranks": P, "replayed_allgathers": comm.loopback_stats()[0] if comm else 0,
-                "missed_allgathers": comm.loopback_stats()[1] if comm else 0, "recorded_calls_per_search": lb_calls,
-                "note": (f"ONE process on one GPU timing rank 0's step of a {P}-rank run: its shard "
-                         f"({n_local} rows), every all-gather one device kernel where ncclAllGather sits "
-                         "(no host wait), the other ranks' contributions replayed from a real "
-                         f"{P}-rank run of this batch (host transport). value = queries / this step: a "
-                         "per-rank step projection without the collectives' latency, not a scaling "
-                         "measurement")},
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle_ms": args.settle_ms,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "filter_dtype": args.filter,
-            "data": f"synthetic U(-1,1) {'bf16' if corpus_bf16 else 'f32'} corpus generated on device (seed 42), "
-                    f"{Q} queries (seed 43, query 0 = row 0), HBM-resident",
-            "config": {
-                "workload": args.label + ("" if args.rows is None else f" (rows overridden: {n_total})"),
-                "rows_total": n_total, "rows_per_gpu_rank0": n_local, "queries": Q, "top_k": K, "dim": D,
-                "parallelism": (f"corpus sharded over {world} GPU(s) (interval_by_rank)" +
-                                ("" if world == 1 else f" + {args.comm.upper()} all-gather of the partial lists"
-                                                       " + root merge")) if not loop else
-                               f"rank 0 of {P} (interval_by_rank), loopback communicator: emulated all-gathers",
-                "filter": "int8 MFMA (v_mfma_i32_16x16x64_i8) candidates, " + (
-                    f"exact sequential-f32 rescore of k'={st.n_candidates} per query, certified (DESIGN.md §4)"
-                    if st.n_candidates else
-                    "emission threshold selected from every rank's sample (all-gathered), exact sequential-f32 "
-                    "rescore of every emitted row, the merged lists certified on every rank (DESIGN.md §6)"),
-            },
+        out = headline()
+        out.update({
             "p50_ms": round(p50, 4) if p50 is not None else None,
             "p50_config": f"1 query over {n_total} rows on {world} GPU(s)" + (
                 (" (int8 skinny filter keeping each workgroup's 4 best rows, HBM-bound, + exact rescore)"
@@ -743,13 +809,7 @@ def main():
                 "filter_sample": round(prof_scan.gemm_sample_ms / max(prof_scan.gemm_sample_launches, 1), 4),
                 "exact_scan": round(prof_scan.scan_ms / max(prof_scan.scan_launches, 1), 4),
                 "local_search_total": round(prof_scan.search_ms / max(prof_scan.searches, 1), 4)},
-            "fallback_queries_per_step_rank0": stats_fb / args.steps,
-            "rescued_queries_per_step_rank0": stats_rescued / args.steps,
-            "candidates_per_query": st.n_candidates,  # (0: global threshold, every emitted row rescored)
-            "self_query_rank1": bool(res_i[0, 0] == 0 and res_d[0, 0] == 0.0),
-            "emitted_per_query_rank0": round(st.n_emitted / max(Q, 1), 1),
-            "row_ebound": round(float(st.row_ebound), 6),
-        }
+        })
         if c1:
             out["configs1"] = c1
         kms = (prof_scan.gemm_emit_ms / max(prof_scan.gemm_emit_launches, 1) if args.filter == "i8" else
@@ -841,14 +901,7 @@ def main():
     if rank == 0:
         out.setdefault("cpu_baseline", None)  # N > 1: the baseline is measured at N = 1 only
         print(json.dumps(out), flush=True)
-    if watchdog:
-        watchdog.disarm()
-    barrier(timeout=max(args.collective_timeout, 1200))  # (rank 0's spot-check and CPU sweep ran)
-    if comm:
-        comm.close()
-    index.close()
-    if dist:
-        dist.destroy_process_group()
+    finish(timeout=max(args.collective_timeout, 1200))  # (rank 0's spot-check and CPU sweep ran)
 
 
 if __name__ == "__main__":

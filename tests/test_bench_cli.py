@@ -25,3 +25,14 @@ def test_bench_failing_rank_fails_fast_cpu():
     d = json.loads(lines[0])
     assert d["value"] is None and d["failed_rank"] == 1 and "rank 1 exited with status 3" in d["error"]
     assert "BSR_BENCH_FAIL_RANK" in d["stderr_tail"]
+
+
+def test_bench_options_and_step_count_cpu():
+    """--full and --dump-outputs exist, and --steps is the number of timed steps: none is refused
+    by the parser (exit status 2) before anything else runs."""
+    bench = [sys.executable, os.path.join(ROOT, "bench.py")]
+    r = subprocess.run([*bench, "--help"], cwd=ROOT, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    r = subprocess.run([*bench, "--gpus", "1", "--steps", "0", "--warmup", "0"], cwd=ROOT, capture_output=True,
+                       text=True, timeout=60)
+    assert r.returncode == 2 and "--steps" in r.stderr

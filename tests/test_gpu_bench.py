@@ -2,18 +2,24 @@
 default workload at a reduced row count, configs[0] through the parquet store (`--config c1`)
 and the N > 1 path (`--gpus 2 --comm host`: spawn, sharding, the library's exchange and the
 root merge, the spot-check over the whole corpus) with two rank processes on the one GPU.
+Those runs are `--full` ones (the side measurements and checks they read); the plain run, the
+headline line alone, and `--dump-outputs` are checked against them.
 Each run is a child process; nothing here re-executes a GPU-initialised process."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QUICK = ["--steps", "3", "--warmup", "1", "--settle-ms", "0", "--p50-iters", "2", "--no-cpu-baseline"]
+PLAIN = ["--steps", "3", "--warmup", "1", "--settle-ms", "0"]
+# (the side measurements and checks these tests read run under --full)
+QUICK = [*PLAIN, "--full", "--p50-iters", "2", "--no-cpu-baseline"]
+SMALL = ["--rows", "300000"]  # the default workload at a reduced row count (plain and --full runs)
 
 
 def _bench(*args, timeout=240):
@@ -35,9 +41,22 @@ def _common(d, n_gpus, steps=3):
     assert "workload" in d["config"]
 
 
-def test_bench_default_workload_small(gpu):
-    d = _bench("--rows", "300000", "--no-configs1", "--verify", "2", *QUICK)
+def _dump(path):
+    return {n: np.load(os.path.join(path, n + ".npy")) for n in ("indices", "distances", "counts")}
+
+
+@pytest.fixture(scope="module")
+def full_small(gpu, tmp_path_factory):
+    """One --full run of the reduced default workload, its outputs dumped (shared, read-only)."""
+    out = str(tmp_path_factory.mktemp("bench_full") / "out")
+    d = _bench(*SMALL, "--no-configs1", "--verify", "2", "--dump-outputs", out, *QUICK)
+    return d, _dump(out)
+
+
+def test_bench_default_workload_small(full_small):
+    d, _ = full_small
     _common(d, 1)
+    assert d["full"] is True
     rf = d["roofline"]
     assert rf["bound"] == "mfma" and rf["unit"] == "TOP/s" and rf["peak"] == 5000.0
     assert 0 < rf["frac"] < 1 and abs(rf["achieved"] / rf["peak"] - rf["frac"]) < 1e-3
@@ -47,6 +66,44 @@ def test_bench_default_workload_small(gpu):
     assert sc["indices_equal"] and sc["distance_bits_equal"]
     assert d["fallback_queries_per_step_rank0"] == 0
     assert d["self_query_rank1"] is True
+
+
+def test_bench_plain_run_headline_and_outputs(full_small, tmp_path):
+    """A plain run (no --full) times the steps and prints the headline line alone: none of the side
+    measurements or checks.  --dump-outputs writes the last timed step's lists as float .npy files,
+    and the plain and the --full run of the same arguments compute the same outputs, bit for bit
+    (the --full run's are spot-checked against the oracle)."""
+    out = str(tmp_path / "out")
+    d = _bench(*SMALL, "--dump-outputs", out, *PLAIN)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "queries/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 1000 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for key in ("roofline", "cpu_baseline", "parity_spot_check", "p50_ms", "configs1", "kernels_ms_per_step_rank0",
+                "local_search_ms_per_step", "roofline_p50"):
+        assert key not in d, key
+    assert sorted(os.listdir(out)) == ["counts.npy", "distances.npy", "indices.npy"]
+    got, (dfull, want) = _dump(out), full_small
+    assert got["indices"].dtype == np.float64 and got["indices"].shape == (1000, 10)
+    assert got["distances"].dtype == np.float32 and got["distances"].shape == (1000, 10)
+    assert got["counts"].dtype == np.float64 and np.array_equal(got["counts"], np.full(1000, 10.0))
+    assert got["indices"][0, 0] == 0 and got["distances"][0, 0] == 0.0  # the self-query
+    assert np.all(np.diff(got["distances"], axis=1) >= 0)
+    assert np.all((got["indices"] >= 0) & (got["indices"] < 300000))
+    assert d["config"] == dfull["config"] and d["metric"] == dfull["metric"]
+    for n in got:
+        assert got[n].tobytes() == want[n].tobytes(), n
+
+
+def test_bench_configs0_plain_run(gpu, tmp_path):
+    out = str(tmp_path / "out")
+    d = _bench("--config", "c1", "--dump-outputs", out, *PLAIN)
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 3 and d["full"] is False
+    assert "parity_all_queries" not in d and "cpu_baseline" not in d and "p50_ms" not in d
+    got = _dump(out)
+    assert got["indices"].shape == (32, 10) and got["distances"].dtype == np.float32
+    assert got["indices"][0, 0] == 0 and got["distances"][0, 0] == 0.0
 
 
 def test_bench_configs0_parquet_store(gpu):

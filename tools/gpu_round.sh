@@ -63,7 +63,8 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 9
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
 mkdir -p "$O"
-NOB="--no-cpu-baseline --no-configs1"
+# (every bench step here reads the side measurements: --full; a plain bench.py prints the headline only)
+NOB="--full --no-cpu-baseline --no-configs1"
 
 run() {  # run SECONDS LABEL OUTFILE CMD...: one GPU step, its limit, its status
     local t=$1 label=$2 out=$3
@@ -80,9 +81,9 @@ for step in $STEPS; do
       timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > "$O/pytest_gpu.log" 2>&1
       rc=$?; echo "pytest rc=$rc"; tail -3 "$O/pytest_gpu.log"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      run 400 bench "$O/bench.json" python bench.py; head -c 400 "$O/bench.json"; echo ;;
+      run 400 bench "$O/bench.json" python bench.py --full; head -c 400 "$O/bench.json"; echo ;;
     configs)
-      run 300 "bench c1" "$O/bench_c1.json" python bench.py --config c1 --steps 50 --warmup 5
+      run 300 "bench c1" "$O/bench_c1.json" python bench.py --full --config c1 --steps 50 --warmup 5
       run 300 "bench c2" "$O/bench_c2.json" python bench.py --config c2 --steps 20 --warmup 3 --verify 2 $NOB
       run 300 "bench c4" "$O/bench_c4.json" python bench.py --config c4 --steps 5 --warmup 2 --verify 2 $NOB
       run 300 "bench c5" "$O/bench_c5.json" python bench.py --config c5 --steps 5 --warmup 2 --verify 2 $NOB ;;
@@ -133,7 +134,7 @@ for step in $STEPS; do
       for r in 1 2; do
         for v in 0 1; do
           BSR_MERGE_HASH=$v run 300 "mergeab hash=$v $r" "$O/mergeab_${v}_$r.json" python bench.py --comm loopback --gpus 8 \
-              --replay "$O/loop8.npz" --steps 100 --warmup 5 --verify 1 --no-cpu-baseline
+              --replay "$O/loop8.npz" --steps 100 --warmup 5 --full --verify 1 --no-cpu-baseline
           python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('hash', sys.argv[2], d['ms_per_step'], d['loopback']['missed_allgathers'])" \
               "$O/mergeab_${v}_$r.json" "$v"
         done
@@ -287,13 +288,13 @@ for step in $STEPS; do
       python3 tools/microbench/pmc_summary.py "$O/ps" > "$O/pmc_small_summary.txt" ;;
     rehearsal)
       for n in 2 4 8; do
-        run 400 "bench N=$n host" "$O/bench_n$n.json" python bench.py --gpus $n --comm host --steps 10 --warmup 2 --verify 2 \
+        run 400 "bench N=$n host" "$O/bench_n$n.json" python bench.py --full --gpus $n --comm host --steps 10 --warmup 2 --verify 2 \
             --no-cpu-baseline
         head -c 600 "$O/bench_n$n.json"; echo
       done ;;
     rehprof)
       run 600 "rehearsal N=8 rocprof" "$O/bench_n8_prof.json" rocprofv3 --kernel-trace --stats --output-format csv \
-          -d "$O/rehprof" -o run -- python3 bench.py --gpus 8 --comm host --steps 10 --warmup 2 --verify 0 --no-cpu-baseline \
+          -d "$O/rehprof" -o run -- python3 bench.py --full --gpus 8 --comm host --steps 10 --warmup 2 --verify 0 --no-cpu-baseline \
           --p50-iters 3
       find "$O/rehprof" -name "*kernel_stats.csv" | head -3 ;;
     hist)
@@ -303,7 +304,7 @@ for step in $STEPS; do
       run 300 "filter_hist 10M" "$O/hist_10m.txt" tools/microbench/filter_hist 10000000 1000 9 0.1473
       grep -h -E "median|DIFFER" "$O"/hist_*.txt ;;
     loopback)
-      run 600 "loopback N=8" "$O/bench_loop8.json" python bench.py --comm loopback --gpus 8 --steps 50 --warmup 5 \
+      run 600 "loopback N=8" "$O/bench_loop8.json" python bench.py --full --comm loopback --gpus 8 --steps 50 --warmup 5 \
           --verify 4 --no-cpu-baseline
       head -c 700 "$O/bench_loop8.json"; echo ;;
     looprec)
