@@ -55,6 +55,12 @@ BSR_PATH_DEVICE_MERGE = 8
 BSR_PATH_FALLBACK = 16
 BSR_PATH_SKINNY_TOP = 32
 BSR_PATH_TOP_RERUN = 64
+BSR_PATH_MASK_LIST = 128    # masked search: exact top-k over the allowed-row list
+BSR_PATH_MASK_FILTER = 256  # masked search: int8 filter, emitted lists cut by the mask
+BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
+BSR_MASK_LIST = 1
+BSR_MASK_FILTER = 2
+_MASK_MODES = {"auto": BSR_MASK_AUTO, "list": BSR_MASK_LIST, "filter": BSR_MASK_FILTER}
 FILTER_I8 = 0
 ROOT = 0  # src/mpi_helpers/mod.rs:8
 
@@ -126,6 +132,7 @@ def lib() -> ctypes.CDLL:
         "bsr_index_global_offset": (ctypes.c_int, [_P, ctypes.POINTER(u64)]),
         "bsr_index_get_many": (ctypes.c_int, [_P, u64, u64, _P]),
         "bsr_local_top_k": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
+        "bsr_local_top_k_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
         "bsr_comm_init": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(_P)]),
@@ -253,6 +260,42 @@ class SliceArgs:
     length: int
 
 
+# ---- allow masks (bsr_local_top_k_masked) ---------------------------------------------------
+def pack_allow_mask(n: int, mask=None, ids=None) -> np.ndarray:
+    """The packed allow mask of an n-row shard: ceil(n / 64) uint64 words, bit (i & 63) of word
+    (i >> 6) set when local row i is allowed (little-endian bit order), tail bits zero.  Give a
+    bool array [n] (mask) or integer local row ids (ids: any order, duplicates allowed; an id
+    outside [0, n) raises BsrError(-1))."""
+    n = int(n)
+    if n < 0 or (mask is None) == (ids is None):
+        raise BsrError(-1, "pack_allow_mask takes n >= 0 and exactly one of mask / ids")
+    if mask is not None:
+        bits = np.asarray(mask)
+        if bits.dtype != np.bool_ or bits.shape != (n,):
+            raise BsrError(-1, f"mask must be a bool array of shape ({n},)")
+    else:
+        ids = np.asarray(ids)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise BsrError(-1, "ids must be integers")
+        ids = ids.reshape(-1).astype(np.int64, copy=False) if ids.size else np.zeros(0, np.int64)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise BsrError(-1, f"row id outside [0, {n})")
+        bits = np.zeros(n, np.bool_)
+        bits[ids] = True
+    words = (n + 63) // 64
+    packed = np.zeros(words * 8, np.uint8)
+    packed[:(n + 7) // 8] = np.packbits(bits, bitorder="little")
+    return packed.view("<u8").astype(np.uint64, copy=False)
+
+
+def _mask_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in _MASK_MODES:
+            raise BsrError(-1, f"mask_mode {mode!r}: one of {sorted(_MASK_MODES)}")
+        return _MASK_MODES[mode]
+    return int(mode)
+
+
 # ---- the rank's shard ---------------------------------------------------------------------
 class Index:
     """One rank's corpus block resident in HBM (read side of PolarsVectorstore)."""
@@ -336,8 +379,28 @@ class Index:
             raise BsrError(-1, "Index not found")
         return rows[0]
 
-    def local_top_k(self, queries, k: int):
-        """Batched compute_local_top_k -> (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32)."""
+    def _allow_words(self, allow_mask, allow_ids):
+        """(buffer, word count) of a search's allow mask: a bool array [n] or row ids are packed
+        here; packed uint64 words (a numpy array or a torch device tensor) pass through."""
+        if allow_mask is not None and allow_ids is not None:
+            raise BsrError(-1, "give allow_mask or allow_ids, not both")
+        if allow_ids is not None:
+            w = pack_allow_mask(self.get_count(), ids=allow_ids)
+        elif isinstance(allow_mask, np.ndarray) and allow_mask.dtype == np.uint64:
+            w = np.ascontiguousarray(allow_mask).reshape(-1)
+        elif hasattr(allow_mask, "data_ptr"):  # packed words in a torch tensor (host or device)
+            if allow_mask.element_size() != 8 or not allow_mask.is_contiguous():
+                raise BsrError(-1, "a tensor allow_mask holds packed 64-bit words, contiguous")
+            return allow_mask, int(allow_mask.numel())
+        else:
+            w = pack_allow_mask(self.get_count(), mask=np.asarray(allow_mask))
+        return w, int(w.size)
+
+    def local_top_k(self, queries, k: int, allow_mask=None, allow_ids=None, mask_mode="auto"):
+        """Batched compute_local_top_k -> (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32).
+        With allow_mask (a bool array [n], or packed uint64 words: numpy, or a torch tensor passed
+        through as a pointer) or allow_ids (local row ids), the search is restricted to those
+        rows (bsr_local_top_k_masked); mask_mode: "auto", "list", "filter" or a BSR_MASK_* value."""
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -347,13 +410,27 @@ class Index:
         oi = np.empty((nq, k), np.uint64)
         od = np.empty((nq, k), np.float32)
         oc = np.empty(nq, np.uint32)
-        _check(lib().bsr_local_top_k(self._h, _ptr(q), nq, k, _ptr(oi), _ptr(od), _ptr(oc)))
+        if allow_mask is None and allow_ids is None:
+            _check(lib().bsr_local_top_k(self._h, _ptr(q), nq, k, _ptr(oi), _ptr(od), _ptr(oc)))
+            return oi, od, oc
+        w, nw = self._allow_words(allow_mask, allow_ids)
+        # (an empty shard's mask has no words: a valid, non-null pointer all the same)
+        wp = _ptr(w) if nw else _ptr(np.zeros(1, np.uint64))
+        _check(lib().bsr_local_top_k_masked(self._h, _ptr(q), nq, k, wp, nw, _mask_mode(mask_mode), _ptr(oi),
+                                            _ptr(od), _ptr(oc)))
         return oi, od, oc
 
-    def local_top_k_device(self, queries, nq: int, k: int, out_idx, out_dist, out_count):
-        """Zero-copy variant on device buffers (torch tensors or raw pointers)."""
-        _check(lib().bsr_local_top_k(self._h, _ptr(queries), nq, k, _ptr(out_idx), _ptr(out_dist),
-                                     _ptr(out_count)))
+    def local_top_k_device(self, queries, nq: int, k: int, out_idx, out_dist, out_count, allow_words=None,
+                           mask_mode="auto"):
+        """Zero-copy variant on device buffers (torch tensors or raw pointers).  allow_words: the
+        packed allow mask (ceil(n / 64) uint64 words, a numpy array or a torch tensor)."""
+        if allow_words is None:
+            _check(lib().bsr_local_top_k(self._h, _ptr(queries), nq, k, _ptr(out_idx), _ptr(out_dist),
+                                         _ptr(out_count)))
+            return
+        nw = int(allow_words.numel()) if hasattr(allow_words, "numel") else int(allow_words.size)
+        _check(lib().bsr_local_top_k_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), nw,
+                                            _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_count)))
 
     def last_stats(self) -> SearchStats:
         s = SearchStats()

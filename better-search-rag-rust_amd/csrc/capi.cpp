@@ -25,6 +25,9 @@ int bsr_index_append_impl(bsr_index* ix, const void* rows, uint64_t n_rows);
 int bsr_index_get_many_impl(const bsr_index* ix, uint64_t offset, uint64_t count, float* out);
 int bsr_local_top_k_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx,
                          float* out_dist, uint32_t* out_count);
+int bsr_local_top_k_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                                uint64_t allow_words, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                uint32_t* out_count);
 int bsr_index_collect_profile_impl(bsr_index* ix);
 int bsr_copy_out_impl(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist,
                       uint32_t* out_count);
@@ -314,6 +317,13 @@ int bsr_index_get_many(const bsr_index* ix, uint64_t offset, uint64_t count, flo
 int bsr_local_top_k(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint64_t* out_idx,
                     float* out_dist, uint32_t* out_count) {
     BSR_GUARD(bsr_local_top_k_impl(ix, queries, n_queries, k, out_idx, out_dist, out_count));
+}
+
+int bsr_local_top_k_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                           const uint64_t* allow, uint64_t allow_words, uint32_t mode, uint64_t* out_idx,
+                           float* out_dist, uint32_t* out_count) {
+    BSR_GUARD(bsr_local_top_k_masked_impl(ix, queries, n_queries, k, allow, allow_words, mode, out_idx, out_dist,
+                                          out_count));
 }
 
 // The device merge's limits (k_merge_lists: one wave per query, the concatenation in LDS).

@@ -403,8 +403,10 @@ static uint32_t ks_for(uint32_t k) { return (kp_for(k) + 1u) / 8u; }
 // Steps 2-3 of the candidate stage: the sample pass and tau0 (smax: also the ks best sample
 // keys per query, the input of a parallel search's global threshold), then the emit pass.
 // Batches of at most 16 queries use the skinny (HBM-bound, no LDS) filter kernels.
-static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax);
-static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k);
+// ks / cap (0: ks_for(k) / cap_for(k)): the masked search's lowered threshold and longer lists.
+static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax, uint32_t ks = 0,
+                       uint32_t cap = 0);
+static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t cap = 0);
 
 
 // The self-thresholded single-query path (round 6, DESIGN.md §5 tiny batches): batches of <= 16
@@ -423,12 +425,12 @@ static uint32_t top_slots(const bsr_index* ix, uint32_t nq, uint32_t k) {
 }
 
 // Buffers of the candidate stage for a batch (k' = kp_for(k) candidates, lists of cap keys).
-static int filter_buffers(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k) {
+static int filter_buffers(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t cap_in = 0) {
     // k' candidates, (k'+1) % 64 == 0, about 3k: the k-th exact score must clear the (k'+1)-th
     // approximate one by E_q, and in a Gaussian-like tail that takes ~3x as many rows at
     // E_q/sigma ~ 0.26.  63 for k <= 10, 191 for k = 50, 383 for k = 100.
     const uint32_t kp = kp_for(k);
-    const uint32_t cap = std::max(cap_for(k), top_slots(ix, nq, k));
+    const uint32_t cap = std::max(cap_in ? cap_in : cap_for(k), top_slots(ix, nq, k));
     ix->stats.n_candidates = kp;
     BSR_TRY(ix->tau.ensure((size_t)qpad * sizeof(float)));
     BSR_TRY(ix->cand.ensure((size_t)qpad * cap * sizeof(uint64_t)));
@@ -452,14 +454,15 @@ static GemmArgs gemm_args(bsr_index* ix, uint32_t qpad) {
     return g;
 }
 
-static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax) {
-    BSR_TRY(filter_buffers(ix, nq, qpad, k));
+static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax, uint32_t ks_in,
+                       uint32_t cap_in) {
+    BSR_TRY(filter_buffers(ix, nq, qpad, k, cap_in));
     const bool skinny = nq <= kSkinnyMaxQ;
-    const uint32_t cap = cap_for(k);
+    const uint32_t cap = cap_in ? cap_in : cap_for(k);
     // (k'+1)/8: about 8 x 32 = 256 rows reach tau0 for k <= 10.  Fewer (ks = (k'+1)/12, /16)
     // measured 1-2% less filter time and up to 1.3% of the queries falling back to the exact
     // scan (profiles/r02f_*): not worth it.
-    const uint32_t ks = ks_for(k);
+    const uint32_t ks = ks_in ? ks_in : ks_for(k);
     const uint32_t BM = kFilterTile;
     const uint64_t n = ix->n;
     GemmArgs g = gemm_args(ix, qpad);
@@ -496,7 +499,7 @@ static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, ui
     return BSR_OK;
 }
 
-static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k) {
+static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t cap_in) {
     const bool skinny = nq <= kSkinnyMaxQ;
     const uint32_t BM = kFilterTile;
     const uint64_t n = ix->n;
@@ -508,7 +511,7 @@ static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k) {
     g.tau = ix->tau.as<float>();
     g.cand = ix->cand.as<uint64_t>();
     g.cnt = ix->cnt.as<uint32_t>();
-    g.cap = cap_for(k);
+    g.cap = cap_in ? cap_in : cap_for(k);
     // the last 1/kTailDiv of the row tiles are balanced dynamically (k_filter_qs16)
     g.tail = g.n_qt <= kTailCounters ? ix->cnt.as<uint32_t>() + qpad : nullptr;
     BSR_HIP(launch_timed(ix, ix->ev_emit, [&](hipEvent_t e0, hipEvent_t e1) {
@@ -891,6 +894,265 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
 }
 
 // ---------------------------------------------------------------------------------------
+// Masked search (bsr_local_top_k_masked)
+// ---------------------------------------------------------------------------------------
+// Exact top-k over the allowed-row list for n_ids queries (device id list, padded to a multiple
+// of kScanQF with valid ids): the full groups of kScanQF queries share launches (as many groups
+// per launch as kListPartBytes of partial lists hold), the last partial group takes its own.
+constexpr size_t kListPartBytes = 64u << 20;
+static int run_list_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uint32_t k, uint32_t n_list) {
+    if (!n_ids || !n_list) return BSR_OK;
+    const uint32_t grid = scan_grid_for(n_list);
+    const size_t group_bytes = (size_t)grid * kScanQF * k * sizeof(uint64_t);
+    const uint32_t full = n_ids / kScanQF, rest = n_ids % kScanQF;
+    const uint32_t per_launch = (uint32_t)std::min<size_t>(std::max<size_t>(kListPartBytes / group_bytes, 1), 65535);
+    BSR_TRY(ix->part.ensure(group_bytes * std::max(1u, std::min(per_launch, full))));
+    auto scan = [&](uint32_t g0, uint32_t groups, uint32_t nqf) -> int {
+        BSR_HIP(launch_scan_list(ix->rows.as<float>(), ix->ld, ix->dim, ix->mask_list.as<uint32_t>(), n_list,
+                                 ix->na.as<float>(), ix->qf32.as<float>(), ids + (size_t)g0 * kScanQF, nqf, groups,
+                                 ix->nb.as<float>(), k, grid, ix->part.as<uint64_t>(), ix->stream));
+        for (uint32_t g = 0; g < groups; ++g)
+            BSR_HIP(launch_merge_parts(ix->part.as<uint64_t>() + (size_t)g * grid * kScanQF * k, grid,
+                                       ids + (size_t)(g0 + g) * kScanQF, nqf, k, ix->keys.as<uint64_t>(), ix->stream));
+        return BSR_OK;
+    };
+    ev_begin(ix, ix->ev_scan, 1);
+    for (uint32_t g0 = 0; g0 < full; g0 += per_launch) BSR_TRY(scan(g0, std::min(per_launch, full - g0), kScanQF));
+    if (rest) BSR_TRY(scan(full, 1, rest));
+    ev_end(ix, ix->ev_scan);
+    return BSR_OK;
+}
+
+// The masked filter path's lowered threshold: with a fraction rho = A / n of the
+// rows allowed, the ks_m = ceil(ks_for(k) / rho)-th best sampled score lets as many ALLOWED rows
+// through as the unmasked search's threshold lets rows through; 0 when launch_select_tau cannot
+// select that deep (ks_m > 128, i.e. rho < ks_for(k) / 128).
+static uint32_t masked_ks(uint32_t k, uint64_t n, uint64_t A) {
+    if (!A) return 0;
+    const uint64_t ks_m = ((uint64_t)ks_for(k) * n + A - 1) / A;
+    return ks_m <= 128 ? (uint32_t)ks_m : 0u;
+}
+
+// BSR_MASK_AUTO's choice where both paths are possible, a pure function of (n, A, nq, k): whether
+// the list scan is expected to beat the filter path (the measured table).
+// Measured (1M x 768 rows, k = 10, profiles/masked_bench.json): the list scan costs 0.52 ns per
+// listed row for one query (HBM-bound) and 1.30 ns per row and group of kScanQF queries
+// (VALU-bound), taken as linear in the queries per group between the two; the filter path costs
+// one pass over the shard whatever A is.  One query: the list wins at A = n / 4 (0.24 vs 0.30
+// ms), the filter at n / 2 (0.28 vs 0.37 ms), the lines cross near n / 3.  1000 queries: the
+// filter wins wherever it is possible.  Hence: the list when groups x A x w <= n / 3, w = 1 for
+// one query per group up to 2.6 for kScanQF.  k does not enter (the filter's range does that).
+static bool auto_prefers_list(uint64_t n, uint64_t A, uint32_t nq, uint32_t k) {
+    (void)k;
+    const uint64_t groups = (nq + kScanQF - 1) / kScanQF;
+    const uint64_t w100 = 100 + 23 * (uint64_t)(std::min(nq, kScanQF) - 1);
+    return 3 * A * groups * w100 <= 100 * n;
+}
+
+// Which path a masked search takes.  BSR_MASK_FILTER: the filter path whenever it is possible
+// at all; BSR_MASK_AUTO: where it is possible and auto_prefers_list says no.
+static bool masked_filter_path(const bsr_index* ix, uint32_t mode, uint64_t A, uint32_t nq, uint32_t k) {
+    const bool possible = ix->n > 0 && ix->approx_ok && k <= kMaxKForFilter && ix->n > cap_for(k) && A >= 1 &&
+                          masked_ks(k, ix->n, A) != 0;
+    if (!possible || mode == BSR_MASK_LIST) return false;
+    return !(mode == BSR_MASK_AUTO && auto_prefers_list(ix->n, A, nq, k));
+}
+
+int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                                    uint64_t allow_words, uint32_t mode) {
+    bsr_index* ix = this;
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (k == 0 || k > ix->cfg.max_k) return set_error(BSR_E_INVALID, "k=%u outside [1, max_k=%u]", k, ix->cfg.max_k);
+    if (!allow) return set_error(BSR_E_INVALID, "null allow mask (bsr_local_top_k searches without one)");
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (allow_words != (n + 63) / 64)
+        return set_error(BSR_E_INVALID, "allow_words=%llu, the index holds %llu rows (%llu words)",
+                         (unsigned long long)allow_words, (unsigned long long)n, (unsigned long long)((n + 63) / 64));
+    BSR_HIP(hipSetDevice(ix->device));
+    stats = bsr_search_stats{};
+    stats.n_queries = nq;
+    stats.filter_op = 0;
+    stats.row_ebound = row_ebound;
+    BSR_TRY(prepare_result(nq, k));
+    uint32_t* next_status = res[cur ^ 1u].as<uint32_t>();
+    if (nq == 0) return BSR_OK;
+    if (!queries) return set_error(BSR_E_INVALID, "null queries");
+
+    const uint32_t qpad = nq <= kSkinnyMaxQ ? kSkinnyMaxQ : (uint32_t)round_up(nq, kFilterTile);
+    BSR_TRY(qf32.ensure((size_t)qpad * ld * sizeof(float)));
+    BSR_TRY(nb.ensure((size_t)qpad * sizeof(float)));
+    BSR_TRY(qop.ensure((size_t)qpad * op_row_bytes));
+    BSR_TRY(qscale.ensure((size_t)qpad * sizeof(float)));
+    BSR_TRY(ebound.ensure((size_t)qpad * sizeof(float)));
+    BSR_TRY(qflags.ensure((size_t)qpad * sizeof(uint32_t)));
+    BSR_TRY(qids_id.ensure((size_t)qpad * sizeof(int32_t)));
+    BSR_TRY(keys.ensure((size_t)nq * k * sizeof(uint64_t)));
+    BSR_TRY(mask_aux.ensure(((size_t)qpad + 1) * sizeof(uint32_t)));
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = queries;
+    if (!is_device_ptr(queries)) {
+        BSR_TRY(q_in.ensure((size_t)nq * dim * sizeof(float)));
+        BSR_HIP(hipMemcpyAsync(q_in.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, stream));
+        qsrc = q_in.as<float>();
+    }
+    // The mask on the device, and the number of allowed rows A: the host needs it for the path,
+    // the list's size and the result count min(k, A).
+    const uint64_t* dmask = allow;
+    uint32_t A = 0;
+    if (n > 0) {
+        if (!is_device_ptr(allow)) {
+            BSR_TRY(mask_dev.ensure((size_t)allow_words * sizeof(uint64_t)));
+            BSR_HIP(hipMemcpyAsync(mask_dev.p, allow, (size_t)allow_words * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                   stream));
+            dmask = mask_dev.as<uint64_t>();
+        }
+        const uint32_t n_blk = mask_blocks(n);
+        BSR_TRY(mask_blk.ensure(((size_t)n_blk + 1) * sizeof(uint32_t)));
+        BSR_HIP(launch_mask_list_count(dmask, n, mask_blk.as<uint32_t>(), stream));
+        BSR_HIP(hipMemcpyAsync(&A, mask_blk.as<uint32_t>() + n_blk, sizeof A, hipMemcpyDeviceToHost, stream));
+        BSR_HIP(hipStreamSynchronize(stream));
+    }
+    const bool use_filter = masked_filter_path(ix, mode, A, nq, k);
+    const uint32_t ks_m = use_filter ? masked_ks(k, n, A) : 0u;
+    const uint32_t cap_m = 128u * ks_m;  // (cap_for / ks_for's ratio)
+    stats.search_path |= use_filter ? BSR_PATH_MASK_FILTER : BSR_PATH_MASK_LIST;
+
+    QueryPrepArgs qa{};
+    qa.q = qsrc;
+    qa.nq = nq;
+    qa.qpad = qpad;
+    qa.dim = dim;
+    qa.ld = ld;
+    qa.ea_max = flags.as<uint32_t>() + 1;
+    qa.qf32 = qf32.as<float>();
+    qa.nb = nb.as<float>();
+    qa.qop = qop.p;
+    qa.qscale = qscale.as<float>();
+    qa.ebound = ebound.as<float>();
+    qa.qflags = qflags.as<uint32_t>();
+    qa.qids = qids_id.as<int32_t>();
+    qa.status = d_status;
+    qa.with_op = use_filter;
+    BSR_HIP(launch_query_prep(qa, stream));
+
+    // The list: the fallback of the filter path builds it only when a query needs it.
+    bool have_list = false;
+    auto build_list = [&]() -> int {
+        if (have_list || !A) return BSR_OK;
+        BSR_TRY(mask_list.ensure((size_t)A * sizeof(uint32_t)));
+        BSR_HIP(launch_mask_list_scatter(dmask, n, mask_blk.as<uint32_t>(), A, mask_list.as<uint32_t>(), stream));
+        have_list = true;
+        return BSR_OK;
+    };
+    auto finalize_and_read = [&]() -> int {
+        BSR_HIP(launch_finalize(keys.as<uint64_t>(), nq, k, A, global_offset, d_idx, d_dist, d_cnt, next_status,
+                                nullptr, d_status, stream));
+        next_status_clean = true;
+        ev_end(ix, ev_total);
+        BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, res_bytes, hipMemcpyDeviceToHost, stream));
+        BSR_HIP(stream_wait(stream));
+        return BSR_OK;
+    };
+    auto check_queries = [&]() -> int {
+        const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+        if (!(st[kStQueryFlags] & kQueryNonFinite)) return BSR_OK;
+        h_qflags.resize(nq);
+        BSR_HIP(hipMemcpy(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        uint32_t bad = 0;
+        while (bad < nq && !(h_qflags[bad] & kQueryNonFinite)) ++bad;
+        return set_error(BSR_E_NONFINITE, "query %u contains NaN/Inf (the reference panics)", bad);
+    };
+
+    if (!use_filter) {
+        // the list path: every query by the exact scan of the allowed rows
+        stats.n_exact_direct = nq;
+        if (A) {
+            BSR_TRY(build_list());
+            BSR_TRY(run_list_scan(ix, qids_id.as<int32_t>(), nq, k, A));
+        } else {
+            BSR_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(uint64_t), stream));
+        }
+        BSR_TRY(finalize_and_read());
+        return check_queries();
+    }
+
+    // The filter path: the threshold lowered by 1 / rho, the emitted lists cut by the mask, every
+    // remaining row of every query rescored exactly and certified against tau0 (mode B).
+    BSR_TRY(sample_pass(ix, nq, qpad, k, nullptr, ks_m, cap_m));
+    BSR_TRY(emit_pass(ix, nq, qpad, k, cap_m));
+    uint32_t* raw_cnt = mask_aux.as<uint32_t>();
+    uint32_t* items = raw_cnt + qpad;
+    BSR_HIP(launch_mask_cut(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dmask, n, raw_cnt, items, stream));
+    ev_begin(ix, ev_rescore);
+    RescoreArgs rb{};
+    rb.rows = rows.as<float>();
+    rb.ld = ld;
+    rb.dim = dim;
+    rb.na = na.as<float>();
+    rb.qf32 = qf32.as<float>();
+    rb.nb = nb.as<float>();
+    rb.n_items = nq;
+    rb.n_items_dev = items;
+    rb.qlist = reinterpret_cast<const uint32_t*>(qids_id.as<int32_t>());  // (identity for q < nq)
+    rb.kp = kp_for(k);
+    rb.cand_keys = cand.as<uint64_t>();
+    rb.cnt = cnt.as<uint32_t>();
+    rb.cap = cap_m;
+    rb.tau0 = tau.as<float>();
+    rb.k = k;
+    rb.ebound = ebound.as<float>();
+    rb.out_keys = keys.as<uint64_t>();
+    rb.fail_cnt = d_status + kStFail2;
+    rb.fail_list = fail2.as<uint32_t>();
+    rb.res_idx = d_idx;
+    rb.res_dist = d_dist;
+    rb.res_cnt = d_cnt;
+    rb.offset = global_offset;
+    rb.n_rows = A;  // (the fused finalize's count: min(k, A))
+    rb.next_status = next_status;
+    rb.emit_cnt = raw_cnt;
+    rb.cur_status = d_status;
+    rb.n_queries = nq;
+    BSR_HIP(launch_rescore(rb, stream));
+    ev_end(ix, ev_rescore);
+    next_status_clean = true;
+    ev_end(ix, ev_total);
+    BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, res_bytes, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(stream_wait(stream));
+    BSR_TRY(check_queries());
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+    stats.n_emitted = st[kStEmitted];
+    const uint32_t nfail = st[kStFail2];
+    if (nfail) {
+        // Uncertified queries (an overflowed list among them) and queries the filter cannot
+        // serve take the list scan: the reference's arithmetic on every allowed row.
+        h_fail.resize(nfail);
+        h_qflags.resize(nq);
+        BSR_HIP(hipMemcpyAsync(h_fail.data(), fail2.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        BSR_HIP(hipMemcpyAsync(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        BSR_HIP(hipStreamSynchronize(stream));
+        std::sort(h_fail.begin(), h_fail.end());
+        const uint32_t groups = (nfail + kScanQF - 1) / kScanQF;
+        std::vector<int32_t> padded((size_t)groups * kScanQF);
+        for (size_t i = 0; i < padded.size(); ++i)
+            padded[i] = (int32_t)(i < nfail ? h_fail[i] : h_fail[i / kScanQF * kScanQF]);
+        for (uint32_t q : h_fail) {
+            if (h_qflags[q] & kQueryNoApprox) ++stats.n_exact_direct;
+            else ++stats.n_fallback;
+        }
+        BSR_TRY(qids.ensure(padded.size() * sizeof(int32_t)));
+        BSR_HIP(hipMemcpyAsync(qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        stats.search_path |= BSR_PATH_MASK_LIST;
+        BSR_TRY(build_list());
+        BSR_TRY(run_list_scan(ix, qids.as<int32_t>(), nfail, k, A));
+        BSR_TRY(finalize_and_read());
+    }
+    return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // The parallel search's global emission threshold: phase A / phase B
 // ---------------------------------------------------------------------------------------
 bool bsr_index::gtau_eligible(uint32_t nq, uint32_t k) const {
@@ -1053,6 +1315,17 @@ int bsr_local_top_k_impl(bsr_index* ix, const float* queries, uint32_t nq, uint3
     if (!ix) return set_error(BSR_E_INVALID, "null index");
     if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
     BSR_TRY(ix->search_device(queries, nq, k));
+    BSR_TRY(copy_out(ix, nq, k, out_idx, out_dist, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+int bsr_local_top_k_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                                uint64_t allow_words, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    BSR_TRY(ix->search_device_masked(queries, nq, k, allow, allow_words, mode));
     BSR_TRY(copy_out(ix, nq, k, out_idx, out_dist, out_count));
     collect_profile(ix);
     return BSR_OK;

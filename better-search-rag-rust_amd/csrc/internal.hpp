@@ -144,6 +144,16 @@ struct bsr_index {
                       void* ctx = nullptr);
     int prepare_result(uint32_t nq, uint32_t k);
 
+    // The local search restricted to the rows an allow mask names (bsr_local_top_k_masked,
+    // DESIGN.md §10): launched directly, never captured, no publish flag; results where
+    // search_device leaves them.  allow: host or device words, ceil(n / 64) of them.
+    int search_device_masked(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                             uint64_t allow_words, uint32_t mode);
+    bsr::DevBuf mask_dev;   // a host mask's device copy
+    bsr::DevBuf mask_blk;   // u32 [mask_blocks(n) + 1]: block offsets, the allowed-row count
+    bsr::DevBuf mask_list;  // u32 [A]: the allowed rows, ascending
+    bsr::DevBuf mask_aux;   // u32 [qpad + 1]: emitted counts before the cut; the rescore's item count
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

@@ -1074,6 +1074,143 @@ __global__ __launch_bounds__(256, 2) void k_scan_exact(const float* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Exact top-k over a row list (masked search): k_scan_exact's tile loop with the
+// tile's 256 rows taken from list[] (ascending local row ids) instead of 256 consecutive rows.
+// Every listed row is gathered whole, 64-element chunks through LDS, and walked by its lane in
+// index order with the same arithmetic.  Thread t fetches entry t of the next tile a tile ahead
+// (it is also the row this lane will walk) and passes it to the loading threads through LDS,
+// so no row load waits for its id.  blockIdx.y: the query group.
+// ------------------------------------------------------------------------------------
+template <int QF, int E>
+__global__ __launch_bounds__(256, 2) void k_scan_list(const float* __restrict__ rows, uint32_t ld,
+                                                      uint32_t dim, const uint32_t* __restrict__ list,
+                                                      uint32_t n_list, const float* __restrict__ na,
+                                                      const float* __restrict__ qf32,
+                                                      const int32_t* __restrict__ qids_all,
+                                                      const float* __restrict__ nb, uint32_t k,
+                                                      uint64_t* __restrict__ part_all) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    __shared__ uint32_t s_ids[256];  // the rows of the tile being loaded
+    float* ldq = lds + 256 * 68;
+    const int t = threadIdx.x, w = t >> 6;
+    const uint32_t n_tiles = (n_list + 255) / 256;
+    const uint32_t nch = ld / 64;
+    const int32_t* qids = qids_all + (uint64_t)blockIdx.y * QF;
+    uint64_t* part = part_all + (uint64_t)blockIdx.y * gridDim.x * QF * k;
+
+    const float* qp[QF];
+    float mag_b[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        const int32_t id = qids[j];
+        qp[j] = qf32 + (uint64_t)id * ld;
+        mag_b[j] = nb[id];
+    }
+    WaveTopK<E> L[QF];
+    uint64_t thr[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) { L[j].init(); thr[j] = kKeyNone; }
+
+    // This lane's 16 loads of a tile chunk: list entry (i*256+t)>>4 of the tile, float4 (t&15).
+    const uint32_t lrow0 = (uint32_t)t >> 4;   // + 16*i
+    const uint32_t lcol = ((uint32_t)t & 15) * 4;
+    uint32_t tile = blockIdx.x;
+    uint32_t ch = 0;
+    // entry t of a tile (past the list: row 0, loaded and never offered)
+    auto id_at = [&](uint64_t tl) -> uint32_t {
+        const uint64_t p = tl * 256 + t;
+        return p < n_list ? list[p] : 0u;
+    };
+    f32x4_t pre[16];
+    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
+    auto issue = [&](uint32_t c) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            pre[i] = *reinterpret_cast<const f32x4_t*>(rows + (uint64_t)s_ids[lrow0 + 16 * i] * ld + c * 64 + lcol);
+        if constexpr (QF > 1) {
+            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + c * 64);
+        }
+    };
+    // this lane's own row of the tile being walked and its magnitude; its entry of the next tile
+    uint32_t myrow = 0, idn = 0;
+    float mag_a = 0.0f;
+    if (tile < n_tiles) {
+        myrow = id_at(tile);
+        idn = id_at((uint64_t)tile + gridDim.x);
+        s_ids[t] = myrow;
+        __syncthreads();
+        issue(0);
+        mag_a = na[myrow];
+    }
+    float acc[QF], mx[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+
+    while (tile < n_tiles) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
+        if constexpr (QF > 1) {
+            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
+        }
+        // (the last chunk's loads are out: the next loads are the next tile's.  Without a next
+        // tile idn is row 0 everywhere and the reload below fetches it in vain.)
+        if (ch == nch - 1) s_ids[t] = idn;
+        __syncthreads();
+        // next (tile, chunk); past the end: reload the current chunk (branch-free prefetch)
+        uint32_t nch_ = ch + 1;
+        if (nch_ == nch) nch_ = (uint64_t)tile + gridDim.x < n_tiles ? 0u : ch;
+        issue(nch_);
+
+        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+        const float* bq[QF];
+#pragma unroll
+        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
+        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
+
+        if (ch == nch - 1) {
+            const bool valid = (uint64_t)tile * 256 + t < n_list;
+#pragma unroll
+            for (int j = 0; j < QF; ++j) {
+                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+                L[j].offer(valid ? dist_key(d, myrow) : kKeyNone, (int)k, thr[j]);
+                acc[j] = -0.0f;
+                mx[j] = 0.0f;
+            }
+            ch = 0;
+            tile += gridDim.x;
+            myrow = idn;
+            idn = id_at((uint64_t)tile + gridDim.x);
+            mag_a = na[myrow];
+        } else {
+            ++ch;
+        }
+    }
+
+    // Block merge: 4 wave lists per query -> one list per query.
+    __syncthreads();
+    uint64_t* lk = reinterpret_cast<uint64_t*>(lds);  // [4][QF][64E] keys (<= 64 KiB)
+#pragma unroll
+    for (int j = 0; j < QF; ++j) L[j].store(lk + ((uint64_t)w * QF + j) * 64 * E, (int)k);
+    __syncthreads();
+    for (int j = w; j < QF; j += 4) {
+        WaveTopK<E> M;
+        M.init();
+        uint64_t mt = kKeyNone;
+        for (int s = 0; s < 4; ++s) {
+            const uint64_t* src = lk + ((uint64_t)s * QF + j) * 64 * E;
+            for (uint32_t base = 0; base < k; base += kWave) {
+                const uint32_t i = base + (t & 63);
+                M.offer(i < k ? src[i] : kKeyNone, (int)k, mt);
+            }
+        }
+        M.store(part + ((uint64_t)blockIdx.x * QF + j) * k, (int)k);
+    }
+}
+
 // Per scanned query: merge the per-block lists of k_scan_exact into out_keys[qid].  Four
 // waves each take a quarter of the grid's lists (loads issued 4 deep), then wave 0 merges
 // the four wave lists through LDS.
@@ -1548,6 +1685,37 @@ hipError_t launch_scan_exact(const float* rows, uint32_t ld, uint32_t dim, uint6
     else if (nqf <= 2) launch_scan_qf<2>(rows, ld, dim, n, na, qf32, qids, nb, k, grid, part, s);
     else if (nqf <= 4) launch_scan_qf<4>(rows, ld, dim, n, na, qf32, qids, nb, k, grid, part, s);
     else launch_scan_qf<8>(rows, ld, dim, n, na, qf32, qids, nb, k, grid, part, s);
+    return hipGetLastError();
+}
+
+template <int QF>
+static void launch_list_qf(const float* rows, uint32_t ld, uint32_t dim, const uint32_t* list, uint32_t n_list,
+                           const float* na, const float* qf32, const int32_t* qids, uint32_t groups,
+                           const float* nb, uint32_t k, uint32_t grid, uint64_t* part, hipStream_t s) {
+    const uint32_t e = (k + 63) / 64;
+#define BSR_LIST(E)                                                                                 \
+    hipLaunchKernelGGL((k_scan_list<QF, E>), dim3(grid, groups), dim3(256), 0, s, rows, ld, dim, list, \
+                       n_list, na, qf32, qids, nb, k, part)
+    switch (e) {
+        case 1: BSR_LIST(1); break;
+        case 2: BSR_LIST(2); break;
+        case 3: BSR_LIST(3); break;
+        default: BSR_LIST(4); break;
+    }
+#undef BSR_LIST
+}
+
+hipError_t launch_scan_list(const float* rows, uint32_t ld, uint32_t dim, const uint32_t* list, uint32_t n_list,
+                            const float* na, const float* qf32, const int32_t* qids, uint32_t nqf,
+                            uint32_t groups, const float* nb, uint32_t k, uint32_t grid, uint64_t* part,
+                            hipStream_t s) {
+    // (the template widths and the part layout are launch_scan_exact's, so launch_merge_parts
+    // reads a group's lists back with the same nqf)
+    if (!n_list || !groups || groups > 65535 || (groups > 1 && nqf != kScanQF)) return hipErrorInvalidValue;
+    if (nqf <= 1) launch_list_qf<1>(rows, ld, dim, list, n_list, na, qf32, qids, groups, nb, k, grid, part, s);
+    else if (nqf <= 2) launch_list_qf<2>(rows, ld, dim, list, n_list, na, qf32, qids, groups, nb, k, grid, part, s);
+    else if (nqf <= 4) launch_list_qf<4>(rows, ld, dim, list, n_list, na, qf32, qids, groups, nb, k, grid, part, s);
+    else launch_list_qf<8>(rows, ld, dim, list, n_list, na, qf32, qids, groups, nb, k, grid, part, s);
     return hipGetLastError();
 }
 

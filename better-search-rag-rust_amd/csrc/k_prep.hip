@@ -470,6 +470,130 @@ __global__ __launch_bounds__(256) void k_header_publish(const int32_t* __restric
     if (threadIdx.x == 0) __hip_atomic_store(host_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ------------------------------------------------------------------------------------
+// Masked search: the allow mask as a list of row ids, and the emitted lists cut
+// by the mask.  Bit (i & 63) of word (i >> 6) allows local row i; bits at positions >= n are
+// ignored.  The list is built in three deterministic steps -- per-block popcounts (a block =
+// kMaskBlockWords words), one workgroup's exclusive scan of them, a scatter -- so the ids come
+// out ascending: the list scan then walks the slab front to back.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t mask_word(const uint64_t* __restrict__ allow, uint64_t w, uint64_t n) {
+    const uint64_t lo = w * 64;
+    if (lo >= n) return 0;
+    const uint64_t x = allow[w];
+    return n - lo >= 64 ? x : x & ((1ull << (n - lo)) - 1ull);
+}
+
+// The workgroup's 256 per-thread counts: this thread's exclusive prefix, *total = their sum.
+__device__ __forceinline__ uint32_t block_exclusive_256(uint32_t v, uint32_t* s_wave, uint32_t* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)inc, d, kWave);
+        if (lane >= d) inc += y;
+    }
+    __syncthreads();  // (s_wave may still be read from an earlier call)
+    if (lane == 63) s_wave[w] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t c = s_wave[i];
+        before += i < w ? c : 0u;
+        all += c;
+    }
+    *total = all;
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(256) void k_mask_count(const uint64_t* __restrict__ allow, uint64_t n,
+                                                    uint32_t* __restrict__ blk) {
+    __shared__ uint32_t s_wave[4];
+    const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
+    uint32_t total;
+    (void)block_exclusive_256((uint32_t)__popcll(mask_word(allow, w, n)), s_wave, &total);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+}
+
+// blk[0..n_blk) -> their exclusive prefix sums, blk[n_blk] = the number of allowed rows.
+__global__ __launch_bounds__(256) void k_mask_scan(uint32_t* __restrict__ blk, uint32_t n_blk) {
+    __shared__ uint32_t s_wave[4];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n_blk; base += 256) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < n_blk ? blk[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_256(v, s_wave, &total);
+        if (i < n_blk) blk[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) blk[n_blk] = carry;
+}
+
+__global__ __launch_bounds__(256) void k_mask_scatter(const uint64_t* __restrict__ allow, uint64_t n,
+                                                      const uint32_t* __restrict__ blk, uint32_t n_list,
+                                                      uint32_t* __restrict__ list) {
+    __shared__ uint32_t s_wave[4];
+    const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
+    uint64_t x = mask_word(allow, w, n);
+    uint32_t total;
+    uint32_t pos = blk[blockIdx.x] + block_exclusive_256((uint32_t)__popcll(x), s_wave, &total);
+    while (x) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(x);
+        x &= x - 1;
+        if (pos < n_list) list[pos] = (uint32_t)(w * 64 + b);
+        ++pos;
+    }
+}
+
+// One wave per query: cand[q][0 .. cnt[q]) compacted in place to the keys whose row is allowed,
+// cnt[q] rewritten; raw[q] keeps the emitted count.  A chunk of 64 keys is read before anything
+// is written at or below it, so the compaction needs no second buffer.  An overflowed list
+// (cnt[q] > cap: rows were dropped) is left as it is -- it must stay overflowed.  *items = nq (the
+// device-counted rescore that follows reads its item count there).
+__global__ __launch_bounds__(256) void k_mask_cut(uint64_t* __restrict__ cand, uint32_t* __restrict__ cnt,
+                                                  uint32_t cap, uint32_t nq, const uint64_t* __restrict__ allow,
+                                                  uint64_t n, uint32_t* __restrict__ raw,
+                                                  uint32_t* __restrict__ items) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *items = nq;
+    if (q >= nq) return;
+    const uint32_t c = cnt[q];
+    if (lane == 0) raw[q] = c;
+    if (c > cap) return;
+    uint64_t* keys = cand + (uint64_t)q * cap;
+    uint32_t out = 0;
+    for (uint32_t base = 0; base < c; base += kWave) {
+        const uint32_t i = base + lane;
+        const uint64_t key = i < c ? keys[i] : kKeyNone;
+        const uint32_t row = key_row(key);
+        const bool keep = key != kKeyNone && row < n && ((allow[row >> 6] >> (row & 63)) & 1ull);
+        const uint64_t m = __ballot(keep);
+        if (keep) keys[out + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = key;
+        out += (uint32_t)__popcll(m);
+    }
+    if (lane == 0) cnt[q] = out;
+}
+
+hipError_t launch_mask_list_count(const uint64_t* allow, uint64_t n, uint32_t* blk, hipStream_t s) {
+    const uint32_t n_blk = mask_blocks(n);
+    hipLaunchKernelGGL(k_mask_count, dim3(n_blk), dim3(256), 0, s, allow, n, blk);
+    hipLaunchKernelGGL(k_mask_scan, dim3(1), dim3(256), 0, s, blk, n_blk);
+    return hipGetLastError();
+}
+hipError_t launch_mask_list_scatter(const uint64_t* allow, uint64_t n, const uint32_t* blk, uint32_t n_list,
+                                    uint32_t* list, hipStream_t s) {
+    hipLaunchKernelGGL(k_mask_scatter, dim3(mask_blocks(n)), dim3(256), 0, s, allow, n, blk, n_list, list);
+    return hipGetLastError();
+}
+hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
+                           uint64_t n, uint32_t* raw, uint32_t* items, hipStream_t s) {
+    hipLaunchKernelGGL(k_mask_cut, dim3((nq + 3) / 4), dim3(256), 0, s, cand, cnt, cap, nq, allow, n, raw, items);
+    return hipGetLastError();
+}
+
 hipError_t launch_synth_uniform(float* out, uint64_t row0, uint64_t n_rows, uint32_t dim,
                                 uint32_t ld, uint64_t seed, hipStream_t s) {
     hipLaunchKernelGGL(k_synth_uniform, dim3(grid_for(n_rows * ld, 256)), dim3(256), 0, s, out, row0,

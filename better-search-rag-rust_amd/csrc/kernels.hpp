@@ -77,6 +77,25 @@ hipError_t launch_header_publish(const int32_t* src, uint32_t words, int32_t* ho
 hipError_t launch_gather_emulate(const void* send, const void* script, void* recv, uint64_t bytes, uint32_t P,
                                  uint32_t rank, hipStream_t s);
 
+// Masked search.  The allow mask: bit (i & 63) of word (i >> 6) allows local row
+// i; bits at positions >= n are ignored.  Its row list is built in two launches around the
+// host's read of the count: blk [mask_blocks(n) + 1] receives the exclusive prefix sums of the
+// per-block popcounts and, in its last word, the number of allowed rows A; the scatter then
+// writes the A ids in ascending order.
+constexpr uint32_t kMaskBlockWords = 256;  // mask words per workgroup of the list build
+static inline uint32_t mask_blocks(uint64_t n) {
+    const uint64_t words = (n + 63) / 64, b = (words + kMaskBlockWords - 1) / kMaskBlockWords;
+    return (uint32_t)(b < 1 ? 1 : b);
+}
+hipError_t launch_mask_list_count(const uint64_t* allow, uint64_t n, uint32_t* blk, hipStream_t s);
+hipError_t launch_mask_list_scatter(const uint64_t* allow, uint64_t n, const uint32_t* blk, uint32_t n_list,
+                                    uint32_t* list, hipStream_t s);
+// The emitted lists cut by the mask: cand[q][0 .. cnt[q]) compacted in place to the keys of
+// allowed rows and cnt[q] rewritten (an overflowed list, cnt[q] > cap, is left overflowed);
+// raw[q] = the emitted count; *items = nq.
+hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
+                           uint64_t n, uint32_t* raw, uint32_t* items, hipStream_t s);
+
 // ---- MFMA candidate filter (k_filter.hip) ---------------------------------------------
 struct GemmArgs {
     const uint8_t* A;       // filter rows [n_pad][row_bytes]
@@ -260,6 +279,14 @@ hipError_t launch_scan_exact(const float* rows, uint32_t ld, uint32_t dim, uint6
                              uint64_t* part, hipStream_t s);
 hipError_t launch_merge_parts(const uint64_t* part, uint32_t grid, const int32_t* qids,
                               uint32_t nqf, uint32_t k, uint64_t* out_keys, hipStream_t s);
+// Exact top-k over a row list (masked search): the n_list rows list[0 .. n_list) of the slab
+// (local ids, each < n), gathered whole, for `groups` groups of queries in one launch -- group g
+// takes the ids qids[g * kScanQF ..] and writes its partial lists to part + g * grid * kScanQF * k
+// (launch_merge_parts' layout).  groups > 1 needs nqf == kScanQF; n_list >= 1.
+hipError_t launch_scan_list(const float* rows, uint32_t ld, uint32_t dim, const uint32_t* list,
+                            uint32_t n_list, const float* na, const float* qf32, const int32_t* qids,
+                            uint32_t nqf, uint32_t groups, const float* nb, uint32_t k, uint32_t grid,
+                            uint64_t* part, hipStream_t s);
 // The root's merge of gathered [P][nq][k_in] lists (counts [P][nq]) into [nq][k] outputs on
 // the device (compute_global_top_k); P <= 64, P * k_in <= kMergeMaxEntries, k <= 256.
 // *first_nan must hold ~0 before the launch; afterwards the lowest query with a NaN distance.

@@ -108,7 +108,8 @@ typedef struct {
 } bsr_search_stats;
 
 /* bsr_search_stats.search_path: which branches the last search took (bits 1-16: the parallel
- * search; 32, 64: a batch of <= 16 queries on the self-thresholded path) */
+ * search; 32, 64: a batch of <= 16 queries on the self-thresholded path; 128,
+ * 256: bsr_local_top_k_masked -- both when the filter path sent some queries to the list scan) */
 #define BSR_PATH_COLLECTIVE 1u   /* the collectives ran (size > 1, or BSR_FORCE_COLLECTIVES=1) */
 #define BSR_PATH_GLOBAL_TAU 2u   /* the global-threshold search */
 #define BSR_PATH_DIRECT_OUT 4u   /* root: merged rows written straight into coherent pinned outputs */
@@ -116,6 +117,8 @@ typedef struct {
 #define BSR_PATH_FALLBACK 16u    /* global threshold: uncertified queries took the collective fallback */
 #define BSR_PATH_SKINNY_TOP 32u  /* no sample pass: every filter wave's 4 best keys per query */
 #define BSR_PATH_TOP_RERUN 64u   /* ... left a query uncertified: the batch ran again, thresholded */
+#define BSR_PATH_MASK_LIST   128u /* masked search: exact top-k over the allowed-row list */
+#define BSR_PATH_MASK_FILTER 256u /* masked search: int8 filter, emitted lists cut by the mask */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -163,6 +166,33 @@ int bsr_index_get_many(const bsr_index* ix, uint64_t offset, uint64_t count, flo
  * in (distance asc, global index asc) order.  Indices are global (offset added). ------ */
 int bsr_local_top_k(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
                     uint64_t* out_idx, float* out_dist, uint32_t* out_count);
+
+/* ---- a-2 over an allow-list of rows: compute_local_top_k as if the store held only the allowed
+ * rows, each keeping its global index.  allow is ONE bitset for the whole batch: bit (i & 63) of
+ * word (i >> 6) is set when local row i may be returned; host or device memory, detected per
+ * call (a device mask produced on a non-default stream must be complete before the call, as
+ * queries).  allow_words must equal ceil(n / 64) for the index's current row count n
+ * (BSR_E_INVALID otherwise); bits at positions >= n are ignored.  allow == NULL or an unknown
+ * mode: BSR_E_INVALID (a search without a mask is bsr_local_top_k).  With A allowed rows,
+ * out_count[q] = min(k, A) entries in (distance asc, global index asc) order with the
+ * reference's exact f32 distances; entries past the count are (~0, +inf).  A = 0 is not an
+ * error: every count is 0.  Every other status as bsr_local_top_k.
+ * mode picks the path (bsr_search_stats.search_path reports it; results are identical):
+ *   BSR_MASK_LIST    an exact top-k over the list of allowed rows: cost scales with A;
+ *   BSR_MASK_FILTER  the int8 filter over the whole shard with its threshold lowered by n / A,
+ *                    the emitted lists cut by the mask, every remaining row rescored exactly and
+ *                    certified; uncertified queries take the list scan.  Possible when the
+ *                    unmasked search would filter (k <= 200, a shard of more rows than one
+ *                    query's candidate list) and A / n >= ks(k) / 128 (1/16 for k <= 10, 0.19
+ *                    for k = 50, 0.375 for k = 100); the list scan otherwise;
+ *   BSR_MASK_AUTO    the library's choice.
+ * Never graph-replayed (graph_replay = 0); it leaves the unmasked search's graphs as they are. */
+#define BSR_MASK_AUTO   0u
+#define BSR_MASK_LIST   1u
+#define BSR_MASK_FILTER 2u
+int bsr_local_top_k_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                           const uint64_t* allow, uint64_t allow_words, uint32_t mode,
+                           uint64_t* out_idx, float* out_dist, uint32_t* out_count);
 
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]

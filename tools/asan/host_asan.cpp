@@ -103,6 +103,14 @@ static void test_interval(std::mt19937_64& rng) {
     }
     bsr_rank_interval iv;
     EXPECT(bsr_interval_by_rank(4, 4, 10, &iv) == BSR_E_INVALID, "rank out of range accepted");
+    // the masked search's argument check that needs no device: a null index
+    const float q[4] = {1, 2, 3, 4};
+    const uint64_t allow = ~0ull;
+    uint64_t mi[2];
+    float md[2];
+    uint32_t mc = 0;
+    EXPECT(bsr_local_top_k_masked(nullptr, q, 1, 2, &allow, 1, BSR_MASK_AUTO, mi, md, &mc) == BSR_E_INVALID,
+           "masked search accepted a null index");
 }
 
 // ---- P ranks as P threads over an in-process host all-gather ---------------------------------
