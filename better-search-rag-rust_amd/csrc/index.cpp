@@ -454,16 +454,55 @@ static GemmArgs gemm_args(bsr_index* ix, uint32_t qpad) {
     return g;
 }
 
+// The sample of a batch (n > cap): every 32nd row (fop_s) scored one by one or -- compact, large
+// shards -- as maxima over 32 sampled rows; or, for the batched query-stationary filter in
+// compact mode, whole tiles of fop scored once (tiles != 0, GemmArgs::s_tiles): one 128-row
+// tile in 32, four values per tile, the same number of values per query as the compact sample.
+struct SampleLayout {
+    uint32_t n_s, n_rt_s;  // the fop_s sample: rows, 256-row tiles
+    bool compact;
+    uint32_t tiles;        // sample tiles of fop (0: the fop_s sample)
+    uint32_t s_ld, n_vals; // S: row length, valid values per query
+};
+// BSR_SAMPLE_TILES=0 (read per search, an A/B switch): the fop_s sample for every batch.  No shard
+// size limit: from 1M rows (no difference) to 10M (-2.4% per step) the sample tiles were never
+// slower than the fop_s sample at 1000 queries.
+static bool sample_tiles_on() {
+    const char* v = getenv("BSR_SAMPLE_TILES");
+    return !(v && v[0] == '0');
+}
+static SampleLayout sample_layout(const bsr_index* ix, uint32_t nq, uint32_t ks) {
+    SampleLayout L{};
+    const uint32_t BM = kFilterTile;
+    L.n_s = (uint32_t)((ix->n + kSampleStride - 1) / kSampleStride);
+    L.n_rt_s = (L.n_s + BM - 1) / BM;
+    L.compact = L.n_s >= 32u * 8u * ks;
+    const uint32_t nk = ix->op_row_bytes / 64;
+    const bool qs16 = ix->op_row_bytes % 64 == 0 && nk % 2 == 0 && nk >= 2 && nk <= 12;
+    if (L.compact && nq > kSkinnyMaxQ && qs16 && sample_tiles_on()) L.tiles = sample_tiles_for(ix->n);
+    if (L.tiles) {
+        // (the last sample tile may be the shard's partial last tile: its blocks with a valid row)
+        const uint64_t last0 = ((uint64_t)(L.tiles - 1) * kSampleTileEvery + kSampleTilePhase) * 128;
+        const uint64_t valid = std::min<uint64_t>(128, ix->n - last0);
+        L.s_ld = 4 * L.tiles;
+        L.n_vals = 4 * (L.tiles - 1) + (uint32_t)((valid + kQuantBlock - 1) / kQuantBlock);
+    } else {
+        L.s_ld = L.compact ? L.n_rt_s * (BM / 32) : L.n_rt_s * BM;
+        L.n_vals = L.compact ? (L.n_s + 31) / 32 : L.n_s;
+    }
+    return L;
+}
+
 static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax, uint32_t ks_in,
                        uint32_t cap_in) {
     BSR_TRY(filter_buffers(ix, nq, qpad, k, cap_in));
+    ix->smp_tiles = 0;
     const bool skinny = nq <= kSkinnyMaxQ;
     const uint32_t cap = cap_in ? cap_in : cap_for(k);
     // (k'+1)/8: about 8 x 32 = 256 rows reach tau0 for k <= 10.  Fewer (ks = (k'+1)/12, /16)
     // measured 1-2% less filter time and up to 1.3% of the queries falling back to the exact
     // scan (profiles/r02f_*): not worth it.
     const uint32_t ks = ks_in ? ks_in : ks_for(k);
-    const uint32_t BM = kFilterTile;
     const uint64_t n = ix->n;
     GemmArgs g = gemm_args(ix, qpad);
     uint32_t* status = ix->d_status;
@@ -471,21 +510,30 @@ static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, ui
         // tau0 from every 32nd row: the ks-th best sampled score, or (large shards) the
         // ks-th best maximum over 32 sampled rows -- never above the former, so at least
         // ~ks*32 rows of the shard reach it.
-        const uint32_t n_s = (uint32_t)((n + kSampleStride - 1) / kSampleStride);
-        const uint32_t n_rt_s = (n_s + BM - 1) / BM;
-        const bool compact = n_s >= 32u * 8u * ks;
-        const uint32_t s_ld = compact ? n_rt_s * (BM / 32) : n_rt_s * BM;
-        const uint32_t n_vals = compact ? (n_s + 31) / 32 : n_s;
+        const SampleLayout L = sample_layout(ix, nq, ks);
+        const uint32_t s_ld = L.s_ld, n_vals = L.n_vals;
         BSR_TRY(ix->S.ensure((size_t)qpad * s_ld * sizeof(float)));
-        g.A = ix->fop_s.as<uint8_t>();  // the sampled rows, contiguous
         g.a_stride = ix->op_row_bytes;
-        g.a_scale = ix->ascale_s.as<float>();
-        g.a_scale_rows = kSampleScaleRows;
-        g.n_rows = n_s;
-        g.n_rt = n_rt_s;
+        if (L.tiles) {
+            // sample tiles of fop, the emit pass's scales (gemm_args): scored here and nowhere else
+            g.a_scale_rows = kQuantBlock;
+            g.n_rows = (uint32_t)n;
+            g.n_rt = L.tiles;
+            g.s_tiles = L.tiles;
+            g.s_vals = n_vals;
+            ix->smp_tiles = L.tiles;
+            ix->smp_ld = s_ld;
+            ix->smp_vals = n_vals;
+        } else {
+            g.A = ix->fop_s.as<uint8_t>();  // the sampled rows, contiguous
+            g.a_scale = ix->ascale_s.as<float>();
+            g.a_scale_rows = kSampleScaleRows;
+            g.n_rows = L.n_s;
+            g.n_rt = L.n_rt_s;
+        }
         g.S = ix->S.as<float>();
         g.s_ld = s_ld;
-        g.s_compact = compact ? 1u : 0u;
+        g.s_compact = L.compact ? 1u : 0u;
         BSR_HIP(launch_timed(ix, ix->ev_sample, [&](hipEvent_t e0, hipEvent_t e1) {
             return skinny ? launch_filter_skinny_sample(g, ix->stream, e0, e1)
                           : launch_filter_sample(g, ix->stream, e0, e1);
@@ -514,9 +562,18 @@ static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint
     g.cap = cap_in ? cap_in : cap_for(k);
     // the last 1/kTailDiv of the row tiles are balanced dynamically (k_filter_qs16)
     g.tail = g.n_qt <= kTailCounters ? ix->cnt.as<uint32_t>() + qpad : nullptr;
+    // sample tiles (this batch's sample pass scored them): the emit filter skips them and the
+    // fix-up emits their rows from S and the final threshold (one more kernel in the stream)
+    g.s_tiles = skinny ? 0u : ix->smp_tiles;
+    g.S = ix->S.as<float>();
+    g.s_ld = ix->smp_ld;
+    g.s_vals = ix->smp_vals;
+    g.n_q = nq;
     BSR_HIP(launch_timed(ix, ix->ev_emit, [&](hipEvent_t e0, hipEvent_t e1) {
-        return skinny ? launch_filter_skinny_emit(g, ix->stream, e0, e1)
-                      : launch_filter_emit(g, ix->stream, e0, e1);
+        hipError_t r = skinny ? launch_filter_skinny_emit(g, ix->stream, e0, e1)
+                              : launch_filter_emit(g, ix->stream, e0, e1);
+        if (r == hipSuccess && g.s_tiles) r = launch_sample_fixup(g, ix->stream);
+        return r;
     }));
     return BSR_OK;
 }
@@ -784,7 +841,8 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
     const bool graphable = use_filter && n > 0 && (!profiling(ix) || prof_level == 0) && !force_threshold;
     SearchGraph& gs = graphs[cur];
     // (the graph key: the TOP row layout and the skinny filter's A/B switch, both read per search)
-    const uint32_t lay = (top ? top_layout_lab() : 2u) | (skinny_glds_on() ? 0x100u : 0u);
+    const uint32_t lay = (top ? top_layout_lab() : 2u) | (skinny_glds_on() ? 0x100u : 0u) |
+                         (sample_tiles_on() ? 0x200u : 0u);
     const bool same_shape = warm.nq == nq && warm.k == k && warm.qsrc == qsrc && warm.n == n &&
                             warm.timed == (profiling(ix) ? prof_level : 0) && warm.top == top &&
                             warm.top_layout == lay;
@@ -1186,11 +1244,7 @@ int bsr_index::gtau_prepare(const float* queries, uint32_t nq, uint32_t k) {
     BSR_TRY(smax.ensure((size_t)qpad * ks * sizeof(uint64_t)));
     if (!is_device_ptr(queries)) BSR_TRY(q_in.ensure((size_t)nq * dim * sizeof(float)));
     BSR_TRY(filter_buffers(this, nq, qpad, k));
-    const uint32_t n_s = (uint32_t)((n + kSampleStride - 1) / kSampleStride);
-    const uint32_t n_rt_s = (n_s + kFilterTile - 1) / kFilterTile;
-    const bool compact = n_s >= 32u * 8u * ks;
-    const uint32_t s_ld = compact ? n_rt_s * (kFilterTile / 32) : n_rt_s * kFilterTile;
-    BSR_TRY(S.ensure((size_t)qpad * s_ld * sizeof(float)));  // (sample_pass's size)
+    BSR_TRY(S.ensure((size_t)qpad * sample_layout(this, nq, ks).s_ld * sizeof(float)));  // (sample_pass's size)
     gt_nq = nq;
     gt_k = k;
     gt_qpad = qpad;

@@ -82,6 +82,10 @@ struct bsr_index {
     bsr::DevBuf fop;    // filter operand rows: int8 [n_pad][ld]
     bsr::DevBuf fop_s;  // every kSampleStride-th row as the sample pass's operand, contiguous
     bsr::DevBuf ascale_s; // int8: f32 [n_s_pad / kSampleScaleRows] sample operand scales
+    // The sample of the batch in flight (set by its sample pass, read by its emit pass): sample
+    // tiles of fop scored once (GemmArgs::s_tiles; 0: the fop_s sample), the row length of S and
+    // its valid values per query.
+    uint32_t smp_tiles = 0, smp_ld = 0, smp_vals = 0;
     bsr::DevBuf ascale; // int8: f32 [n_pad/32] block scales
     bsr::DevBuf flags;  // u32 [2]: row flags, int8 row error bound (f32 bits)
 

@@ -16,6 +16,7 @@
 
 #include <hip/hip_ext.h>
 
+#include <limits.h>
 #include <math.h>
 
 #include <algorithm>
@@ -426,6 +427,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_filter(GemmArgs p) {
 // to the per-query global lists at the end or when a block could overfill it.
 // SAMPLE: every tile row is one sampled corpus row; the scores (or one maximum per 32
 // sampled rows) go to S.
+// Sample tiles (GemmArgs::s_tiles): SAMPLE reads one emit tile in 32 of the
+// emit operand, with its block scales, and EMIT walks the others -- one integer map per tile
+// (phys()) between the schedule's logical tiles and the rows, scales and row ids; the loop, the
+// barriers and the wait counts are the same.  k_sample_fixup (below) emits the sample tiles' rows.
 // ------------------------------------------------------------------------------------
 // s_waitcnt vmcnt(N) lgkmcnt(0) + s_barrier for a runtime N in [0, 15] (immediate operand).
 __device__ __forceinline__ void qs_barrier(uint32_t n) {
@@ -578,7 +583,15 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
 
     const uint32_t b = blockIdx.x, xcd = b & 7, slot = b >> 3;
     const uint32_t G = (gridDim.x >> 3) / p.n_qt;
-    const uint32_t n_rt = (p.n_rows + BM - 1) / BM;
+    // Sample tiles (p.s_tiles != 0): the schedule below runs over LOGICAL tiles -- the sample pass
+    // over the s_tiles sample tiles, the emit pass over the others -- and phys() names a logical
+    // tile's 128 rows wherever rows, scales or row ids are addressed.
+    const uint32_t n_phys = (p.n_rows + BM - 1) / BM;
+    const uint32_t n_rt = !p.s_tiles ? n_phys : EMIT ? n_phys - p.s_tiles : p.s_tiles;
+    auto phys = [&](uint32_t lt) -> uint32_t {
+        if (!p.s_tiles) return lt;
+        return EMIT ? lt + lt / (kSampleTileEvery - 1) : lt * kSampleTileEvery + kSampleTilePhase;
+    };
     const bool active = slot < G * p.n_qt;
     const uint32_t qt = active ? slot % p.n_qt : 0;
 #ifdef BSR_FILTER_COUNTERS
@@ -745,7 +758,8 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     const uint32_t lchunk = ((lane & 3) ^ qs16_swz(lrow)) * 16;
     // Tile ti's descriptor (base = its first row) and this lane's byte offset in it (SAMPLE:
     // tail rows read the last valid row).
-    auto tile_src_rt = [&](uint32_t rt, __amdgpu_buffer_rsrc_t& rs, uint32_t& off) {
+    auto tile_src_rt = [&](uint32_t lt, __amdgpu_buffer_rsrc_t& rs, uint32_t& off) {
+        const uint32_t rt = phys(lt);
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (uint64_t)rt * BM * p.a_stride), 0,
                                                BM * (uint32_t)p.a_stride, 0x00020000);
         const uint32_t r = (EMIT || rt * BM + lrow < p.n_rows) ? lrow : p.n_rows - 1 - rt * BM;
@@ -875,7 +889,7 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
 #endif
     uint32_t t = 0;
     for (; cur_id != kEnd; ++t) {
-        const uint32_t rt = cur_id;
+        const uint32_t rt = phys(cur_id);
         BSR_FCNT(4);
         if (kStatic && t) {
             rs_cur = rs_nxt;
@@ -896,10 +910,20 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
         unsigned long long gold = 0;
         if (thr && tid == 0) gold = gang_raw();
         const int w0_req = ((req || thr) && w == 0) ? 1 : 0;
-        // SAMPLE: one scale for the tile's 128 sampled rows (a scalar load: counted in lgkmcnt,
-        // it leaves the DMA stream's vmcnt waits alone)
-        float sc_tile = 1.0f;
-        if constexpr (!EMIT) sc_tile = p.a_scale[rt * BM / kSampleScaleRows];
+        // SAMPLE: one scale for the tile's 128 sampled rows, or (sample tiles) the emit pass's
+        // four block scales (scalar loads: counted in lgkmcnt, they leave the DMA stream's vmcnt
+        // waits alone)
+        float sc_tile = 1.0f, sc_blk[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+        if constexpr (!EMIT) {
+            if (p.s_tiles) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) sc_blk[g] = p.a_scale[rt * (BM / kQuantBlock) + g];
+            } else {
+                sc_tile = p.a_scale[rt * BM / kSampleScaleRows];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) sc_blk[g] = sc_tile;
+            }
+        }
         static_for(std::make_integer_sequence<int, NK>{}, [&](auto KT) {
             constexpr int kt = decltype(KT)::value;
             const uint32_t jj = t * NK + kt;
@@ -996,18 +1020,27 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
             // group (row blocks 2g, 2g+1: the lane's 8 values, then across the four lanes of its
             // query by two VALU lane swaps), scored once; full = every row's score
             if (p.s_compact) {
+                // (sample tiles: the rows at or past n_rows of a partial last tile do not count)
+                const bool part = p.s_tiles && rt * BM + BM > p.n_rows;
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
 #pragma unroll
                     for (int nb = 0; nb < 2; ++nb) {
-                        const i32x4v_t& x = acc[2 * g][nb];
-                        const i32x4v_t& y = acc[2 * g + 1][nb];
+                        i32x4v_t x = acc[2 * g][nb], y = acc[2 * g + 1][nb];
+                        if (part) {
+                            const uint32_t r0 = rt * BM + g * 32 + 4 * (lane >> 4);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                x[r] = r0 + r < p.n_rows ? x[r] : INT_MIN;
+                                y[r] = r0 + 16 + r < p.n_rows ? y[r] : INT_MIN;
+                            }
+                        }
                         int m = max(max(max(x[0], x[1]), max(x[2], x[3])), max(max(y[0], y[1]), max(y[2], y[3])));
                         const auto p16 = __builtin_amdgcn_permlane16_swap(m, m, false, false);
                         m = max((int)p16[0], (int)p16[1]);
                         const auto p32 = __builtin_amdgcn_permlane32_swap(m, m, false, false);
                         m = max((int)p32[0], (int)p32[1]);
-                        const float v = ((float)m * sc_tile) * sbq[nb];
+                        const float v = ((float)m * sc_blk[g]) * sbq[nb];
                         if (lane < 16) sbuf[((t % kSampleTilesPerWG) * 4 + g) * BN + (qq[nb] - qt * BN)] = v;
                     }
                 if (t % kSampleTilesPerWG == kSampleTilesPerWG - 1 || t + 1 == my_rt) {
@@ -1230,6 +1263,91 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     }
 }
 
+
+// ------------------------------------------------------------------------------------
+// The sample tiles' share of the emission (p.s_tiles != 0).  The sample pass left in S[q][j] the
+// exact maximum emit score of sample block j (tile 32 (j >> 2) + kSampleTilePhase, its 32-row
+// block j & 3), and the emit pass walked every other tile; here each block with S[q][j] >= tau[q]
+// -- ties included: a block holds a row reaching tau iff its maximum does -- is scored again,
+// row by row, and the rows reaching tau are appended to the query's list as the emit pass
+// appends them.  About ks blocks per query pass (tau0 is the ks-th best of S), so the work is
+// reading S once and ~ks x 32 rows per query: HBM-bound, no MFMA.
+// One workgroup per query, four waves.  A wave looks at 64 values of S at a time and scores the
+// passing blocks itself: lane l takes rows (l >> 2) and 16 + (l >> 2) of the block, 16 bytes
+// (l & 3) of every 64-byte K slice against the query's (in registers); the four lanes of a row
+// add up their integer dot products -- the MFMA's exact sum -- and the score is the emit pass's
+// ((float)I * s_block) * s_query.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_sample_fixup(GemmArgs p) {
+    constexpr int NKM = 12, U = 4;  // K slices at most (the query-stationary filter's), S loads in flight
+    const uint32_t q = blockIdx.x;
+    const float tq = p.tau[q];
+    if (!(tq < INFINITY)) return;  // (a query the filter does not serve, or padding: it emits nothing)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t w0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 64;
+    const uint32_t c = lane & 3, rr = lane >> 2;
+    const int nk = p.row_bytes / kSliceB;
+    const float sbq = p.b_scale[q];
+    i32x4_t fb[NKM];
+#pragma unroll
+    for (int s = 0; s < NKM; ++s)
+        fb[s] = s < nk ? *reinterpret_cast<const i32x4_t*>(p.B + (uint64_t)q * p.row_bytes + s * kSliceB + c * 16)
+                       : i32x4_t{0, 0, 0, 0};
+    // one 32-row block (uniform j): its rows reaching tau to the query's list
+    auto block = [&](uint32_t j) {
+        const uint32_t r0 = ((j >> 2) * kSampleTileEvery + kSampleTilePhase) * 128 + (j & 3) * 32;
+        const float sc = p.a_scale[r0 / kQuantBlock];
+        i32x4_t fa[2][NKM];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const uint8_t* a = p.A + (uint64_t)(r0 + 16 * h + rr) * p.a_stride + c * 16;
+#pragma unroll
+            for (int s = 0; s < NKM; ++s)
+                if (s < nk) fa[h][s] = *reinterpret_cast<const i32x4_t*>(a + s * kSliceB);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            int acc = 0;
+#pragma unroll
+            for (int s = 0; s < NKM; ++s)
+                if (s < nk)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_sdot4(fa[h][s][e], fb[s][e], acc, false);
+            acc += (int)xor_lane32<1>((uint32_t)acc);
+            acc += (int)xor_lane32<2>((uint32_t)acc);
+            const float v = ((float)acc * sc) * sbq;
+            const uint32_t row = r0 + 16 * h + rr;
+            const bool pass = c == 0 && v >= tq && row < p.n_rows;
+            const uint64_t mk = __ballot(pass);
+            if (mk) {
+                uint32_t gp = 0;
+                if (lane == 0) gp = atomicAdd(p.cnt + q, (uint32_t)__builtin_popcountll(mk));
+                gp = __builtin_amdgcn_readfirstlane(gp);
+                const uint32_t pos = gp + (uint32_t)__builtin_popcountll(mk & ((1ull << lane) - 1ull));
+                if (pass && pos < p.cap) p.cand[(uint64_t)q * p.cap + pos] = score_key(v, row);
+            }
+        }
+    };
+    const float* srow = p.S + (uint64_t)q * p.s_ld;
+    for (uint32_t base = 0; base < p.s_vals; base += U * 256) {
+        float sv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t j = base + u * 256 + tid;
+            sv[u] = j < p.s_vals ? srow[j] : -INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t j = base + u * 256 + tid;
+            uint64_t m = __ballot(j < p.s_vals && sv[u] >= tq);
+            while (m) {
+                const uint32_t b = (uint32_t)__builtin_ctzll(m);
+                m &= m - 1;
+                block(base + u * 256 + w0 + b);
+            }
+        }
+    }
+}
 
 // ------------------------------------------------------------------------------------
 // Skinny int8 filter for batches of at most 16 queries (single-query latency path): the
@@ -2079,7 +2197,7 @@ hipError_t launch_filter_skinny_top(const GemmArgs& a, hipStream_t s, hipEvent_t
 static bool gang_possible(const GemmArgs& a, uint32_t grid) {
     if (!a.tail || a.n_qt < 2 || a.n_qt > 4) return false;
     const uint32_t G = (grid / 8) / a.n_qt, RG = 8 * G;
-    const uint32_t n_rt = (a.n_rows + 127) / 128, n_st = n_rt - n_rt / 8;  // (TAILX = 8)
+    const uint32_t n_rt = (a.n_rows + 127) / 128 - a.s_tiles, n_st = n_rt - n_rt / 8;  // (TAILX = 8)
     return RG && n_st && (n_st - 1) / RG + 1 >= kGangMinTiles;
 }
 
@@ -2109,6 +2227,12 @@ hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s, hipEvent_t e0,
 }
 hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     launch_filter<true>(a, s, e0, e1);
+    return hipGetLastError();
+}
+hipError_t launch_sample_fixup(const GemmArgs& a, hipStream_t s) {
+    const uint32_t nk = a.row_bytes / kSliceB;
+    if (!a.s_tiles || !a.n_q || nk < 1 || nk > 12 || a.row_bytes % kSliceB) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sample_fixup, dim3(a.n_q), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_select_tau(const float* S, uint32_t s_ld, uint32_t n_s, uint32_t nq, uint32_t qpad,

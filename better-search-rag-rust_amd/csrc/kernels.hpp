@@ -123,7 +123,17 @@ struct GemmArgs {
     uint32_t* status;
     uint32_t n_q;
     uint32_t top_layout;  // the skinny TOP row layout: 2 = the product strided pairs (0: lab, k_filter.hip)
+    // Sample tiles (int8 query-stationary kernel, compact sample; 0 = off): the sample is the
+    // s_tiles 128-row tiles 32 L + kSampleTilePhase of A itself, scored once -- the sample pass
+    // reads them with the emit scales (S[q][4 L + g] = the exact maximum emit score of the tile's
+    // g-th 32-row block), the emit pass walks the other tiles, and launch_sample_fixup emits the
+    // sample tiles' rows.  s_vals: the values of S per query that hold a valid row.
+    uint32_t s_tiles, s_vals;
 };
+constexpr uint32_t kSampleTileEvery = 32;  // one 128-row tile in 32 is a sample tile ...
+constexpr uint32_t kSampleTilePhase = 31;  // ... the last of each 32
+// Sample tiles of a shard of n rows: floor(ceil(n / 128) / 32).
+static inline uint32_t sample_tiles_for(uint64_t n) { return (uint32_t)(((n + 127) / 128) / kSampleTileEvery); }
 // Dynamic tail of the emit filter: 1/kTailDiv of the row tiles; counters per (XCD pool, query
 // tile) (<= kTailCounters query tiles) after the per-query counters, cnt[qpad + x * n_qt + qt].
 constexpr uint32_t kTailDiv = 8;
@@ -143,6 +153,12 @@ hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s, hipEvent_t e0 
                                 hipEvent_t e1 = nullptr);
 hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s, hipEvent_t e0 = nullptr,
                               hipEvent_t e1 = nullptr);
+// The sample tiles' share of the emission (a.s_tiles != 0; after the threshold is final, before
+// the rescore): for every query q < a.n_q and sample value S[q][j] >= tau[q] (ties included),
+// the 32 rows of that block are scored as the emit pass scores them and those reaching tau[q]
+// are appended to the query's list (the emit pass's keys, counters and overflow behaviour).
+// A query with tau = +inf (flagged, padding) emits nothing.
+hipError_t launch_sample_fixup(const GemmArgs& a, hipStream_t s);
 // int8 only, batches of <= 16 queries (query tile rows 0..15), HBM-bound: the same
 // contract as the two launches above.
 constexpr uint32_t kSkinnyMaxQ = 16;
