@@ -170,9 +170,9 @@ static inline void ev_end(bsr_index* ix, Events& e) {
 template <class F>
 static inline hipError_t launch_timed(bsr_index* ix, Events& e, F&& launch, int level = 1) {
     const bool timed = !ix->capturing && profiling(ix) && ix->prof_level >= level && e.a;
-    if (!timed) return launch((hipEvent_t) nullptr, (hipEvent_t) nullptr);
+    if (!timed) return launch();
     hipError_t r = hipEventRecord(e.a, ix->stream);
-    if (r == hipSuccess) r = launch((hipEvent_t) nullptr, (hipEvent_t) nullptr);
+    if (r == hipSuccess) r = launch();
     if (r == hipSuccess) r = hipEventRecord(e.b, ix->stream);
     e.armed = r == hipSuccess;
     return r;
@@ -379,35 +379,10 @@ static int run_exact_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uin
     return BSR_OK;
 }
 
-// The same for a host list of query ids (the fallback queries of a batch).
-static int run_exact_scan_list(bsr_index* ix, const std::vector<int32_t>& ids, uint32_t k) {
-    if (ids.empty()) return BSR_OK;
-    const uint32_t groups = (uint32_t)((ids.size() + kScanQF - 1) / kScanQF);
-    std::vector<int32_t> padded((size_t)groups * kScanQF);
-    for (uint32_t g = 0; g < groups; ++g)
-        for (uint32_t j = 0; j < kScanQF; ++j) {
-            const size_t i = (size_t)g * kScanQF + j;
-            padded[i] = i < ids.size() ? ids[i] : ids[(size_t)g * kScanQF];
-        }
-    BSR_TRY(ix->qids.ensure(padded.size() * sizeof(int32_t)));
-    BSR_HIP(hipMemcpyAsync(ix->qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                           ix->stream));
-    return run_exact_scan(ix, ix->qids.as<int32_t>(), (uint32_t)ids.size(), k);
-}
-
 static uint32_t kp_for(uint32_t k) { return 64u * ((3u * k + 34u + 63u) / 64u) - 1u; }
 static uint32_t cap_for(uint32_t k) { return 16u * (kp_for(k) + 1u); }
 
 static uint32_t ks_for(uint32_t k) { return (kp_for(k) + 1u) / 8u; }
-
-// Steps 2-3 of the candidate stage: the sample pass and tau0 (smax: also the ks best sample
-// keys per query, the input of a parallel search's global threshold), then the emit pass.
-// Batches of at most 16 queries use the skinny (HBM-bound, no LDS) filter kernels.
-// ks / cap (0: ks_for(k) / cap_for(k)): the masked search's lowered threshold and longer lists.
-static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax, uint32_t ks = 0,
-                       uint32_t cap = 0);
-static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t cap = 0);
-
 
 // The self-thresholded single-query path (round 6, DESIGN.md §5 tiny batches): batches of <= 16
 // queries over shards of >= kSkinnyTopMinRows rows, k' <= 63, rows of <= 16 K slices, with the
@@ -416,7 +391,7 @@ static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint
 // best of them.  Returns the lists' slots per query (0: the thresholded path).
 static uint32_t top_slots(const bsr_index* ix, uint32_t nq, uint32_t k) {
     const char* v = getenv("BSR_SKINNY_TOP");
-    if ((v && v[0] == '0') || ix->force_threshold) return 0;
+    if (v && v[0] == '0') return 0;
     if (nq > kSkinnyMaxQ || ix->n < kSkinnyTopMinRows || kp_for(k) > 63 || k > 64 || ix->op_row_bytes > 16 * 64 ||
         ix->ld % 64 != 0 || ix->ld > 1024 || !rescore_kp_enabled())
         return 0;
@@ -425,6 +400,8 @@ static uint32_t top_slots(const bsr_index* ix, uint32_t nq, uint32_t k) {
 }
 
 // Buffers of the candidate stage for a batch (k' = kp_for(k) candidates, lists of cap keys).
+// (top_slots whatever path the batch takes: the thresholded rerun of a self-thresholded batch finds
+// the lists that batch sized.)
 static int filter_buffers(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t cap_in = 0) {
     // k' candidates, (k'+1) % 64 == 0, about 3k: the k-th exact score must clear the (k'+1)-th
     // approximate one by E_q, and in a Gaussian-like tail that takes ~3x as many rows at
@@ -451,6 +428,18 @@ static GemmArgs gemm_args(bsr_index* ix, uint32_t qpad) {
     g.n_qt = qpad / kFilterTile;
     g.a_scale = ix->ascale.as<float>();
     g.b_scale = ix->qscale.as<float>();
+    return g;
+}
+// ... of a pass over every row of the shard that emits into the candidate lists (emit_pass, top_pass)
+static GemmArgs emit_args(bsr_index* ix, uint32_t nq, uint32_t qpad) {
+    GemmArgs g = gemm_args(ix, qpad);
+    g.a_stride = ix->op_row_bytes;
+    g.a_scale_rows = kQuantBlock;
+    g.n_rows = (uint32_t)ix->n;
+    g.n_rt = (uint32_t)((ix->n + kFilterTile - 1) / kFilterTile);
+    g.cand = ix->cand.as<uint64_t>();
+    g.cnt = ix->cnt.as<uint32_t>();
+    g.n_q = nq;
     return g;
 }
 
@@ -493,8 +482,12 @@ static SampleLayout sample_layout(const bsr_index* ix, uint32_t nq, uint32_t ks)
     return L;
 }
 
-static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax, uint32_t ks_in,
-                       uint32_t cap_in) {
+// Steps 2-3 of the candidate stage: the sample pass and tau0 (smax: also the ks best sample
+// keys per query, the input of a parallel search's global threshold), then the emit pass.
+// Batches of at most 16 queries use the skinny (HBM-bound, no LDS) filter kernels.
+// ks / cap (0: ks_for(k) / cap_for(k)): the masked search's lowered threshold and longer lists.
+static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax, uint32_t ks_in = 0,
+                       uint32_t cap_in = 0) {
     BSR_TRY(filter_buffers(ix, nq, qpad, k, cap_in));
     ix->smp_tiles = 0;
     const bool skinny = nq <= kSkinnyMaxQ;
@@ -534,9 +527,8 @@ static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, ui
         g.S = ix->S.as<float>();
         g.s_ld = s_ld;
         g.s_compact = L.compact ? 1u : 0u;
-        BSR_HIP(launch_timed(ix, ix->ev_sample, [&](hipEvent_t e0, hipEvent_t e1) {
-            return skinny ? launch_filter_skinny_sample(g, ix->stream, e0, e1)
-                          : launch_filter_sample(g, ix->stream, e0, e1);
+        BSR_HIP(launch_timed(ix, ix->ev_sample, [&] {
+            return skinny ? launch_filter_skinny_sample(g, ix->stream) : launch_filter_sample(g, ix->stream);
         }, 2));
         BSR_HIP(launch_select_tau(ix->S.as<float>(), s_ld, n_vals, nq, qpad, ix->qflags.as<uint32_t>(), ks,
                                   ix->tau.as<float>(), ix->cnt.as<uint32_t>(), status, ix->stream, smax));
@@ -547,18 +539,10 @@ static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, ui
     return BSR_OK;
 }
 
-static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t cap_in) {
+static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t cap_in = 0) {
     const bool skinny = nq <= kSkinnyMaxQ;
-    const uint32_t BM = kFilterTile;
-    const uint64_t n = ix->n;
-    GemmArgs g = gemm_args(ix, qpad);
-    g.a_stride = ix->op_row_bytes;
-    g.a_scale_rows = kQuantBlock;
-    g.n_rows = (uint32_t)n;
-    g.n_rt = (uint32_t)((n + BM - 1) / BM);
+    GemmArgs g = emit_args(ix, nq, qpad);
     g.tau = ix->tau.as<float>();
-    g.cand = ix->cand.as<uint64_t>();
-    g.cnt = ix->cnt.as<uint32_t>();
     g.cap = cap_in ? cap_in : cap_for(k);
     // the last 1/kTailDiv of the row tiles are balanced dynamically (k_filter_qs16)
     g.tail = g.n_qt <= kTailCounters ? ix->cnt.as<uint32_t>() + qpad : nullptr;
@@ -568,10 +552,8 @@ static int emit_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint
     g.S = ix->S.as<float>();
     g.s_ld = ix->smp_ld;
     g.s_vals = ix->smp_vals;
-    g.n_q = nq;
-    BSR_HIP(launch_timed(ix, ix->ev_emit, [&](hipEvent_t e0, hipEvent_t e1) {
-        hipError_t r = skinny ? launch_filter_skinny_emit(g, ix->stream, e0, e1)
-                              : launch_filter_emit(g, ix->stream, e0, e1);
+    BSR_HIP(launch_timed(ix, ix->ev_emit, [&] {
+        hipError_t r = skinny ? launch_filter_skinny_emit(g, ix->stream) : launch_filter_emit(g, ix->stream);
         if (r == hipSuccess && g.s_tiles) r = launch_sample_fixup(g, ix->stream);
         return r;
     }));
@@ -585,35 +567,78 @@ static uint32_t top_layout_lab() {
 }
 
 // The self-thresholded filter pass: every wave's 4 best keys per query (launch_filter_skinny_top).
-static int top_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k) {
+static int top_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t top) {
     BSR_TRY(filter_buffers(ix, nq, qpad, k));
-    GemmArgs g = gemm_args(ix, qpad);
-    g.a_stride = ix->op_row_bytes;
-    g.a_scale_rows = kQuantBlock;
-    g.n_rows = (uint32_t)ix->n;
-    g.n_rt = (uint32_t)((ix->n + kFilterTile - 1) / kFilterTile);
-    g.cand = ix->cand.as<uint64_t>();
-    g.cnt = ix->cnt.as<uint32_t>();
-    g.cap = top_slots(ix, nq, k);
+    GemmArgs g = emit_args(ix, nq, qpad);
+    g.cap = top;
     g.status = ix->d_status;
-    g.n_q = nq;
     g.top_layout = top_layout_lab();
-    BSR_HIP(launch_timed(ix, ix->ev_emit, [&](hipEvent_t e0, hipEvent_t e1) {
-        return launch_filter_skinny_top(g, ix->stream, e0, e1);
-    }));
+    BSR_HIP(launch_timed(ix, ix->ev_emit, [&] { return launch_filter_skinny_top(g, ix->stream); }));
     return BSR_OK;
 }
 
-// Candidate stage (steps 2-5) for every query of the batch.
-static int run_filter(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t* next_status, bool publish) {
-    const uint32_t top = top_slots(ix, nq, k);
+// What every rescore launch of a batch takes from the index: the exact operands, one item per
+// query, the k' / k of the batch, and the result rows of res[cur] (the rescore kernels write them
+// themselves: no k_finalize launch) counted against the whole shard.
+static RescoreArgs rescore_args(const bsr_index* ix, uint32_t nq, uint32_t k) {
+    RescoreArgs r{};
+    r.rows = ix->rows.as<float>();
+    r.ld = ix->ld;
+    r.dim = ix->dim;
+    r.na = ix->na.as<float>();
+    r.qf32 = ix->qf32.as<float>();
+    r.nb = ix->nb.as<float>();
+    r.n_items = nq;
+    r.kp = kp_for(k);
+    r.k = k;
+    r.ebound = ix->ebound.as<float>();
+    r.out_keys = ix->keys.as<uint64_t>();
+    r.res_idx = ix->d_idx;
+    r.res_dist = ix->d_dist;
+    r.res_cnt = ix->d_cnt;
+    r.offset = ix->global_offset;
+    r.n_rows = ix->n;
+    return r;
+}
+// ... over the emitted lists of cap keys (mode B; with sel, the lists mode S selects from)
+static void rescore_emitted(RescoreArgs& r, const bsr_index* ix, uint32_t cap) {
+    r.cand_keys = ix->cand.as<uint64_t>();
+    r.cnt = ix->cnt.as<uint32_t>();
+    r.cap = cap;
+    r.tau0 = ix->tau.as<float>();
+}
+// ... as the batch's last kernel: it zeroes the NEXT search's status words and sums the emitted
+// counts (emit_cnt) into this search's
+static void rescore_bookkeeping(RescoreArgs& r, const bsr_index* ix, uint32_t nq, const uint32_t* emit_cnt) {
+    r.next_status = ix->res[ix->cur ^ 1u].as<uint32_t>();
+    r.emit_cnt = emit_cnt;
+    r.cur_status = ix->d_status;
+    r.n_queries = nq;
+}
+// ... of a published search: the result rows also go straight to the host mirror, and the last
+// kernel copies the status words there and raises the flag
+static void rescore_mirror(RescoreArgs& r, const bsr_index* ix) {
+    r.hres_idx = reinterpret_cast<uint64_t*>(ix->h_res_dev + ix->res_off_idx);
+    r.hres_dist = reinterpret_cast<float*>(ix->h_res_dev + ix->res_off_dist);
+    r.hres_cnt = reinterpret_cast<uint32_t*>(ix->h_res_dev + ix->res_off_cnt);
+}
+static void rescore_publish(RescoreArgs& r, const bsr_index* ix) {
+    r.pub_src = ix->res[ix->cur].as<uint8_t>();
+    r.pub_dst = ix->h_res_dev;
+    r.pub_bytes = kStWords * sizeof(uint32_t);  // (the rows: written through by both passes)
+    r.pub_flag = ix->h_flag_dev;
+    r.pub_ticket = ix->pub_ticket.as<uint32_t>();
+}
+
+// Candidate stage (steps 2-5) for every query of the batch.  top: the slots per query of the
+// self-thresholded path (top_slots), 0 on the thresholded path.
+static int run_filter(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint32_t top, bool publish) {
     if (top) {
-        BSR_TRY(top_pass(ix, nq, qpad, k));
+        BSR_TRY(top_pass(ix, nq, qpad, k, top));
     } else {
         BSR_TRY(sample_pass(ix, nq, qpad, k, nullptr));
         BSR_TRY(emit_pass(ix, nq, qpad, k));
     }
-    const uint32_t kp = kp_for(k);
     const uint32_t cap = top ? top : cap_for(k);
     uint32_t* status = ix->d_status;
     // lists of <= 1024 keys (k <= 10): the rescore kernel selects its own k' candidates (the
@@ -622,45 +647,22 @@ static int run_filter(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uin
     if (!fused_select) {
         ev_begin(ix, ix->ev_select);
         BSR_HIP(launch_select_cand(ix->cand.as<uint64_t>(), ix->cnt.as<uint32_t>(), cap, nq, ix->tau.as<float>(),
-                                   kp, ix->cand_rows.as<uint32_t>(), ix->ncand.as<uint32_t>(),
+                                   kp_for(k), ix->cand_rows.as<uint32_t>(), ix->ncand.as<uint32_t>(),
                                    ix->tau_excl.as<float>(), ix->stream));
         ev_end(ix, ix->ev_select);
     }
     ev_begin(ix, ix->ev_rescore);
-    RescoreArgs ra{};
-    ra.rows = ix->rows.as<float>();
-    ra.ld = ix->ld;
-    ra.dim = ix->dim;
-    ra.na = ix->na.as<float>();
-    ra.qf32 = ix->qf32.as<float>();
-    ra.nb = ix->nb.as<float>();
-    ra.n_items = nq;
+    // the first pass: the k' selected candidates (mode A), or selected here (mode S)
+    RescoreArgs ra = rescore_args(ix, nq, k);
     ra.cand_rows = ix->cand_rows.as<uint32_t>();
     ra.ncand = ix->ncand.as<uint32_t>();
-    ra.kp = kp;
     ra.tau_excl = ix->tau_excl.as<float>();
-    ra.k = k;
-    ra.ebound = ix->ebound.as<float>();
-    ra.out_keys = ix->keys.as<uint64_t>();
     ra.fail_cnt = status + kStFail;
     ra.fail_list = ix->fail.as<uint32_t>();
-    // the result rows are written by the rescore kernels themselves (no k_finalize launch)
-    ra.res_idx = ix->d_idx;
-    ra.res_dist = ix->d_dist;
-    ra.res_cnt = ix->d_cnt;
-    if (publish) {  // the result rows also go straight to the host mirror (published below)
-        ra.hres_idx = reinterpret_cast<uint64_t*>(ix->h_res_dev + ix->res_off_idx);
-        ra.hres_dist = reinterpret_cast<float*>(ix->h_res_dev + ix->res_off_dist);
-        ra.hres_cnt = reinterpret_cast<uint32_t*>(ix->h_res_dev + ix->res_off_cnt);
-    }
-    ra.offset = ix->global_offset;
-    ra.n_rows = ix->n;
+    if (publish) rescore_mirror(ra, ix);
     if (fused_select) {
         ra.sel = 1;
-        ra.cand_keys = ix->cand.as<uint64_t>();
-        ra.cnt = ix->cnt.as<uint32_t>();
-        ra.cap = cap;
-        ra.tau0 = ix->tau.as<float>();
+        rescore_emitted(ra, ix, cap);
     }
     if (top) {
         ra.top_w = top / 4;  // (lists: one per workgroup of the skinny filter)
@@ -676,29 +678,16 @@ static int run_filter(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uin
     RescoreArgs rb = ra;
     rb.sel = 0;
     rb.top_w = 0;
-    rb.n_items = nq;
     rb.n_items_dev = status + kStFail;
     rb.qlist = ix->fail.as<uint32_t>();
     rb.cand_rows = nullptr;
     rb.ncand = nullptr;
     rb.tau_excl = nullptr;
-    rb.cand_keys = ix->cand.as<uint64_t>();
-    rb.cnt = ix->cnt.as<uint32_t>();
-    rb.cap = cap;
-    rb.tau0 = ix->tau.as<float>();
+    rescore_emitted(rb, ix, cap);
     rb.fail_cnt = status + kStFail2;
     rb.fail_list = ix->fail2.as<uint32_t>();
-    rb.next_status = next_status;
-    rb.emit_cnt = ix->cnt.as<uint32_t>();
-    rb.cur_status = status;
-    rb.n_queries = nq;
-    if (publish) {  // the batch's last kernel: the status words to host memory, then the flag
-        rb.pub_src = ix->res[ix->cur].as<uint8_t>();
-        rb.pub_dst = ix->h_res_dev;
-        rb.pub_bytes = kStWords * sizeof(uint32_t);  // (the rows: written through by both passes)
-        rb.pub_flag = ix->h_flag_dev;
-        rb.pub_ticket = ix->pub_ticket.as<uint32_t>();
-    }
+    rescore_bookkeeping(rb, ix, nq, ix->cnt.as<uint32_t>());
+    if (publish) rescore_publish(rb, ix);  // (the batch's last kernel)
     BSR_HIP(launch_rescore(rb, ix->stream));
     ev_end(ix, ix->ev_rescore);
     return BSR_OK;
@@ -752,8 +741,116 @@ int bsr_index::prepare_result(uint32_t nq, uint32_t k) {
     return BSR_OK;
 }
 
-int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int (*after_launch)(void*),
-                             void* ctx) {
+// ---- the query stage (step 1), shared by the plain, masked and global-threshold searches ----
+// Queries padded to the filter's 256-query tile; batches of <= 16 (the skinny kernels read query
+// rows 0..15 only) to 16, so that the per-query kernels launch 16 workgroups, not 256.  (The
+// global-threshold search, batches of more than 16 only, always takes the rounded value.)
+static uint32_t qpad_for(uint32_t nq) {
+    return nq <= kSkinnyMaxQ ? kSkinnyMaxQ : (uint32_t)round_up(nq, kFilterTile);
+}
+// Its scratch, and the batch's result keys.
+static int query_buffers(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k) {
+    BSR_TRY(ix->qf32.ensure((size_t)qpad * ix->ld * sizeof(float)));
+    BSR_TRY(ix->nb.ensure((size_t)qpad * sizeof(float)));
+    BSR_TRY(ix->qop.ensure((size_t)qpad * ix->op_row_bytes));
+    BSR_TRY(ix->qscale.ensure((size_t)qpad * sizeof(float)));
+    BSR_TRY(ix->ebound.ensure((size_t)qpad * sizeof(float)));
+    BSR_TRY(ix->qflags.ensure((size_t)qpad * sizeof(uint32_t)));
+    BSR_TRY(ix->qids_id.ensure((size_t)qpad * sizeof(int32_t)));
+    BSR_TRY(ix->keys.ensure((size_t)nq * k * sizeof(uint64_t)));
+    return BSR_OK;
+}
+// Its launch arguments over those buffers (qsrc: the queries on the device, stage_queries).
+static QueryPrepArgs query_prep_args(const bsr_index* ix, const float* qsrc, uint32_t nq, uint32_t qpad, bool with_op) {
+    QueryPrepArgs qa{};
+    qa.q = qsrc;
+    qa.nq = nq;
+    qa.qpad = qpad;
+    qa.dim = ix->dim;
+    qa.ld = ix->ld;
+    qa.ea_max = ix->flags.as<uint32_t>() + 1;
+    qa.qf32 = ix->qf32.as<float>();
+    qa.nb = ix->nb.as<float>();
+    qa.qop = ix->qop.p;
+    qa.qscale = ix->qscale.as<float>();
+    qa.ebound = ix->ebound.as<float>();
+    qa.qflags = ix->qflags.as<uint32_t>();
+    qa.qids = ix->qids_id.as<int32_t>();
+    qa.status = ix->d_status;
+    qa.with_op = with_op;
+    return qa;
+}
+// The queries on the device: device queries where they are, host queries copied into q_in (sized
+// here unless it already is: gtau_prepare sizes it ahead of phase A, which allocates nothing).
+static int stage_queries(bsr_index* ix, const float* queries, uint32_t nq, const float** qsrc) {
+    *qsrc = queries;
+    if (is_device_ptr(queries)) return BSR_OK;
+    const size_t bytes = (size_t)nq * ix->dim * sizeof(float);
+    BSR_TRY(ix->q_in.ensure(bytes));
+    BSR_HIP(hipMemcpyAsync(ix->q_in.p, queries, bytes, hipMemcpyHostToDevice, ix->stream));
+    *qsrc = ix->q_in.as<float>();
+    return BSR_OK;
+}
+
+// ---- after the status readback -----------------------------------------------------------
+// A batch with a NaN/Inf query is an error that names the first such query.
+static int check_queries(bsr_index* ix, uint32_t nq) {
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(ix->h_res);
+    if (!(st[kStQueryFlags] & kQueryNonFinite)) return BSR_OK;
+    ix->h_qflags.resize(nq);
+    BSR_HIP(hipMemcpy(ix->h_qflags.data(), ix->qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint32_t bad = 0;
+    while (bad < nq && !(ix->h_qflags[bad] & kQueryNonFinite)) ++bad;
+    return set_error(BSR_E_NONFINITE, "query %u contains NaN/Inf (the reference panics)", bad);
+}
+// The nfail queries of fail2 -- uncertified, or not served by the filter (zero/tiny/huge |b|) --
+// as the exact scans' input: their ids in ascending order, counted into stats (direct: the filter
+// cannot serve the query; fallback: it was left uncertified), in qids (device) in groups of kScanQF,
+// the last group padded with its first id.  rerun (optional): set, with nothing counted or
+// uploaded, when a query the filter serves is among them.
+static int failed_queries(bsr_index* ix, uint32_t nq, uint32_t nfail, bool* rerun = nullptr) {
+    std::vector<uint32_t>& h_fail = ix->h_fail;
+    h_fail.resize(nfail);
+    ix->h_qflags.resize(nq);
+    BSR_HIP(hipMemcpyAsync(h_fail.data(), ix->fail2.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           ix->stream));
+    BSR_HIP(hipMemcpyAsync(ix->h_qflags.data(), ix->qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           ix->stream));
+    BSR_HIP(hipStreamSynchronize(ix->stream));
+    if (rerun) {
+        for (uint32_t q : h_fail) *rerun |= !(ix->h_qflags[q] & kQueryNoApprox);
+        if (*rerun) return BSR_OK;
+    }
+    std::sort(h_fail.begin(), h_fail.end());
+    for (uint32_t q : h_fail) {
+        if (ix->h_qflags[q] & kQueryNoApprox) ++ix->stats.n_exact_direct;
+        else ++ix->stats.n_fallback;
+    }
+    std::vector<int32_t> padded(round_up(nfail, kScanQF));
+    for (size_t i = 0; i < padded.size(); ++i)
+        padded[i] = (int32_t)(i < nfail ? h_fail[i] : h_fail[i / kScanQF * kScanQF]);
+    BSR_TRY(ix->qids.ensure(padded.size() * sizeof(int32_t)));
+    BSR_HIP(hipMemcpyAsync(ix->qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                           ix->stream));
+    return BSR_OK;
+}
+// A later round (the exact scans of the failed queries) finalizes every query's keys again,
+// counted against n_rows, and reads the result back.  poll: the masked search's form -- its total
+// ends here and the host polls the stream; otherwise a blocking wait.
+static int finalize_and_read(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t n_rows, bool poll) {
+    BSR_HIP(launch_finalize(ix->keys.as<uint64_t>(), nq, k, n_rows, ix->global_offset, ix->d_idx, ix->d_dist,
+                            ix->d_cnt, ix->res[ix->cur ^ 1u].as<uint32_t>(), nullptr, ix->d_status, ix->stream));
+    ix->next_status_clean = true;
+    if (poll) ev_end(ix, ix->ev_total);
+    BSR_HIP(hipMemcpyAsync(ix->h_res, ix->res[ix->cur].p, ix->res_bytes, hipMemcpyDeviceToHost, ix->stream));
+    BSR_HIP(poll ? stream_wait(ix->stream) : hipStreamSynchronize(ix->stream));
+    return BSR_OK;
+}
+
+// force_threshold: the thresholded path whatever top_slots says, launched directly (the rerun of a
+// batch the self-thresholded path left uncertified, below).
+int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int (*after_launch)(void*), void* ctx,
+                             bool force_threshold) {
     bsr_index* ix = this;
     if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
     if (k == 0 || k > ix->cfg.max_k) return set_error(BSR_E_INVALID, "k=%u outside [1, max_k=%u]", k, ix->cfg.max_k);
@@ -763,71 +860,44 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
     stats.filter_op = 0;  // int8
     stats.row_ebound = row_ebound;
     BSR_TRY(prepare_result(nq, k));
-    uint32_t* next_status = res[cur ^ 1u].as<uint32_t>();
     if (nq == 0) return BSR_OK;
     if (!queries) return set_error(BSR_E_INVALID, "null queries");
 
-    // queries padded to the filter's 256-query tile; batches of <= 16 (the skinny kernels read
-    // query rows 0..15 only) to 16, so that the per-query kernels launch 16 workgroups, not 256
-    const uint32_t qpad = nq <= kSkinnyMaxQ ? kSkinnyMaxQ : (uint32_t)round_up(nq, kFilterTile);
-    BSR_TRY(qf32.ensure((size_t)qpad * ld * sizeof(float)));
-    BSR_TRY(nb.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(qop.ensure((size_t)qpad * op_row_bytes));
-    BSR_TRY(qscale.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(ebound.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(qflags.ensure((size_t)qpad * sizeof(uint32_t)));
-    BSR_TRY(qids_id.ensure((size_t)qpad * sizeof(int32_t)));
-    BSR_TRY(keys.ensure((size_t)nq * k * sizeof(uint64_t)));
-
+    const uint32_t qpad = qpad_for(nq);
+    BSR_TRY(query_buffers(ix, nq, qpad, k));
     ev_begin(ix, ev_total);
-    const float* qsrc = queries;
-    if (!is_device_ptr(queries)) {
-        BSR_TRY(q_in.ensure((size_t)nq * dim * sizeof(float)));
-        BSR_HIP(hipMemcpyAsync(q_in.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, stream));
-        qsrc = q_in.as<float>();
-    }
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
     // (the status words of res[cur] were zeroed by the previous search's finalize)
     // every batch is filtered (batches of <= 16 queries by the skinny kernels)
     const bool use_filter = n > 0 && approx_ok && k <= kMaxKForFilter;
-    QueryPrepArgs qa{};
-    qa.q = qsrc;
-    qa.nq = nq;
-    qa.qpad = qpad;
-    qa.dim = dim;
-    qa.ld = ld;
-    qa.ea_max = flags.as<uint32_t>() + 1;
-    qa.qf32 = qf32.as<float>();
-    qa.nb = nb.as<float>();
-    qa.qop = qop.p;
-    qa.qscale = qscale.as<float>();
-    qa.ebound = ebound.as<float>();
-    qa.qflags = qflags.as<uint32_t>();
-    qa.qids = qids_id.as<int32_t>();
-    qa.status = d_status;
-    qa.with_op = use_filter;
+    const QueryPrepArgs qa = query_prep_args(ix, qsrc, nq, qpad, use_filter);
+    const uint32_t top = use_filter && !force_threshold ? top_slots(ix, nq, k) : 0u;
+    if (top) stats.search_path |= BSR_PATH_SKINNY_TOP;
     // The filtered path publishes its result: the rescore kernels write every result row into
     // the pinned host mirror as well, and the last kernel copies the status words there and
     // raises a host flag, which the host polls -- no D2H copy node, no wait for the stream's
     // completion signal.  Profile level 2 (every stage evented) keeps the D2H
     // copy and the stream wait.
-    const bool publish = use_filter && n > 0 && (!profiling(ix) || prof_level <= 1);
+    const bool publish = use_filter && (!profiling(ix) || prof_level <= 1);
     // prep -> local search -> finalize -> one D2H copy of the packed result (graph-capturable:
     // no allocation and no host synchronisation once the buffers are sized)
     auto enqueue_search = [&]() -> int {
         BSR_HIP(launch_query_prep(qa, stream));
-        if (n == 0) {
-            // Empty shard (e.g. a rank whose interval_by_rank block is empty): no results.
-            BSR_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(uint64_t), stream));
-        } else if (!use_filter) {
-            stats.n_exact_direct = nq;
-            BSR_TRY(run_exact_scan(ix, qids_id.as<int32_t>(), nq, k));
-        } else {
+        if (use_filter) {
             // (the rescore kernels write the result rows and the status bookkeeping)
-            BSR_TRY(run_filter(ix, nq, qpad, k, next_status, publish));
+            BSR_TRY(run_filter(ix, nq, qpad, k, top, publish));
+        } else {
+            if (n == 0) {
+                // Empty shard (e.g. a rank whose interval_by_rank block is empty): no results.
+                BSR_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(uint64_t), stream));
+            } else {
+                stats.n_exact_direct = nq;
+                BSR_TRY(run_exact_scan(ix, qids_id.as<int32_t>(), nq, k));
+            }
+            BSR_HIP(launch_finalize(keys.as<uint64_t>(), nq, k, n, global_offset, d_idx, d_dist, d_cnt,
+                                    res[cur ^ 1u].as<uint32_t>(), nullptr, d_status, stream));
         }
-        if (!(use_filter && n > 0))
-            BSR_HIP(launch_finalize(keys.as<uint64_t>(), nq, k, n, global_offset, d_idx, d_dist, d_cnt, next_status,
-                                    nullptr, d_status, stream));
         ev_end(ix, ev_total);
         if (!publish) BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, res_bytes, hipMemcpyDeviceToHost, stream));
         return BSR_OK;
@@ -835,36 +905,36 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
     if (publish) __atomic_store_n(h_flag, 0u, __ATOMIC_RELEASE);  // (before any launch of this search)
 
     // Every filtered batch is graph-capturable; a timed search (profile level >= 1) launches
-    // directly, its events recorded on the stream (launch_timed).
-    const bool top = use_filter && top_slots(ix, nq, k) != 0;
-    if (top) stats.search_path |= BSR_PATH_SKINNY_TOP;
-    const bool graphable = use_filter && n > 0 && (!profiling(ix) || prof_level == 0) && !force_threshold;
+    // directly, its events recorded on the stream (launch_timed), and so does a rerun.
+    const bool graphable = use_filter && (!profiling(ix) || prof_level == 0) && !force_threshold;
+    // (the key, after every buffer outside enqueue_search is sized; the switches are read per search)
+    SearchKey key;
+    key.nq = nq;
+    key.k = k;
+    key.qsrc = qsrc;
+    key.n = n;
+    key.gen = g_alloc_gen;
+    key.top = top != 0;
+    key.top_layout = top ? top_layout_lab() : 2u;
+    key.skinny_glds = skinny_glds_on();
+    key.sample_tiles = sample_tiles_on();
     SearchGraph& gs = graphs[cur];
-    // (the graph key: the TOP row layout and the skinny filter's A/B switch, both read per search)
-    const uint32_t lay = (top ? top_layout_lab() : 2u) | (skinny_glds_on() ? 0x100u : 0u) |
-                         (sample_tiles_on() ? 0x200u : 0u);
-    const bool same_shape = warm.nq == nq && warm.k == k && warm.qsrc == qsrc && warm.n == n &&
-                            warm.timed == (profiling(ix) ? prof_level : 0) && warm.top == top &&
-                            warm.top_layout == lay;
-    const int timed_level = profiling(ix) ? prof_level : 0;
-    if (graphable && gs.exec && gs.nq == nq && gs.k == k && gs.qsrc == qsrc && gs.n == n && gs.gen == g_alloc_gen &&
-        gs.timed == timed_level && gs.top == top && gs.top_layout == lay) {
+    if (graphable && gs.exec && gs.key == key) {
         BSR_HIP(hipGraphLaunch(gs.exec, stream));
         stats.n_candidates = kp_for(k);
         ++graph_replays;
         stats.graph_replay = 1;
-    } else if (graphable && same_shape && warm.gen == g_alloc_gen) {
+    } else if (graphable && warm == key) {
         // capture (every buffer already sized by the direct search of this shape), then replay
         if (gs.exec) { (void)hipGraphExecDestroy(gs.exec); gs.exec = nullptr; }
         BSR_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        const uint64_t gen0 = g_alloc_gen;
         capturing = true;
         const int rc = enqueue_search();
         capturing = false;
         hipGraph_t graph = nullptr;
         const hipError_t ec = hipStreamEndCapture(stream, &graph);
         if (rc != BSR_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (ec != hipSuccess || g_alloc_gen != gen0) {
+        if (ec != hipSuccess || g_alloc_gen != key.gen) {  // (an allocation inside the capture)
             if (graph) (void)hipGraphDestroy(graph);
             return set_error(BSR_E_HIP, "search graph capture failed: %s", hipGetErrorString(ec));
         }
@@ -872,13 +942,16 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
         const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (ei != hipSuccess) return set_error(BSR_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ei));
-        gs = SearchGraph{exec, nq, k, qsrc, n, g_alloc_gen, timed_level, top, lay};
+        gs = SearchGraph{exec, key};
         BSR_HIP(hipGraphLaunch(gs.exec, stream));
         ++graph_replays;
         stats.graph_replay = 1;
     } else {
         BSR_TRY(enqueue_search());
-        if (graphable) warm = SearchGraph{nullptr, nq, k, qsrc, n, g_alloc_gen, timed_level, top, lay};
+        if (graphable) {
+            warm = key;
+            warm.gen = g_alloc_gen;  // (the direct search sized the candidate stage's buffers)
+        }
     }
     next_status_clean = true;
     int hook_st = BSR_OK;
@@ -891,64 +964,29 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
         BSR_HIP(stream_wait(stream));
     }
     if (hook_st != BSR_OK) return hook_st;
-    // Later rounds (second-chance rescore, scan) finalize and read back again, directly.
-    auto finalize_and_read = [&]() -> int {
-        BSR_HIP(launch_finalize(keys.as<uint64_t>(), nq, k, n, global_offset, d_idx, d_dist, d_cnt, next_status,
-                                nullptr, d_status, stream));
-        next_status_clean = true;
-        BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, res_bytes, hipMemcpyDeviceToHost, stream));
-        BSR_HIP(hipStreamSynchronize(stream));
-        return BSR_OK;
-    };
-    std::vector<int32_t> exact_ids;
+    BSR_TRY(check_queries(ix, nq));
+    if (!use_filter) return BSR_OK;
     const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
-    if (st[kStQueryFlags] & kQueryNonFinite) {
-        h_qflags.resize(nq);
-        BSR_HIP(hipMemcpy(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        uint32_t bad = 0;
-        while (bad < nq && !(h_qflags[bad] & kQueryNonFinite)) ++bad;
-        return set_error(BSR_E_NONFINITE, "query %u contains NaN/Inf (the reference panics)", bad);
+    stats.n_emitted = st[kStEmitted];
+    // st[kStFail] queries failed the first certification and were rescored over every
+    // emitted row in the same launch sequence; st[kStFail2] of them failed again.
+    const uint32_t nfail = st[kStFail2];
+    stats.n_rescued = st[kStFail] - nfail;
+    if (!nfail) return BSR_OK;
+    bool rerun = false;
+    BSR_TRY(failed_queries(ix, nq, nfail, top ? &rerun : nullptr));
+    if (rerun) {
+        // The self-thresholded path left a query it serves uncertified (more than a wave's 4
+        // best of its rows lie near the top: a cluster of near-duplicates): the batch again
+        // on the thresholded path, directly launched, whose own failures take the exact scan.
+        const int r = search_device(queries, nq, k, nullptr, nullptr, true);
+        stats.search_path |= BSR_PATH_SKINNY_TOP | BSR_PATH_TOP_RERUN;
+        return r;
     }
-    if (use_filter) {
-        stats.n_emitted = st[kStEmitted];
-        // st[kStFail] queries failed the first certification and were rescored over every
-        // emitted row in the same launch sequence; st[kStFail2] of them failed again.
-        const uint32_t nfail = st[kStFail2];
-        const uint32_t* fail_dev = fail2.as<uint32_t>();
-        stats.n_rescued = st[kStFail] - nfail;
-        if (nfail) {
-            // Uncertified queries, and queries the filter cannot serve (zero/tiny/huge |b|),
-            // take the exact full scan: the reference's arithmetic on every row.
-            h_fail.resize(nfail);
-            h_qflags.resize(nq);
-            BSR_HIP(hipMemcpyAsync(h_fail.data(), fail_dev, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                   stream));
-            BSR_HIP(hipMemcpyAsync(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                   stream));
-            BSR_HIP(hipStreamSynchronize(stream));
-            bool served_failed = false;
-            for (uint32_t q : h_fail) served_failed |= !(h_qflags[q] & kQueryNoApprox);
-            if (top && served_failed) {
-                // The self-thresholded path left a query it serves uncertified (more than a wave's 4
-                // best of its rows lie near the top: a cluster of near-duplicates): the batch again
-                // on the thresholded path, directly launched, whose own failures take the exact scan.
-                force_threshold = true;
-                const int r = search_device(queries, nq, k);
-                force_threshold = false;
-                stats.search_path |= BSR_PATH_SKINNY_TOP | BSR_PATH_TOP_RERUN;
-                return r;
-            }
-            std::sort(h_fail.begin(), h_fail.end());
-            for (uint32_t q : h_fail) {
-                exact_ids.push_back((int32_t)q);
-                if (h_qflags[q] & kQueryNoApprox) ++stats.n_exact_direct;
-                else ++stats.n_fallback;
-            }
-            BSR_TRY(run_exact_scan_list(ix, exact_ids, k));
-            BSR_TRY(finalize_and_read());
-        }
-    }
-    return BSR_OK;
+    // Uncertified queries, and queries the filter cannot serve, take the exact full scan: the
+    // reference's arithmetic on every row.  Later rounds finalize and read back again, directly.
+    BSR_TRY(run_exact_scan(ix, qids.as<int32_t>(), nfail, k));
+    return finalize_and_read(ix, nq, k, n, false);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1033,28 +1071,16 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
     stats.filter_op = 0;
     stats.row_ebound = row_ebound;
     BSR_TRY(prepare_result(nq, k));
-    uint32_t* next_status = res[cur ^ 1u].as<uint32_t>();
     if (nq == 0) return BSR_OK;
     if (!queries) return set_error(BSR_E_INVALID, "null queries");
 
-    const uint32_t qpad = nq <= kSkinnyMaxQ ? kSkinnyMaxQ : (uint32_t)round_up(nq, kFilterTile);
-    BSR_TRY(qf32.ensure((size_t)qpad * ld * sizeof(float)));
-    BSR_TRY(nb.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(qop.ensure((size_t)qpad * op_row_bytes));
-    BSR_TRY(qscale.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(ebound.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(qflags.ensure((size_t)qpad * sizeof(uint32_t)));
-    BSR_TRY(qids_id.ensure((size_t)qpad * sizeof(int32_t)));
-    BSR_TRY(keys.ensure((size_t)nq * k * sizeof(uint64_t)));
+    const uint32_t qpad = qpad_for(nq);
+    BSR_TRY(query_buffers(ix, nq, qpad, k));
     BSR_TRY(mask_aux.ensure(((size_t)qpad + 1) * sizeof(uint32_t)));
 
     ev_begin(ix, ev_total);
-    const float* qsrc = queries;
-    if (!is_device_ptr(queries)) {
-        BSR_TRY(q_in.ensure((size_t)nq * dim * sizeof(float)));
-        BSR_HIP(hipMemcpyAsync(q_in.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, stream));
-        qsrc = q_in.as<float>();
-    }
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
     // The mask on the device, and the number of allowed rows A: the host needs it for the path,
     // the list's size and the result count min(k, A).
     const uint64_t* dmask = allow;
@@ -1076,24 +1102,7 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
     const uint32_t ks_m = use_filter ? masked_ks(k, n, A) : 0u;
     const uint32_t cap_m = 128u * ks_m;  // (cap_for / ks_for's ratio)
     stats.search_path |= use_filter ? BSR_PATH_MASK_FILTER : BSR_PATH_MASK_LIST;
-
-    QueryPrepArgs qa{};
-    qa.q = qsrc;
-    qa.nq = nq;
-    qa.qpad = qpad;
-    qa.dim = dim;
-    qa.ld = ld;
-    qa.ea_max = flags.as<uint32_t>() + 1;
-    qa.qf32 = qf32.as<float>();
-    qa.nb = nb.as<float>();
-    qa.qop = qop.p;
-    qa.qscale = qscale.as<float>();
-    qa.ebound = ebound.as<float>();
-    qa.qflags = qflags.as<uint32_t>();
-    qa.qids = qids_id.as<int32_t>();
-    qa.status = d_status;
-    qa.with_op = use_filter;
-    BSR_HIP(launch_query_prep(qa, stream));
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, use_filter), stream));
 
     // The list: the fallback of the filter path builds it only when a query needs it.
     bool have_list = false;
@@ -1104,25 +1113,6 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
         have_list = true;
         return BSR_OK;
     };
-    auto finalize_and_read = [&]() -> int {
-        BSR_HIP(launch_finalize(keys.as<uint64_t>(), nq, k, A, global_offset, d_idx, d_dist, d_cnt, next_status,
-                                nullptr, d_status, stream));
-        next_status_clean = true;
-        ev_end(ix, ev_total);
-        BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, res_bytes, hipMemcpyDeviceToHost, stream));
-        BSR_HIP(stream_wait(stream));
-        return BSR_OK;
-    };
-    auto check_queries = [&]() -> int {
-        const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
-        if (!(st[kStQueryFlags] & kQueryNonFinite)) return BSR_OK;
-        h_qflags.resize(nq);
-        BSR_HIP(hipMemcpy(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        uint32_t bad = 0;
-        while (bad < nq && !(h_qflags[bad] & kQueryNonFinite)) ++bad;
-        return set_error(BSR_E_NONFINITE, "query %u contains NaN/Inf (the reference panics)", bad);
-    };
-
     if (!use_filter) {
         // the list path: every query by the exact scan of the allowed rows
         stats.n_exact_direct = nq;
@@ -1132,8 +1122,8 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
         } else {
             BSR_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(uint64_t), stream));
         }
-        BSR_TRY(finalize_and_read());
-        return check_queries();
+        BSR_TRY(finalize_and_read(ix, nq, k, A, true));
+        return check_queries(ix, nq);
     }
 
     // The filter path: the threshold lowered by 1 / rho, the emitted lists cut by the mask, every
@@ -1144,70 +1134,32 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
     uint32_t* items = raw_cnt + qpad;
     BSR_HIP(launch_mask_cut(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dmask, n, raw_cnt, items, stream));
     ev_begin(ix, ev_rescore);
-    RescoreArgs rb{};
-    rb.rows = rows.as<float>();
-    rb.ld = ld;
-    rb.dim = dim;
-    rb.na = na.as<float>();
-    rb.qf32 = qf32.as<float>();
-    rb.nb = nb.as<float>();
-    rb.n_items = nq;
+    RescoreArgs rb = rescore_args(ix, nq, k);
     rb.n_items_dev = items;
     rb.qlist = reinterpret_cast<const uint32_t*>(qids_id.as<int32_t>());  // (identity for q < nq)
-    rb.kp = kp_for(k);
-    rb.cand_keys = cand.as<uint64_t>();
-    rb.cnt = cnt.as<uint32_t>();
-    rb.cap = cap_m;
-    rb.tau0 = tau.as<float>();
-    rb.k = k;
-    rb.ebound = ebound.as<float>();
-    rb.out_keys = keys.as<uint64_t>();
+    rescore_emitted(rb, ix, cap_m);
     rb.fail_cnt = d_status + kStFail2;
     rb.fail_list = fail2.as<uint32_t>();
-    rb.res_idx = d_idx;
-    rb.res_dist = d_dist;
-    rb.res_cnt = d_cnt;
-    rb.offset = global_offset;
     rb.n_rows = A;  // (the fused finalize's count: min(k, A))
-    rb.next_status = next_status;
-    rb.emit_cnt = raw_cnt;
-    rb.cur_status = d_status;
-    rb.n_queries = nq;
+    rescore_bookkeeping(rb, ix, nq, raw_cnt);
     BSR_HIP(launch_rescore(rb, stream));
     ev_end(ix, ev_rescore);
     next_status_clean = true;
     ev_end(ix, ev_total);
     BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, res_bytes, hipMemcpyDeviceToHost, stream));
     BSR_HIP(stream_wait(stream));
-    BSR_TRY(check_queries());
+    BSR_TRY(check_queries(ix, nq));
     const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
     stats.n_emitted = st[kStEmitted];
     const uint32_t nfail = st[kStFail2];
-    if (nfail) {
-        // Uncertified queries (an overflowed list among them) and queries the filter cannot
-        // serve take the list scan: the reference's arithmetic on every allowed row.
-        h_fail.resize(nfail);
-        h_qflags.resize(nq);
-        BSR_HIP(hipMemcpyAsync(h_fail.data(), fail2.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        BSR_HIP(hipMemcpyAsync(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        BSR_HIP(hipStreamSynchronize(stream));
-        std::sort(h_fail.begin(), h_fail.end());
-        const uint32_t groups = (nfail + kScanQF - 1) / kScanQF;
-        std::vector<int32_t> padded((size_t)groups * kScanQF);
-        for (size_t i = 0; i < padded.size(); ++i)
-            padded[i] = (int32_t)(i < nfail ? h_fail[i] : h_fail[i / kScanQF * kScanQF]);
-        for (uint32_t q : h_fail) {
-            if (h_qflags[q] & kQueryNoApprox) ++stats.n_exact_direct;
-            else ++stats.n_fallback;
-        }
-        BSR_TRY(qids.ensure(padded.size() * sizeof(int32_t)));
-        BSR_HIP(hipMemcpyAsync(qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        stats.search_path |= BSR_PATH_MASK_LIST;
-        BSR_TRY(build_list());
-        BSR_TRY(run_list_scan(ix, qids.as<int32_t>(), nfail, k, A));
-        BSR_TRY(finalize_and_read());
-    }
-    return BSR_OK;
+    if (!nfail) return BSR_OK;
+    // Uncertified queries (an overflowed list among them) and queries the filter cannot
+    // serve take the list scan: the reference's arithmetic on every allowed row.
+    BSR_TRY(failed_queries(ix, nq, nfail));
+    stats.search_path |= BSR_PATH_MASK_LIST;
+    BSR_TRY(build_list());
+    BSR_TRY(run_list_scan(ix, qids.as<int32_t>(), nfail, k, A));
+    return finalize_and_read(ix, nq, k, A, true);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1233,14 +1185,7 @@ int bsr_index::gtau_prepare(const float* queries, uint32_t nq, uint32_t k) {
     BSR_TRY(prepare_result(nq, k));
     const uint32_t qpad = (uint32_t)round_up(nq, kFilterTile);
     const uint32_t ks = ks_for(k);
-    BSR_TRY(qf32.ensure((size_t)qpad * ld * sizeof(float)));
-    BSR_TRY(nb.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(qop.ensure((size_t)qpad * op_row_bytes));
-    BSR_TRY(qscale.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(ebound.ensure((size_t)qpad * sizeof(float)));
-    BSR_TRY(qflags.ensure((size_t)qpad * sizeof(uint32_t)));
-    BSR_TRY(qids_id.ensure((size_t)qpad * sizeof(int32_t)));
-    BSR_TRY(keys.ensure((size_t)nq * k * sizeof(uint64_t)));
+    BSR_TRY(query_buffers(this, nq, qpad, k));
     BSR_TRY(smax.ensure((size_t)qpad * ks * sizeof(uint64_t)));
     if (!is_device_ptr(queries)) BSR_TRY(q_in.ensure((size_t)nq * dim * sizeof(float)));
     BSR_TRY(filter_buffers(this, nq, qpad, k));
@@ -1262,29 +1207,10 @@ int bsr_index::gtau_phase_a(const float* queries, int part) {
         BSR_TRY(sample_pass(ix, nq, qpad, k, smax.as<uint64_t>()));
         return BSR_OK;
     }
-    const float* qsrc = queries;
-    if (!is_device_ptr(queries)) {
-        BSR_HIP(hipMemcpyAsync(q_in.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, stream));
-        qsrc = q_in.as<float>();
-    }
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));  // (q_in: sized by gtau_prepare)
     ev_begin(ix, ev_total);
-    QueryPrepArgs qa{};
-    qa.q = qsrc;
-    qa.nq = nq;
-    qa.qpad = qpad;
-    qa.dim = dim;
-    qa.ld = ld;
-    qa.ea_max = flags.as<uint32_t>() + 1;
-    qa.qf32 = qf32.as<float>();
-    qa.nb = nb.as<float>();
-    qa.qop = qop.p;
-    qa.qscale = qscale.as<float>();
-    qa.ebound = ebound.as<float>();
-    qa.qflags = qflags.as<uint32_t>();
-    qa.qids = qids_id.as<int32_t>();
-    qa.status = d_status;
-    qa.with_op = true;
-    BSR_HIP(launch_query_prep(qa, stream));
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, true), stream));
     return BSR_OK;
 }
 
@@ -1296,32 +1222,10 @@ int bsr_index::gtau_phase_b(const uint64_t* g_smax, uint32_t P, uint32_t* merge_
     // every emitted row rescored exactly, one wave per query (mode B); the list is this rank's
     // contribution, its exclusion bound goes with it (the root certifies the merged lists)
     ev_begin(ix, ev_rescore);
-    RescoreArgs ra{};
-    ra.rows = rows.as<float>();
-    ra.ld = ld;
-    ra.dim = dim;
-    ra.na = na.as<float>();
-    ra.qf32 = qf32.as<float>();
-    ra.nb = nb.as<float>();
-    ra.n_items = nq;
-    ra.cand_keys = cand.as<uint64_t>();
-    ra.cnt = cnt.as<uint32_t>();
-    ra.cap = cap_for(k);
-    ra.tau0 = tau.as<float>();
-    ra.kp = kp_for(k);
-    ra.k = k;
-    ra.ebound = ebound.as<float>();
-    ra.out_keys = keys.as<uint64_t>();
-    ra.res_idx = d_idx;
-    ra.res_dist = d_dist;
-    ra.res_cnt = d_cnt;
-    ra.offset = global_offset;
-    ra.n_rows = n;
+    RescoreArgs ra = rescore_args(ix, nq, k);
+    rescore_emitted(ra, ix, cap_for(k));
     ra.excl_out = d_x;
-    ra.next_status = res[cur ^ 1u].as<uint32_t>();
-    ra.emit_cnt = cnt.as<uint32_t>();
-    ra.cur_status = d_status;
-    ra.n_queries = nq;
+    rescore_bookkeeping(ra, ix, nq, cnt.as<uint32_t>());
     ra.merge_words = merge_words;  // (the merge's two words: no memset launches before it)
     BSR_HIP(launch_rescore(ra, stream));
     ev_end(ix, ev_rescore);

@@ -120,23 +120,32 @@ struct bsr_index {
     int prof_level = 2;  // bsr_index_set_profile
 
     // Filtered batches replay a captured hipGraph of query prep -> filter -> select -> rescore
-    // -> finalize -> D2H instead of ~9 launches.  One graph per result buffer; captured on the second search of a shape
-    // (the first sizes every buffer), dropped when the shape or any allocation changes.
+    // (-> D2H) instead of ~9 launches.  One graph per result buffer; captured on the second search
+    // of a shape (the first sizes every buffer), dropped when the shape or any allocation changes.
+    // Only untimed searches are captured (a timed search launches directly, its events recorded
+    // on the stream).
+    // The shape of a graphable search: what a capture bakes in.
+    struct SearchKey {
+        uint32_t nq = 0, k = 0;
+        const float* qsrc = nullptr;  // the queries on the device (the caller's, or q_in)
+        uint64_t n = 0, gen = 0;      // shard rows; g_alloc_gen
+        bool top = false;             // the self-thresholded single-query path (round 6)
+        // the switches read per search (A/B runs change them in process):
+        uint32_t top_layout = 2;      // the TOP row layout (BSR_TOP_LAYOUT, lab)
+        bool skinny_glds = true;      // BSR_SKINNY_GLDS
+        bool sample_tiles = true;     // BSR_SAMPLE_TILES
+        bool operator==(const SearchKey& o) const {
+            return nq == o.nq && k == o.k && qsrc == o.qsrc && n == o.n && gen == o.gen && top == o.top &&
+                   top_layout == o.top_layout && skinny_glds == o.skinny_glds && sample_tiles == o.sample_tiles;
+        }
+    };
     struct SearchGraph {
         hipGraphExec_t exec = nullptr;
-        uint32_t nq = 0, k = 0;
-        const float* qsrc = nullptr;
-        uint64_t n = 0, gen = 0;
-        int timed = 0;  // profile level it was captured at (always 0: timed searches launch directly)
-        bool top = false;  // the self-thresholded single-query path (round 6)
-        uint32_t top_layout = 2;  // its row layout (BSR_TOP_LAYOUT, lab: read per search)
+        SearchKey key;
     };
-    // (round 6) the batch is searched again on the thresholded path: the self-thresholded path
-    // left a query uncertified (direct launches, no graph)
-    bool force_threshold = false;
     bool capturing = false;    // a search is being captured into a graph
     SearchGraph graphs[2];
-    SearchGraph warm;  // the last direct search of a graphable shape (no exec)
+    SearchKey warm;  // the last direct search of a graphable shape
     uint64_t graph_replays = 0;
     ~bsr_index();
 
@@ -144,8 +153,9 @@ struct bsr_index {
     // the pinned host mirror h_res at the same offsets.  after_launch (optional) runs once the
     // search's GPU work is enqueued, before the host waits for it (the parallel search issues
     // its shape-agreement collective there); its non-OK status is returned after the wait.
+    // force_threshold: the search's own rerun of a batch the self-thresholded path left uncertified.
     int search_device(const float* queries, uint32_t nq, uint32_t k, int (*after_launch)(void*) = nullptr,
-                      void* ctx = nullptr);
+                      void* ctx = nullptr, bool force_threshold = false);
     int prepare_result(uint32_t nq, uint32_t k);
 
     // The local search restricted to the rows an allow mask names (bsr_local_top_k_masked,

@@ -1582,8 +1582,9 @@ hipError_t launch_rescore(const RescoreArgs& a_in, hipStream_t s) {
     a.solo = 0;
     const uint32_t e = (a.k + 63) / 64;
     // the first pass (mode S) of a tiny batch: one workgroup per query, one wave per chunk
-    // (BSR_RESCORE_KP=0: the one-wave kernel instead, for A/B runs)
-    static const bool kp_on = rescore_kp_enabled();
+    // (BSR_RESCORE_KP=0: the one-wave kernel instead, for A/B runs; read per call, as top_slots
+    // reads it per search)
+    const bool kp_on = rescore_kp_enabled();
     if (a.top_w && !(kp_on && a.n_items <= 16 && a.ld % 64 == 0 && a.ld <= 1024 && a.k <= 64 && a.kp <= 63 &&
                      4 * a.top_w <= 64u * kTopKeysPerLane))
         return hipErrorInvalidValue;  // (the self-thresholded path needs k_rescore_kp: the caller checks)

@@ -2126,13 +2126,7 @@ static uint32_t filter_grid(uint32_t n_qt) {
     return 8 * per_xcd;
 }
 
-// Filter launches: with timing events, hipExtLaunchKernel records them at the kernel's own
-// dispatch and completion; without, a plain launch (also inside stream capture).
-#define BSR_KLAUNCH(K, G, B, S, E0, E1, A)                               \
-    do {                                                                 \
-        if (E0) hipExtLaunchKernelGGL(K, G, B, 0, S, E0, E1, 0u, A);     \
-        else hipLaunchKernelGGL(K, G, B, 0, S, A);                       \
-    } while (0)
+#define BSR_KLAUNCH(K, G, B, S, A) hipLaunchKernelGGL(K, G, B, 0, S, A)
 
 static uint32_t skinny_grid(uint32_t n_rows) {
     const uint32_t groups = (n_rows + 31) / 32, wgs = (groups + 3) / 4;
@@ -2152,32 +2146,32 @@ bool skinny_glds_on() {
     return !(v && v[0] == '0');
 }
 template <int MODE>
-static void launch_skinny(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+static void launch_skinny(const GemmArgs& a, hipStream_t s) {
     const uint32_t nk = a.row_bytes / kSliceB;
     if constexpr (MODE != kSkSample) {
         if (nk == 12 && skinny_glds_on()) {
-            BSR_KLAUNCH((k_filter_skinny_glds<MODE, 12>), dim3(skinny2_grid(a.n_rows)), dim3(128), s, e0, e1, a);
+            BSR_KLAUNCH((k_filter_skinny_glds<MODE, 12>), dim3(skinny2_grid(a.n_rows)), dim3(128), s, a);
             return;
         }
     }
     const dim3 g(nk <= 16 ? skinny2_grid(a.n_rows) : skinny_grid(a.n_rows)), b(256);
-    if (nk <= 4) BSR_KLAUNCH((k_filter_skinny2<MODE, 4>), g, b, s, e0, e1, a);
-    else if (nk <= 8) BSR_KLAUNCH((k_filter_skinny2<MODE, 8>), g, b, s, e0, e1, a);
-    else if (nk <= 12) BSR_KLAUNCH((k_filter_skinny2<MODE, 12>), g, b, s, e0, e1, a);
-    else if (nk <= 16) BSR_KLAUNCH((k_filter_skinny2<MODE, 16>), g, b, s, e0, e1, a);
-    else if constexpr (MODE != kSkTop) BSR_KLAUNCH(k_filter_skinny<MODE == kSkEmit>, g, b, s, e0, e1, a);
+    if (nk <= 4) BSR_KLAUNCH((k_filter_skinny2<MODE, 4>), g, b, s, a);
+    else if (nk <= 8) BSR_KLAUNCH((k_filter_skinny2<MODE, 8>), g, b, s, a);
+    else if (nk <= 12) BSR_KLAUNCH((k_filter_skinny2<MODE, 12>), g, b, s, a);
+    else if (nk <= 16) BSR_KLAUNCH((k_filter_skinny2<MODE, 16>), g, b, s, a);
+    else if constexpr (MODE != kSkTop) BSR_KLAUNCH(k_filter_skinny<MODE == kSkEmit>, g, b, s, a);
 }
-hipError_t launch_filter_skinny_sample(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    launch_skinny<kSkSample>(a, s, e0, e1);
+hipError_t launch_filter_skinny_sample(const GemmArgs& a, hipStream_t s) {
+    launch_skinny<kSkSample>(a, s);
     return hipGetLastError();
 }
-hipError_t launch_filter_skinny_emit(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    launch_skinny<kSkEmit>(a, s, e0, e1);
+hipError_t launch_filter_skinny_emit(const GemmArgs& a, hipStream_t s) {
+    launch_skinny<kSkEmit>(a, s);
     return hipGetLastError();
 }
-hipError_t launch_filter_skinny_top(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+hipError_t launch_filter_skinny_top(const GemmArgs& a, hipStream_t s) {
     if (a.row_bytes / kSliceB > 16) return hipErrorInvalidValue;  // (v2 widths only: the caller checks)
-    launch_skinny<kSkTop>(a, s, e0, e1);
+    launch_skinny<kSkTop>(a, s);
     return hipGetLastError();
 }
 
@@ -2202,31 +2196,31 @@ static bool gang_possible(const GemmArgs& a, uint32_t grid) {
 }
 
 template <bool EMIT>
-static void launch_filter(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+static void launch_filter(const GemmArgs& a, hipStream_t s) {
     const uint32_t nk = a.row_bytes / kSliceB, grid = filter_grid(a.n_qt);
     if (nk % 2 == 0 && nk <= 12) {
         const dim3 g(grid), b(512);
         if (EMIT && nk == 12 && !gang_possible(a, grid)) {
-            BSR_KLAUNCH((k_filter_qs16<EMIT, 12, 0, 8, 0, 0, 1, 0>), g, b, s, e0, e1, a);
+            BSR_KLAUNCH((k_filter_qs16<EMIT, 12, 0, 8, 0, 0, 1, 0>), g, b, s, a);
             return;
         }
         switch (nk) {
-            case 2: BSR_KLAUNCH((k_filter_qs16<EMIT, 2>), g, b, s, e0, e1, a); return;
-            case 4: BSR_KLAUNCH((k_filter_qs16<EMIT, 4>), g, b, s, e0, e1, a); return;
-            case 6: BSR_KLAUNCH((k_filter_qs16<EMIT, 6>), g, b, s, e0, e1, a); return;
-            case 8: BSR_KLAUNCH((k_filter_qs16<EMIT, 8>), g, b, s, e0, e1, a); return;
-            case 10: BSR_KLAUNCH((k_filter_qs16<EMIT, 10>), g, b, s, e0, e1, a); return;
-            default: BSR_KLAUNCH((k_filter_qs16<EMIT, 12>), g, b, s, e0, e1, a); return;
+            case 2: BSR_KLAUNCH((k_filter_qs16<EMIT, 2>), g, b, s, a); return;
+            case 4: BSR_KLAUNCH((k_filter_qs16<EMIT, 4>), g, b, s, a); return;
+            case 6: BSR_KLAUNCH((k_filter_qs16<EMIT, 6>), g, b, s, a); return;
+            case 8: BSR_KLAUNCH((k_filter_qs16<EMIT, 8>), g, b, s, a); return;
+            case 10: BSR_KLAUNCH((k_filter_qs16<EMIT, 10>), g, b, s, a); return;
+            default: BSR_KLAUNCH((k_filter_qs16<EMIT, 12>), g, b, s, a); return;
         }
     }
-    BSR_KLAUNCH((k_filter<OpI8, EMIT>), dim3(grid), dim3(kThreads), s, e0, e1, a);
+    BSR_KLAUNCH((k_filter<OpI8, EMIT>), dim3(grid), dim3(kThreads), s, a);
 }
-hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    launch_filter<false>(a, s, e0, e1);
+hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s) {
+    launch_filter<false>(a, s);
     return hipGetLastError();
 }
-hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    launch_filter<true>(a, s, e0, e1);
+hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s) {
+    launch_filter<true>(a, s);
     return hipGetLastError();
 }
 hipError_t launch_sample_fixup(const GemmArgs& a, hipStream_t s) {

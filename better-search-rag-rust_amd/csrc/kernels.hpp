@@ -147,12 +147,8 @@ constexpr uint32_t kGangWords = 2 * 256;
 // small-shard build at 2.5M rows, 0.8% at 5M, 0-1% faster at 10M -- profiles/r05hm_hist_*,
 // r05e_hist_10m.txt; the threshold was 256, ~2.5M rows)
 constexpr uint32_t kGangMinTiles = 600;
-// e0 / e1 (optional): events recorded at the kernel's own dispatch and completion
-// (hipExtLaunchKernel), i.e. its device duration without the stream's launch gaps.
-hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s, hipEvent_t e0 = nullptr,
-                                hipEvent_t e1 = nullptr);
-hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s, hipEvent_t e0 = nullptr,
-                              hipEvent_t e1 = nullptr);
+hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s);
+hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s);
 // The sample tiles' share of the emission (a.s_tiles != 0; after the threshold is final, before
 // the rescore): for every query q < a.n_q and sample value S[q][j] >= tau[q] (ties included),
 // the 32 rows of that block are scored as the emit pass scores them and those reaching tau[q]
@@ -162,13 +158,13 @@ hipError_t launch_sample_fixup(const GemmArgs& a, hipStream_t s);
 // int8 only, batches of <= 16 queries (query tile rows 0..15), HBM-bound: the same
 // contract as the two launches above.
 constexpr uint32_t kSkinnyMaxQ = 16;
-hipError_t launch_filter_skinny_sample(const GemmArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-hipError_t launch_filter_skinny_emit(const GemmArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t launch_filter_skinny_sample(const GemmArgs& a, hipStream_t s);
+hipError_t launch_filter_skinny_emit(const GemmArgs& a, hipStream_t s);
 // The self-thresholded single-query path (round 6; rows of <= 16 K slices): no sample pass and no
 // tau0 -- each of the skinny2 grid's W = skinny_top_lists(n) workgroups writes its 4 best keys per
 // query to cand[q][W][4] (ascending; every other row of the workgroup scores at most the 4th), and
 // cnt[q] = 4 W for q < 16; the status words kStFail / kStEmitted / kStFail2 are zeroed.
-hipError_t launch_filter_skinny_top(const GemmArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t launch_filter_skinny_top(const GemmArgs& a, hipStream_t s);
 uint32_t skinny_top_lists(uint32_t n_rows);
 bool skinny_glds_on();  // the LDS-DMA skinny filter for 768-byte rows (BSR_SKINNY_GLDS=0: off; read per call)
 // Shards of at least this many rows take the self-thresholded path for batches of <= 16 queries
