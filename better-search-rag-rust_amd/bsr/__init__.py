@@ -131,6 +131,9 @@ def lib() -> ctypes.CDLL:
         "bsr_index_dim": (ctypes.c_int, [_P, ctypes.POINTER(u32)]),
         "bsr_index_global_offset": (ctypes.c_int, [_P, ctypes.POINTER(u64)]),
         "bsr_index_get_many": (ctypes.c_int, [_P, u64, u64, _P]),
+        "bsr_index_delete": (ctypes.c_int, [_P, _P, u64, ctypes.POINTER(u64)]),
+        "bsr_index_live_count": (ctypes.c_int, [_P, ctypes.POINTER(u64)]),
+        "bsr_index_deleted_mask": (ctypes.c_int, [_P, _P, u64]),
         "bsr_local_top_k": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
@@ -153,7 +156,9 @@ def lib() -> ctypes.CDLL:
         "bsr_index_set_profile": (ctypes.c_int, [_P, ctypes.c_int]),
         "bsr_synth_uniform": (ctypes.c_int, [_P, u64, u64, u32, u64]),
     }
-    optional = {"bsr_host_alloc", "bsr_host_free"}  # (absent in older builds used for A/B runs)
+    # (absent in older builds used for A/B runs)
+    optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
+                "bsr_index_deleted_mask"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -378,6 +383,51 @@ class Index:
         if rows.shape[0] == 0:
             raise BsrError(-1, "Index not found")
         return rows[0]
+
+    # ---- tombstones (bsr_index_delete) ----
+    def delete(self, ids) -> int:
+        """Mark rows as deleted; every search then answers over the live rows alone.  ids: GLOBAL
+        indices as the searches return them (global_offset + local row) -- an int, a sequence or
+        numpy array of integers, or a torch tensor of 64-bit integers (host or device) -- in any
+        order, duplicates allowed.  All or nothing: an id outside the shard raises BsrError(-1)
+        and no row changes.  Returns the number of rows that went live -> deleted in this call."""
+        if hasattr(ids, "data_ptr"):  # a torch tensor, passed through as a pointer
+            if ids.is_floating_point() or ids.is_complex() or ids.element_size() != 8:
+                raise BsrError(-1, "a tensor of ids holds 64-bit integers")
+            ids = ids.reshape(-1)
+            if not ids.is_contiguous():
+                ids = ids.contiguous()
+            n = int(ids.numel())
+            if n and ids.dtype.is_signed and bool((ids < 0).any()):
+                raise BsrError(-1, "negative row id")
+            buf = ids
+        else:
+            a = np.asarray(ids)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise BsrError(-1, "ids must be integers")
+            a = a.reshape(-1)
+            if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
+                raise BsrError(-1, "negative row id")
+            buf = np.ascontiguousarray(a, np.uint64) if a.size else np.zeros(0, np.uint64)
+            n = int(buf.size)
+        out = ctypes.c_uint64(0)
+        _check(lib().bsr_index_delete(self._h, _ptr(buf) if n else None, n, ctypes.byref(out)))
+        return int(out.value)
+
+    def live_count(self) -> int:
+        """Rows not deleted: get_count() minus the tombstones."""
+        n = ctypes.c_uint64()
+        _check(lib().bsr_index_live_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def deleted_mask(self) -> np.ndarray:
+        """bool [n]: True where local row i is deleted (~ of it is a valid allow_mask)."""
+        n = self.get_count()
+        words = (n + 63) // 64
+        w = np.zeros(max(words, 1), np.uint64)
+        _check(lib().bsr_index_deleted_mask(self._h, _ptr(w), words))
+        bits = np.unpackbits(w[:words].view(np.uint8), bitorder="little")
+        return bits[:n].astype(np.bool_)
 
     def _allow_words(self, allow_mask, allow_ids):
         """(buffer, word count) of a search's allow mask: a bool array [n] or row ids are packed

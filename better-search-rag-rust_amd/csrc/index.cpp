@@ -308,6 +308,7 @@ int bsr_index_load_impl(bsr_index* ix, const void* rows, uint64_t n_rows, uint64
     if (n_rows >= (1ull << 31)) return set_error(BSR_E_INVALID, "shard too large (the reference slices with i32 offsets)");
     BSR_HIP(hipSetDevice(ix->device));
     ix->loaded = false;
+    ix->clear_tombstones();  // (a load replaces the contents: every row live)
     ix->n = n_rows;
     ix->n_pad = round_up(n_rows ? n_rows : 1, kRowPad);
     ix->global_offset = global_offset;
@@ -339,8 +340,17 @@ int bsr_index_append_impl(bsr_index* ix, const void* rows, uint64_t n_rows) {
     }
     ix->n = new_n;
     ix->n_pad = new_pad;
-    BSR_TRY(index_prepare_rows(ix, rows, n_rows, old_n));
-    return index_finish_load(ix);
+    // the tombstones are kept and the appended rows are live; the requantised operand of the
+    // deleted rows is zeroed again
+    int r = index_prepare_rows(ix, rows, n_rows, old_n);
+    if (r == BSR_OK) r = index_finish_load(ix);
+    if (r == BSR_OK) r = ix->tombstones_after_append();
+    if (r != BSR_OK) {
+        // n has grown past what the operand and the bitset cover: the index is empty until a load
+        ix->loaded = false;
+        ix->clear_tombstones();
+    }
+    return r;
 }
 
 int bsr_index_get_many_impl(const bsr_index* ix, uint64_t offset, uint64_t count, float* out) {
@@ -354,6 +364,144 @@ int bsr_index_get_many_impl(const bsr_index* ix, uint64_t offset, uint64_t count
                              ix->ld * sizeof(float), ix->dim * sizeof(float), count, kind, ix->stream));
     BSR_HIP(hipStreamSynchronize(ix->stream));
     return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// tombstones (bsr_index_delete)
+// ---------------------------------------------------------------------------------------
+// The bitset sized for the padded shard: allocated zeroed, or grown with its contents kept (the
+// stream is idle when the old allocation is freed).
+static int dead_reserve(bsr_index* ix) {
+    const size_t need = ix->n_pad / 64 * sizeof(uint64_t);
+    if (ix->dead.p && ix->dead.bytes >= need) return BSR_OK;
+    DevBuf grown;
+    BSR_TRY(grown.ensure(need));
+    BSR_HIP(hipMemsetAsync(grown.p, 0, need, ix->stream));
+    if (ix->dead.p)
+        BSR_HIP(hipMemcpyAsync(grown.p, ix->dead.p, ix->dead.bytes, hipMemcpyDeviceToDevice, ix->stream));
+    BSR_HIP(hipStreamSynchronize(ix->stream));
+    std::swap(ix->dead.p, grown.p);
+    std::swap(ix->dead.bytes, grown.bytes);
+    return BSR_OK;
+}
+
+// A deleted row scores exactly 0 in the emit, fix-up and TOP kernels and in the sample tiles, and
+// the fop_s sample becomes every 32nd LIVE row (by rank, from the bitset's prefix counts): it
+// leaves tau0's order statistics and the candidate lists.  (Speed only: the exact kernels drop it
+// whatever it scores.)  After every delete, and after an append -- index_finish_load requantises
+// the shard.  Walks the whole bitset and rewrites every deleted row: O(n_dead ld), whatever the
+// number of ids of the delete.  The masked search's allow & ~dead buffer is sized here too, so
+// that no search allocates -- and invalidates the captured graphs -- because of tombstones.
+static int dead_zero_operand(bsr_index* ix) {
+    BSR_TRY(ix->mask_eff.ensure((size_t)((ix->n + 63) / 64) * sizeof(uint64_t)));
+    BSR_TRY(ix->live_blk.ensure(((size_t)mask_blocks(ix->n) + 1) * sizeof(uint32_t)));
+    BSR_HIP(launch_mask_list_count(ix->dead.as<uint64_t>(), ix->n, ix->live_blk.as<uint32_t>(), ix->stream));
+    BSR_HIP(launch_dead_zero_fop(ix->dead.as<uint64_t>(), ix->n, ix->live_blk.as<uint32_t>(), ix->op_row_bytes,
+                                 ix->fop.as<uint8_t>(), ix->fop_s.as<uint8_t>(), ix->rows.as<float>(), ix->dim,
+                                 ix->ascale_s.as<float>(), ix->stream));
+    BSR_HIP(hipStreamSynchronize(ix->stream));
+    return BSR_OK;
+}
+
+void bsr_index::clear_tombstones() {
+    if (n_dead) ++dead_gen;
+    n_dead = 0;
+    live_list_ok = false;
+    (void)hipStreamSynchronize(stream);
+    dead.release();
+}
+
+int bsr_index::tombstones_after_append() {
+    live_list_ok = false;
+    if (!dead.p) return BSR_OK;
+    BSR_TRY(dead_reserve(this));  // (the appended rows: live)
+    if (n_dead) BSR_TRY(dead_zero_operand(this));
+    return BSR_OK;
+}
+
+int bsr_index::delete_rows(const uint64_t* ids, uint64_t n_ids, uint64_t* out_deleted) {
+    bsr_index* ix = this;
+    if (out_deleted) *out_deleted = 0;
+    if (!loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (!n_ids) return BSR_OK;
+    if (!ids) return set_error(BSR_E_INVALID, "null ids");
+    if (n_ids >> 32) return set_error(BSR_E_INVALID, "n_ids=%llu: at most 2^32 - 1 ids per call", (unsigned long long)n_ids);
+    BSR_HIP(hipSetDevice(device));
+    const uint64_t* dids = ids;
+    if (!is_device_ptr(ids)) {
+        BSR_TRY(dead_ids.ensure((size_t)n_ids * sizeof(uint64_t)));
+        BSR_HIP(hipMemcpyAsync(dead_ids.p, ids, (size_t)n_ids * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        dids = dead_ids.as<uint64_t>();
+    }
+    BSR_TRY(dead_cnt.ensure(2 * sizeof(uint32_t)));
+    BSR_HIP(hipMemsetAsync(dead_cnt.p, 0, 2 * sizeof(uint32_t), stream));
+    uint32_t* bad = dead_cnt.as<uint32_t>();
+    uint32_t h[2] = {0, 0};
+    // all or nothing: the ids are checked first, and nothing is applied when one is out of range
+    BSR_HIP(launch_dead_check(dids, n_ids, global_offset, n, bad, stream));
+    BSR_HIP(hipMemcpyAsync(h, bad, sizeof h, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (h[0])
+        return set_error(BSR_E_INVALID, "%u of the ids lie outside [%llu, %llu): no row was deleted", h[0],
+                         (unsigned long long)global_offset, (unsigned long long)(global_offset + n));
+    BSR_TRY(dead_reserve(ix));
+    BSR_HIP(launch_dead_apply(dids, n_ids, global_offset, n, dead.as<uint64_t>(), bad + 1, stream));
+    BSR_HIP(hipMemcpyAsync(h, bad, sizeof h, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (out_deleted) *out_deleted = h[1];
+    if (!h[1]) return BSR_OK;
+    n_dead += h[1];
+    ++dead_gen;
+    live_list_ok = false;
+    return dead_zero_operand(ix);
+}
+
+int bsr_index::deleted_mask(uint64_t* out_words, uint64_t words) const {
+    if (!loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (words != (n + 63) / 64)
+        return set_error(BSR_E_INVALID, "words=%llu, the index holds %llu rows (%llu words)", (unsigned long long)words,
+                         (unsigned long long)n, (unsigned long long)((n + 63) / 64));
+    if (!words) return BSR_OK;
+    if (!out_words) return set_error(BSR_E_INVALID, "null output");
+    BSR_HIP(hipSetDevice(device));
+    const size_t bytes = (size_t)words * sizeof(uint64_t);
+    const bool dev = is_device_ptr(out_words);
+    if (!n_dead) {
+        if (dev) BSR_HIP(hipMemsetAsync(out_words, 0, bytes, stream));
+        else memset(out_words, 0, bytes);
+    } else {
+        BSR_HIP(hipMemcpyAsync(out_words, dead.p, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+// The exact fallback's row list with tombstones present: the live rows, ascending, built from
+// ~dead by the masked search's list kernels (the count is known: no host read), cached until the
+// next delete, append or load.
+int bsr_index::ensure_live_list() {
+    if (live_list_ok) return BSR_OK;
+    const uint64_t live = live_rows();
+    if (!live) return BSR_OK;
+    const uint32_t n_blk = mask_blocks(n);
+    BSR_TRY(live_mask.ensure((size_t)((n + 63) / 64) * sizeof(uint64_t)));
+    BSR_TRY(live_blk.ensure(((size_t)n_blk + 1) * sizeof(uint32_t)));
+    BSR_TRY(live_list.ensure((size_t)live * sizeof(uint32_t)));
+    BSR_HIP(launch_dead_andnot(nullptr, dead.as<uint64_t>(), n, live_mask.as<uint64_t>(), stream));
+    BSR_HIP(launch_mask_list_count(live_mask.as<uint64_t>(), n, live_blk.as<uint32_t>(), stream));
+    BSR_HIP(launch_mask_list_scatter(live_mask.as<uint64_t>(), n, live_blk.as<uint32_t>(), (uint32_t)live,
+                                     live_list.as<uint32_t>(), stream));
+    live_list_ok = true;
+    return BSR_OK;
+}
+
+int bsr_index_delete_impl(bsr_index* ix, const uint64_t* ids, uint64_t n_ids, uint64_t* out_deleted) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    return ix->delete_rows(ids, n_ids, out_deleted);
+}
+int bsr_index_deleted_mask_impl(const bsr_index* ix, uint64_t* out_words, uint64_t words) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    return ix->deleted_mask(out_words, words);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -377,6 +525,16 @@ static int run_exact_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uin
     }
     ev_end(ix, ix->ev_scan);
     return BSR_OK;
+}
+
+static int run_list_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uint32_t k, const uint32_t* list,
+                         uint32_t n_list);
+// The exact rounds of a search: the full scan, or -- an index with tombstones -- the list scan over
+// its live rows (at least one: a shard without a live row takes the empty-shard branch).
+static int run_exact_rounds(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uint32_t k) {
+    if (!ix->n_dead) return run_exact_scan(ix, ids, n_ids, k);
+    BSR_TRY(ix->ensure_live_list());
+    return run_list_scan(ix, ids, n_ids, k, ix->live_list.as<uint32_t>(), (uint32_t)ix->live_rows());
 }
 
 static uint32_t kp_for(uint32_t k) { return 64u * ((3u * k + 34u + 63u) / 64u) - 1u; }
@@ -579,7 +737,7 @@ static int top_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint3
 
 // What every rescore launch of a batch takes from the index: the exact operands, one item per
 // query, the k' / k of the batch, and the result rows of res[cur] (the rescore kernels write them
-// themselves: no k_finalize launch) counted against the whole shard.
+// themselves: no k_finalize launch) counted against the shard's live rows.
 static RescoreArgs rescore_args(const bsr_index* ix, uint32_t nq, uint32_t k) {
     RescoreArgs r{};
     r.rows = ix->rows.as<float>();
@@ -597,7 +755,8 @@ static RescoreArgs rescore_args(const bsr_index* ix, uint32_t nq, uint32_t k) {
     r.res_dist = ix->d_dist;
     r.res_cnt = ix->d_cnt;
     r.offset = ix->global_offset;
-    r.n_rows = ix->n;
+    r.n_rows = ix->live_rows();
+    r.dead = ix->dead_bits();  // (nullptr without a deleted row: the kernels as they always ran)
     return r;
 }
 // ... over the emitted lists of cap keys (mode B; with sel, the lists mode S selects from)
@@ -870,7 +1029,13 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
     BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
     // (the status words of res[cur] were zeroed by the previous search's finalize)
     // every batch is filtered (batches of <= 16 queries by the skinny kernels)
-    const bool use_filter = n > 0 && approx_ok && k <= kMaxKForFilter;
+    // Tombstones: results are counted against the live rows; a shard whose live rows
+    // would all fit one query's candidate list (live <= cap_for(k)) goes straight to the list scan
+    // over them: that reads fewer rows than the filter would rescore, while the filter would still
+    // stream the whole shard, and with live / 32 < 4 ks sampled live rows tau0 is no order
+    // statistic worth the name (a shard of n <= cap rows has no sample pass for the same reason).
+    const uint64_t live = live_rows();
+    const bool use_filter = live > 0 && approx_ok && k <= kMaxKForFilter && (!n_dead || live > cap_for(k));
     const QueryPrepArgs qa = query_prep_args(ix, qsrc, nq, qpad, use_filter);
     const uint32_t top = use_filter && !force_threshold ? top_slots(ix, nq, k) : 0u;
     if (top) stats.search_path |= BSR_PATH_SKINNY_TOP;
@@ -888,14 +1053,15 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
             // (the rescore kernels write the result rows and the status bookkeeping)
             BSR_TRY(run_filter(ix, nq, qpad, k, top, publish));
         } else {
-            if (n == 0) {
-                // Empty shard (e.g. a rank whose interval_by_rank block is empty): no results.
+            if (live == 0) {
+                // Empty shard (e.g. a rank whose interval_by_rank block is empty), or one whose
+                // every row is deleted: no results.
                 BSR_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(uint64_t), stream));
             } else {
                 stats.n_exact_direct = nq;
-                BSR_TRY(run_exact_scan(ix, qids_id.as<int32_t>(), nq, k));
+                BSR_TRY(run_exact_rounds(ix, qids_id.as<int32_t>(), nq, k));
             }
-            BSR_HIP(launch_finalize(keys.as<uint64_t>(), nq, k, n, global_offset, d_idx, d_dist, d_cnt,
+            BSR_HIP(launch_finalize(keys.as<uint64_t>(), nq, k, live, global_offset, d_idx, d_dist, d_cnt,
                                     res[cur ^ 1u].as<uint32_t>(), nullptr, d_status, stream));
         }
         ev_end(ix, ev_total);
@@ -914,6 +1080,7 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
     key.qsrc = qsrc;
     key.n = n;
     key.gen = g_alloc_gen;
+    key.dead_gen = dead_gen;  // (a delete since the capture: its live count and bitset pointer are stale)
     key.top = top != 0;
     key.top_layout = top ? top_layout_lab() : 2u;
     key.skinny_glds = skinny_glds_on();
@@ -985,8 +1152,9 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
     }
     // Uncertified queries, and queries the filter cannot serve, take the exact full scan: the
     // reference's arithmetic on every row.  Later rounds finalize and read back again, directly.
-    BSR_TRY(run_exact_scan(ix, qids.as<int32_t>(), nfail, k));
-    return finalize_and_read(ix, nq, k, n, false);
+    // (with tombstones: the list scan over the live rows)
+    BSR_TRY(run_exact_rounds(ix, qids.as<int32_t>(), nfail, k));
+    return finalize_and_read(ix, nq, k, live, false);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -996,7 +1164,8 @@ int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int 
 // of kScanQF with valid ids): the full groups of kScanQF queries share launches (as many groups
 // per launch as kListPartBytes of partial lists hold), the last partial group takes its own.
 constexpr size_t kListPartBytes = 64u << 20;
-static int run_list_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uint32_t k, uint32_t n_list) {
+static int run_list_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uint32_t k, const uint32_t* list,
+                         uint32_t n_list) {
     if (!n_ids || !n_list) return BSR_OK;
     const uint32_t grid = scan_grid_for(n_list);
     const size_t group_bytes = (size_t)grid * kScanQF * k * sizeof(uint64_t);
@@ -1004,7 +1173,7 @@ static int run_list_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uint
     const uint32_t per_launch = (uint32_t)std::min<size_t>(std::max<size_t>(kListPartBytes / group_bytes, 1), 65535);
     BSR_TRY(ix->part.ensure(group_bytes * std::max(1u, std::min(per_launch, full))));
     auto scan = [&](uint32_t g0, uint32_t groups, uint32_t nqf) -> int {
-        BSR_HIP(launch_scan_list(ix->rows.as<float>(), ix->ld, ix->dim, ix->mask_list.as<uint32_t>(), n_list,
+        BSR_HIP(launch_scan_list(ix->rows.as<float>(), ix->ld, ix->dim, list, n_list,
                                  ix->na.as<float>(), ix->qf32.as<float>(), ids + (size_t)g0 * kScanQF, nqf, groups,
                                  ix->nb.as<float>(), k, grid, ix->part.as<uint64_t>(), ix->stream));
         for (uint32_t g = 0; g < groups; ++g)
@@ -1022,7 +1191,9 @@ static int run_list_scan(bsr_index* ix, const int32_t* ids, uint32_t n_ids, uint
 // The masked filter path's lowered threshold: with a fraction rho = A / n of the
 // rows allowed, the ks_m = ceil(ks_for(k) / rho)-th best sampled score lets as many ALLOWED rows
 // through as the unmasked search's threshold lets rows through; 0 when launch_select_tau cannot
-// select that deep (ks_m > 128, i.e. rho < ks_for(k) / 128).
+// select that deep (ks_m > 128, i.e. rho < ks_for(k) / 128).  n: the shard's LIVE rows -- deleted
+// rows score 0 and are out of the sample's order statistics already, so the
+// threshold is lowered by live / A only.
 static uint32_t masked_ks(uint32_t k, uint64_t n, uint64_t A) {
     if (!A) return 0;
     const uint64_t ks_m = ((uint64_t)ks_for(k) * n + A - 1) / A;
@@ -1049,7 +1220,7 @@ static bool auto_prefers_list(uint64_t n, uint64_t A, uint32_t nq, uint32_t k) {
 // at all; BSR_MASK_AUTO: where it is possible and auto_prefers_list says no.
 static bool masked_filter_path(const bsr_index* ix, uint32_t mode, uint64_t A, uint32_t nq, uint32_t k) {
     const bool possible = ix->n > 0 && ix->approx_ok && k <= kMaxKForFilter && ix->n > cap_for(k) && A >= 1 &&
-                          masked_ks(k, ix->n, A) != 0;
+                          masked_ks(k, ix->live_rows(), A) != 0;
     if (!possible || mode == BSR_MASK_LIST) return false;
     return !(mode == BSR_MASK_AUTO && auto_prefers_list(ix->n, A, nq, k));
 }
@@ -1092,6 +1263,12 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
                                    stream));
             dmask = mask_dev.as<uint64_t>();
         }
+        if (n_dead) {
+            // tombstones: the mask that drives A, the list, the cut and the counts is allow & ~dead
+            BSR_TRY(mask_eff.ensure((size_t)allow_words * sizeof(uint64_t)));
+            BSR_HIP(launch_dead_andnot(dmask, dead.as<uint64_t>(), n, mask_eff.as<uint64_t>(), stream));
+            dmask = mask_eff.as<uint64_t>();
+        }
         const uint32_t n_blk = mask_blocks(n);
         BSR_TRY(mask_blk.ensure(((size_t)n_blk + 1) * sizeof(uint32_t)));
         BSR_HIP(launch_mask_list_count(dmask, n, mask_blk.as<uint32_t>(), stream));
@@ -1099,7 +1276,7 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
         BSR_HIP(hipStreamSynchronize(stream));
     }
     const bool use_filter = masked_filter_path(ix, mode, A, nq, k);
-    const uint32_t ks_m = use_filter ? masked_ks(k, n, A) : 0u;
+    const uint32_t ks_m = use_filter ? masked_ks(k, live_rows(), A) : 0u;
     const uint32_t cap_m = 128u * ks_m;  // (cap_for / ks_for's ratio)
     stats.search_path |= use_filter ? BSR_PATH_MASK_FILTER : BSR_PATH_MASK_LIST;
     BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, use_filter), stream));
@@ -1118,7 +1295,7 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
         stats.n_exact_direct = nq;
         if (A) {
             BSR_TRY(build_list());
-            BSR_TRY(run_list_scan(ix, qids_id.as<int32_t>(), nq, k, A));
+            BSR_TRY(run_list_scan(ix, qids_id.as<int32_t>(), nq, k, mask_list.as<uint32_t>(), A));
         } else {
             BSR_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(uint64_t), stream));
         }
@@ -1158,7 +1335,7 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
     BSR_TRY(failed_queries(ix, nq, nfail));
     stats.search_path |= BSR_PATH_MASK_LIST;
     BSR_TRY(build_list());
-    BSR_TRY(run_list_scan(ix, qids.as<int32_t>(), nfail, k, A));
+    BSR_TRY(run_list_scan(ix, qids.as<int32_t>(), nfail, k, mask_list.as<uint32_t>(), A));
     return finalize_and_read(ix, nq, k, A, true);
 }
 
@@ -1167,7 +1344,10 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
 // ---------------------------------------------------------------------------------------
 bool bsr_index::gtau_eligible(uint32_t nq, uint32_t k) const {
     // the filter path with a sample pass (a shard of more rows than one query's candidate list)
-    return loaded && nq > 0 && k >= 1 && k <= cfg.max_k && k <= kMaxKForFilter && approx_ok && n > cap_for(k);
+    // (not while a row is deleted: its rescore and the merge's need = min(k, corpus rows) count
+    // every row -- the header then takes every rank to the standard path)
+    return loaded && nq > 0 && k >= 1 && k <= cfg.max_k && k <= kMaxKForFilter && approx_ok && n > cap_for(k) &&
+           n_dead == 0;
 }
 
 // Phase A's buffers (the result buffer of this search, the query and filter scratch, the sample

@@ -129,13 +129,15 @@ struct bsr_index {
         uint32_t nq = 0, k = 0;
         const float* qsrc = nullptr;  // the queries on the device (the caller's, or q_in)
         uint64_t n = 0, gen = 0;      // shard rows; g_alloc_gen
-        bool top = false;             // the self-thresholded single-query path (round 6)
+        uint64_t dead_gen = 0;        // tombstone generation (a capture bakes the live count and the bitset)
+        bool top = false;            // the self-thresholded single-query path (round 6)
         // the switches read per search (A/B runs change them in process):
         uint32_t top_layout = 2;      // the TOP row layout (BSR_TOP_LAYOUT, lab)
         bool skinny_glds = true;      // BSR_SKINNY_GLDS
         bool sample_tiles = true;     // BSR_SAMPLE_TILES
         bool operator==(const SearchKey& o) const {
-            return nq == o.nq && k == o.k && qsrc == o.qsrc && n == o.n && gen == o.gen && top == o.top &&
+            return nq == o.nq && k == o.k && qsrc == o.qsrc && n == o.n && gen == o.gen &&
+                   dead_gen == o.dead_gen && top == o.top &&
                    top_layout == o.top_layout && skinny_glds == o.skinny_glds && sample_tiles == o.sample_tiles;
         }
     };
@@ -167,6 +169,26 @@ struct bsr_index {
     bsr::DevBuf mask_blk;   // u32 [mask_blocks(n) + 1]: block offsets, the allowed-row count
     bsr::DevBuf mask_list;  // u32 [A]: the allowed rows, ascending
     bsr::DevBuf mask_aux;   // u32 [qpad + 1]: emitted counts before the cut; the rescore's item count
+
+    // Tombstones (bsr_index_delete): the bitset of deleted rows, allocated by the
+    // first delete (ceil(n_pad / 64) words, zero beyond the deleted rows), and what is derived from it.
+    bsr::DevBuf dead;
+    uint64_t n_dead = 0;     // deleted rows
+    uint64_t dead_gen = 0;   // bumped by every delete that changes a row, and by a load that clears any
+    bsr::DevBuf dead_ids;    // a delete's host ids on the device
+    bsr::DevBuf dead_cnt;    // u32 [2]: ids out of range, rows newly deleted
+    bsr::DevBuf live_mask;   // ~dead: the live rows as an allow mask
+    bsr::DevBuf live_blk;    // its block offsets (launch_mask_list_count); during a delete, the bitset's own
+    bsr::DevBuf live_list;   // u32 [live]: the live rows, ascending -- the exact fallback's row list
+    bool live_list_ok = false;  // built since the last delete / append / load
+    bsr::DevBuf mask_eff;    // a masked search's allow & ~dead
+    uint64_t live_rows() const { return n - n_dead; }
+    const uint64_t* dead_bits() const { return n_dead ? dead.as<uint64_t>() : nullptr; }
+    int delete_rows(const uint64_t* ids, uint64_t n_ids, uint64_t* out_deleted);
+    int deleted_mask(uint64_t* out_words, uint64_t words) const;
+    void clear_tombstones();        // load: every row live again
+    int tombstones_after_append();  // the bitset grown to the new rows, the operand zeroed again
+    int ensure_live_list();         // live_list, built from ~dead when it is not there
 
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:

@@ -463,8 +463,14 @@ __global__ __launch_bounds__(64 * W * QPW) void k_rescore(RescoreArgs a) {
                         if (ch + 1 < nchk) step(preB, ch + 1, 2);
                     }
                 }
-                const float d = finish_distance(acc[0], mx[0], a.na[myrow], mag_b);
-                L.offer(valid ? dist_key(d, myrow) : kKeyNone, (int)a.k, thr);
+                // (tombstones: the row's word of the bitset goes out with the row's magnitude, the
+                // candidate's other load that is independent of the scan -- one wait for both; a
+                // deleted row offers no key)
+                const float mag_a = a.na[myrow];
+                const uint32_t dw = a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[myrow >> 5] : 0u;
+                const float d = finish_distance(acc[0], mx[0], mag_a, mag_b);
+                const bool live = !((dw >> (myrow & 31)) & 1u);
+                L.offer(valid && live ? dist_key(d, myrow) : kKeyNone, (int)a.k, thr);
             }
         };
         if (qlds && nch == 12) scan(std::true_type{}, std::integral_constant<uint32_t, 12>{});
@@ -936,8 +942,13 @@ __global__ __launch_bounds__(1024) void k_rescore_kp(RescoreArgs a) {
     {
         float mx = 0.0f;
         for (int v = 0; v < nw; ++v) mx = fmaxf(mx, s_mxw[v][lane]);
-        const float d = finish_distance(s_acc[lane], mx, a.na[myrow], mag_b);  // (the last wave's sum)
-        L.offer(lane < (int)c ? dist_key(d, myrow) : kKeyNone, (int)a.k, thr);
+        // (tombstones, as k_rescore: the row's word of the bitset with its magnitude; a deleted
+        // row offers no key)
+        const float mag_a = a.na[myrow];
+        const uint32_t dw = a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[myrow >> 5] : 0u;
+        const float d = finish_distance(s_acc[lane], mx, mag_a, mag_b);  // (the last wave's sum)
+        const bool live = !((dw >> (myrow & 31)) & 1u);
+        L.offer(lane < (int)c && live ? dist_key(d, myrow) : kKeyNone, (int)a.k, thr);
     }
     L.store(a.out_keys + (uint64_t)q * a.k, (int)a.k);
     bool certified = false;

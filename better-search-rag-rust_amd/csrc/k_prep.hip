@@ -577,6 +577,147 @@ __global__ __launch_bounds__(256) void k_mask_cut(uint64_t* __restrict__ cand, u
     if (lane == 0) cnt[q] = out;
 }
 
+// ------------------------------------------------------------------------------------
+// Tombstones: the index's bitset of deleted rows -- bit (i & 63) of word (i >> 6)
+// set = local row i is deleted; bits at positions >= n are never set.  A delete is two launches
+// around the host's read of the first one's count: the check counts the ids outside
+// [lo, lo + n) (all or nothing: the host applies nothing when there is one), the apply sets the
+// bits and counts the rows that went live -> deleted (a duplicate, or a row deleted before, finds
+// its bit set in the word atomicOr returns: counted once).
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_dead_check(const uint64_t* __restrict__ ids, uint64_t n_ids, uint64_t lo,
+                                                    uint64_t n, uint32_t* __restrict__ bad) {
+    uint32_t mine = 0;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_ids; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t id = ids[i];
+        mine += (id < lo || id - lo >= n) ? 1u : 0u;
+    }
+    mine = wave_reduce_u32(mine, [](uint32_t x, uint32_t y) { return x + y; });
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(bad, mine);
+}
+
+__global__ __launch_bounds__(256) void k_dead_apply(const uint64_t* __restrict__ ids, uint64_t n_ids, uint64_t lo,
+                                                    uint64_t n, uint64_t* __restrict__ dead,
+                                                    uint32_t* __restrict__ newly) {
+    uint32_t mine = 0;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_ids; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t id = ids[i];
+        if (id < lo || id - lo >= n) continue;  // (the check found none: never taken)
+        const uint64_t r = id - lo, bit = 1ull << (r & 63);
+        const unsigned long long old = atomicOr(reinterpret_cast<unsigned long long*>(dead + (r >> 6)),
+                                                (unsigned long long)bit);
+        mine += (old & bit) ? 0u : 1u;
+    }
+    mine = wave_reduce_u32(mine, [](uint32_t x, uint32_t y) { return x + y; });
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(newly, mine);
+}
+
+// The filter operand of every deleted row zeroed, driven by the bitset: one wave per word of 64
+// rows, its lanes writing 16-byte zeros along each deleted row of fop (row_bytes = ld, a multiple
+// of 64).  A deleted row then scores exactly 0 in every filter kernel.  The fop_s sample holds one
+// row per kSampleStride-row block, as loaded the block's first.  Every block with a deleted row
+// gets its fop_s row rewritten so that the sample is the live rows thinned 1 in kSampleStride: it
+// becomes the operand of the block's live row whose rank among the shard's live rows is a multiple
+// of kSampleStride (at most one: a block has <= kSampleStride live rows of consecutive ranks) --
+// quantized as k_rows_to_i8_sample quantizes, with the scale its group of sample rows already
+// has, clamped to +-127 (the sample only places the threshold; no certification depends on it) --
+// or zeros when the block has no such row.  dead_blk: launch_mask_list_count's prefix sums over
+// the bitset itself, i.e. the deleted rows ahead of every kMaskBlockWords words.
+__global__ __launch_bounds__(256) void k_dead_zero_fop(const uint64_t* __restrict__ dead, uint64_t n,
+                                                       const uint32_t* __restrict__ dead_blk, uint32_t row_bytes,
+                                                       uint8_t* __restrict__ fop, uint8_t* __restrict__ fop_s,
+                                                       const float* __restrict__ rows, uint32_t dim,
+                                                       const float* __restrict__ scales_s) {
+    static_assert(kSampleStride == 32, "two sample blocks per word of the bitset");
+    const int lane = threadIdx.x & 63;
+    const uint64_t words = (n + 63) / 64;
+    const uint32_t units = row_bytes / 16, ld = row_bytes;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < words; w += (uint64_t)gridDim.x * 4) {
+        const uint64_t x0 = mask_word(dead, w, n);  // (wave-uniform)
+        if (!x0) continue;
+        uint64_t x = x0;
+        while (x) {
+            const uint32_t b = (uint32_t)__builtin_ctzll(x);
+            x &= x - 1;
+            uint4* row = reinterpret_cast<uint4*>(fop + (w * 64 + b) * row_bytes);
+            for (uint32_t u = lane; u < units; u += kWave) row[u] = z;
+        }
+        // the deleted rows ahead of this word: those ahead of its block of words, plus the words between
+        const uint64_t w0 = w / kMaskBlockWords * kMaskBlockWords;
+        uint32_t before = 0;
+        for (uint64_t v = w0 + lane; v < w; v += kWave) before += (uint32_t)__popcll(dead[v]);
+        before = dead_blk[w / kMaskBlockWords] + wave_reduce_u32(before, [](uint32_t p, uint32_t q) { return p + q; });
+        const uint64_t in_n = n - w * 64 >= 64 ? ~0ull : (1ull << (n - w * 64)) - 1ull;  // rows of the shard
+        for (uint32_t j = 0; j < 2; ++j) {
+            const uint64_t b0 = w * 64 + 32 * j;  // the block's first row
+            const uint32_t gone = (uint32_t)(x0 >> (32 * j));
+            if (b0 >= n || !gone) continue;
+            uint32_t live = ~gone & (uint32_t)(in_n >> (32 * j));
+            const uint64_t rank0 = b0 - before - (j ? (uint32_t)__popc((uint32_t)x0) : 0u);  // live rows ahead of b0
+            uint32_t t = (uint32_t)((kSampleStride - rank0 % kSampleStride) % kSampleStride);
+            const uint64_t rs = b0 / kSampleStride;  // sample row
+            if (t >= (uint32_t)__popc(live)) {
+                uint4* srow = reinterpret_cast<uint4*>(fop_s + rs * row_bytes);
+                for (uint32_t u = lane; u < units; u += kWave) srow[u] = z;
+                continue;
+            }
+            for (; t; --t) live &= live - 1;  // (its t-th live row)
+            const float* a = rows + (b0 + (uint32_t)__builtin_ctz(live)) * (uint64_t)ld;
+            double ss = 0.0;
+            for (uint32_t c = lane; c < dim; c += kWave) {
+                const double v = a[c];
+                ss += v * v;
+            }
+            ss = wave_sum_f64(ss);
+            const double inv = (ss > 0.0 && ss < 1e300) ? 1.0 / sqrt(ss) : 0.0;
+            const double s = scales_s[rs / kSampleScaleRows];
+            for (uint32_t c0 = lane * 4; c0 < ld; c0 += 4 * kWave) {
+                int8_t qv[4] = {0, 0, 0, 0};
+                if (inv > 0.0) {
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj)
+                        if (c0 + jj < dim) qv[jj] = quant_i8((double)a[c0 + jj] * inv, s);
+                }
+                *reinterpret_cast<char4*>(fop_s + rs * row_bytes + c0) = make_char4(qv[0], qv[1], qv[2], qv[3]);
+            }
+        }
+    }
+}
+
+// out[w] = allow[w] & ~dead[w] (allow = nullptr: ~dead[w], the live rows' mask) over the mask's
+// ceil(n / 64) words; the tail bits of the last word are left to the readers (mask_word).
+__global__ __launch_bounds__(256) void k_dead_andnot(const uint64_t* __restrict__ allow,
+                                                     const uint64_t* __restrict__ dead, uint64_t words,
+                                                     uint64_t* __restrict__ out) {
+    for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < words; w += (uint64_t)gridDim.x * blockDim.x)
+        out[w] = (allow ? allow[w] : ~0ull) & ~dead[w];
+}
+
+hipError_t launch_dead_check(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, uint32_t* bad,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(k_dead_check, dim3(grid_for(n_ids, 256, 2048)), dim3(256), 0, s, ids, n_ids, lo, n, bad);
+    return hipGetLastError();
+}
+hipError_t launch_dead_apply(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, uint64_t* dead,
+                             uint32_t* newly, hipStream_t s) {
+    hipLaunchKernelGGL(k_dead_apply, dim3(grid_for(n_ids, 256, 2048)), dim3(256), 0, s, ids, n_ids, lo, n, dead, newly);
+    return hipGetLastError();
+}
+hipError_t launch_dead_zero_fop(const uint64_t* dead, uint64_t n, const uint32_t* dead_blk, uint32_t row_bytes,
+                                uint8_t* fop, uint8_t* fop_s, const float* rows, uint32_t dim, const float* scales_s,
+                                hipStream_t s) {
+    if (row_bytes % 64 != 0 || dim > row_bytes) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dead_zero_fop, dim3(grid_for((n + 63) / 64, 4, 4096)), dim3(256), 0, s, dead, n, dead_blk,
+                       row_bytes, fop, fop_s, rows, dim, scales_s);
+    return hipGetLastError();
+}
+hipError_t launch_dead_andnot(const uint64_t* allow, const uint64_t* dead, uint64_t n, uint64_t* out, hipStream_t s) {
+    const uint64_t words = (n + 63) / 64;
+    hipLaunchKernelGGL(k_dead_andnot, dim3(grid_for(words, 256, 2048)), dim3(256), 0, s, allow, dead, words, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_mask_list_count(const uint64_t* allow, uint64_t n, uint32_t* blk, hipStream_t s) {
     const uint32_t n_blk = mask_blocks(n);
     hipLaunchKernelGGL(k_mask_count, dim3(n_blk), dim3(256), 0, s, allow, n, blk);

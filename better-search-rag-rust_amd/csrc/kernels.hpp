@@ -96,6 +96,26 @@ hipError_t launch_mask_list_scatter(const uint64_t* allow, uint64_t n, const uin
 hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
                            uint64_t n, uint32_t* raw, uint32_t* items, hipStream_t s);
 
+// Tombstones.  dead: the index's bitset of deleted rows, bit (i & 63) of word
+// (i >> 6) set = local row i is deleted; no bit at a position >= n is ever set.
+// *bad += the ids outside [lo, lo + n).
+hipError_t launch_dead_check(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, uint32_t* bad,
+                             hipStream_t s);
+// The bits of rows ids[i] - lo set (atomicOr); *newly += the rows whose bit was clear before.
+hipError_t launch_dead_apply(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, uint64_t* dead,
+                             uint32_t* newly, hipStream_t s);
+// Zeros over the fop row of every deleted row: it scores exactly 0 in every filter kernel.  The
+// fop_s row of every kSampleStride-row block with a deleted row becomes the operand of the block's
+// live row whose rank among the live rows is a multiple of kSampleStride, or zeros when it has
+// none: the sample is the live rows thinned 1 in kSampleStride (rows: the f32 slab
+// [n_pad][row_bytes]; scales_s: the sample operand's scales, kept; dead_blk
+// [mask_blocks(n) + 1]: launch_mask_list_count over dead).  row_bytes = ld, a multiple of 64.
+hipError_t launch_dead_zero_fop(const uint64_t* dead, uint64_t n, const uint32_t* dead_blk, uint32_t row_bytes,
+                                uint8_t* fop, uint8_t* fop_s, const float* rows, uint32_t dim, const float* scales_s,
+                                hipStream_t s);
+// out = allow & ~dead over the mask's ceil(n / 64) words (allow = nullptr: ~dead, the live rows).
+hipError_t launch_dead_andnot(const uint64_t* allow, const uint64_t* dead, uint64_t n, uint64_t* out, hipStream_t s);
+
 // ---- MFMA candidate filter (k_filter.hip) ---------------------------------------------
 struct GemmArgs {
     const uint8_t* A;       // filter rows [n_pad][row_bytes]
@@ -237,7 +257,10 @@ struct RescoreArgs {
     uint64_t* res_idx;          // [nq][k] (nullptr: no fused finalize)
     float* res_dist;
     uint32_t* res_cnt;          // [nq]
-    uint64_t offset, n_rows;    // global index of local row 0; shard rows (count = min(k, n))
+    uint64_t offset, n_rows;    // global index of local row 0; the shard's live rows (count = min(k, n_rows))
+    // Tombstones (k_rescore, k_rescore_kp): the index's bitset of deleted rows --
+    // a candidate whose bit is set offers no key.  nullptr: no row of the index is deleted.
+    const uint64_t* dead;
     // (optional) the host mirror of the same rows (fine-grained pinned memory): every result row
     // is written there too, by the wave that finalizes it, so the publish copies only the status
     // words (the standard path; the global-threshold path publishes its whole buffer)

@@ -161,6 +161,30 @@ int bsr_index_global_offset(const bsr_index* ix, uint64_t* out);
  * PolarsVectorstore::get_many(SliceArgs{offset,length}) / get (polars.rs:121-169). */
 int bsr_index_get_many(const bsr_index* ix, uint64_t offset, uint64_t count, float* out);
 
+/* ---- tombstones: deleted rows of a loaded shard, honoured by every search.
+ * Row positions never move: bsr_index_count, bsr_index_get_many (a deleted row's stored values
+ * included) and the global indices of live rows are unchanged.  Every search -- bsr_local_top_k,
+ * bsr_local_top_k_masked (over allow & ~deleted), the parallel search -- returns the reference's
+ * result over a store that holds only the live rows, each keeping its global index:
+ * out_count[q] = min(k, live), entries past the count (~0, +inf); zero live rows is not an error.
+ * bsr_index_load clears the tombstones; bsr_index_append keeps them, and the appended rows are
+ * live.  There is no undelete and no compaction.  The plain search keeps its fast path (graph
+ * replay from the second search of a shape after a delete); a parallel search takes the standard
+ * path (BSR_PATH_GLOBAL_TAU clear) while any row of this rank's shard is deleted.
+ *
+ * Mark rows as deleted.  ids are GLOBAL indices as the searches return them (global_offset + local
+ * row), host or device memory (device ids complete before the call, as queries), any order,
+ * duplicates allowed, n_ids < 2^32.  All or nothing: an id outside [global_offset, global_offset
+ * + n) -> BSR_E_INVALID and no row changes.  *out_deleted (optional) = rows that went live ->
+ * deleted in this call.  Not loaded: BSR_E_STATE.  n_ids = 0: BSR_OK.  A one-time mutation like
+ * load and append: it synchronizes with the index's stream. */
+int bsr_index_delete(bsr_index* ix, const uint64_t* ids, uint64_t n_ids, uint64_t* out_deleted);
+int bsr_index_live_count(const bsr_index* ix, uint64_t* out);          /* n - deleted rows */
+/* bit (i & 63) of word (i >> 6) set = local row i is deleted; words must equal ceil(n / 64)
+ * (BSR_E_INVALID otherwise); host or device out.  (~ of it is a valid allow mask.)  Not loaded:
+ * BSR_E_STATE. */
+int bsr_index_deleted_mask(const bsr_index* ix, uint64_t* out_words, uint64_t words);
+
 /* ---- a-2: compute_local_top_k for n_queries queries (row-major [n_queries][dim] f32).
  * out_idx/out_dist are [n_queries][k]; row q holds out_count[q] = min(k, n_rows) entries
  * in (distance asc, global index asc) order.  Indices are global (offset added). ------ */
