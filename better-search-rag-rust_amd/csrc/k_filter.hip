@@ -29,15 +29,6 @@ typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 typedef __attribute__((ext_vector_type(16))) int i32x16_t;
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-struct OpI8 {
-    using frag_t = i32x4_t;
-    using acc_t = i32x16_t;
-    static constexpr bool kInt = true;
-    __device__ __forceinline__ static acc_t mfma(const frag_t& a, const frag_t& b, const acc_t& c) {
-        return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
-    }
-};
-
 constexpr int kSlots = 4;     // LDS ring slots (3 slices in flight + the one being read)
 constexpr int kSliceB = 64;   // bytes of K per row per slice
 constexpr int kWCap = 256;    // candidate buffer entries per wave (one is the counter)
@@ -88,15 +79,15 @@ __device__ __forceinline__ void mid_barrier() {
 // there is not hidden behind another wave's MFMAs).
 // (Ablation variants of this kernel live in tools/microbench/k_filter_lab.hip.)
 // ------------------------------------------------------------------------------------
-template <class Op, bool EMIT>
+template <bool EMIT>
 __global__ __launch_bounds__(kThreads, 2) void k_filter(GemmArgs p) {
-    using frag_t = typename Op::frag_t;
-    using acc_t = typename Op::acc_t;
+    using frag_t = i32x4_t;    // one v_mfma_i32_32x32x32_i8 operand: 16 bytes of K per lane
+    using acc_t = i32x16_t;
     constexpr int BM = kFilterTile, BN = kFilterTile;
     constexpr int A_BYTES = BM * kSliceB, B_BYTES = BN * kSliceB;
     constexpr int SLOT = A_BYTES + B_BYTES;
     constexpr int EM_BYTES = EMIT ? 8 * kWCap * 12 : 0;
-    constexpr bool kScaleDMA = EMIT && Op::kInt;
+    constexpr bool kScaleDMA = EMIT;
     __shared__ __attribute__((aligned(1024))) uint8_t lds[kSlots * SLOT + EM_BYTES + (kScaleDMA ? 8 * 16 : 0)];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wr = w >> 2, wc = w & 3;
@@ -187,7 +178,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_filter(GemmArgs p) {
     for (int n = 0; n < 2; ++n) {
         const uint32_t q = qt * BN + wc * 64 + n * 32 + (lane & 31);
         if (EMIT) tau[n] = p.tau[q];
-        if (Op::kInt) sbq[n] = p.b_scale[q];
+        sbq[n] = p.b_scale[q];
     }
 
     acc_t acc[4][2];
@@ -212,20 +203,17 @@ __global__ __launch_bounds__(kThreads, 2) void k_filter(GemmArgs p) {
 #pragma unroll
             for (int m = half * 2; m < half * 2 + 2; ++m)
 #pragma unroll
-                for (int n = 0; n < 2; ++n) acc[m][n] = Op::mfma(fa[m], fb[n], z);
+                for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], z, 0, 0, 0);
         } else {
 #pragma unroll
             for (int m = half * 2; m < half * 2 + 2; ++m)
 #pragma unroll
-                for (int n = 0; n < 2; ++n) acc[m][n] = Op::mfma(fa[m], fb[n], acc[m][n]);
+                for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], acc[m][n], 0, 0, 0);
         }
     };
-    // The score of accumulator element v of block m (int8: exact integer dot, then the two
-    // scale multiplies in this fixed order; the candidate keys use the same expression).
-    auto score = [&](auto v, float sc_m, int n) -> float {
-        if constexpr (Op::kInt) return ((float)v * sc_m) * sbq[n];
-        else return v;
-    };
+    // The score of accumulator element v of block m: the exact integer dot, then the two scale
+    // multiplies in this fixed order (the candidate keys use the same expression).
+    auto score = [&](int v, float sc_m, int n) -> float { return ((float)v * sc_m) * sbq[n]; };
 
     // Prologue: slices 0..min(J,3)-1 issued; wait for slice 0; F0 <- (0, kk=0).
     set_issue_tile();
@@ -308,12 +296,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_filter(GemmArgs p) {
                         float v[16];
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            float s_r = 1.0f;
-                            if constexpr (Op::kInt) {
-                                uint32_t tr = rbase + (r & 3) + 8 * (r >> 2);
-                                tr = tr < p.n_rows ? tr : p.n_rows - 1;
-                                s_r = p.a_scale[tr / p.a_scale_rows];
-                            }
+                            uint32_t tr = rbase + (r & 3) + 8 * (r >> 2);
+                            tr = tr < p.n_rows ? tr : p.n_rows - 1;
+                            const float s_r = p.a_scale[tr / p.a_scale_rows];
                             v[r] = score(acc[m][n][r], s_r, n);
                         }
                         float* srow = p.S + (uint64_t)(qt * BN + ql) * p.s_ld;
@@ -348,15 +333,15 @@ __global__ __launch_bounds__(kThreads, 2) void k_filter(GemmArgs p) {
                             }
                         };
                         // group maxima: group g = registers 4g..4g+3 = rows rbase + 8g + 0..3
-                        std::remove_reference_t<decltype(acc[m][n][0])> gm[4];
+                        int gm[4];
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            auto x = acc[m][n][4 * g], y = acc[m][n][4 * g + 2];
+                            int x = acc[m][n][4 * g], y = acc[m][n][4 * g + 2];
                             x = x > acc[m][n][4 * g + 1] ? x : acc[m][n][4 * g + 1];
                             y = y > acc[m][n][4 * g + 3] ? y : acc[m][n][4 * g + 3];
                             gm[g] = x > y ? x : y;
                         }
-                        auto mxv = gm[0] > gm[1] ? gm[0] : gm[1];
+                        int mxv = gm[0] > gm[1] ? gm[0] : gm[1];
                         mxv = mxv > gm[2] ? mxv : gm[2];
                         mxv = mxv > gm[3] ? mxv : gm[3];
                         if (__ballot(score(mxv, sc[m], n) >= tau[n])) {
@@ -535,40 +520,29 @@ extern "C" int bsr_lab_filter_stamps(unsigned long long* out, int reset) {
         __builtin_amdgcn_sched_barrier(0);                                              \
     } while (0)
 #endif
-// DEFER (lab): the emission epilogue in front of the next tile's first MFMAs -- 1.9% faster at
-// the 1.25M-row shard, 4% slower at tau = inf, even at 10M (profiles/r04b_fab_*.txt): not kept.
-// TAILX: the dynamic tail in 8 XCD-local pools (the product, tail = 1/8); 0 = one counter per
-// query tile (round 3); 1 or 2 = half or all of the tiles dynamic (no gain: r04c_fab_*.txt).
-// L2, FW (lab, round 5): level 2's passing row blocks as a bool array (1) instead of a bit mask
-// (0); FW = 0: no explicit vmcnt(0) in the flush path.
-// KSB (lab, round 6, timing only at tau = inf): a bound on the K-split wave pair (each wave of a
-// pair holding 64 queries for half of K, the partial sums exchanged through LDS): 1 = every other
-// fragment read skipped (the pair's halved LDS fragment bytes per MFMA); 2 = that plus the
-// exchange's cost per wave and tile (16 KiB of accumulators written to LDS, read back and added).
-template <bool EMIT, int NK, int EPI = 0, int TAILX = 8, int GANG = 2, int RING = 0, int L2 = 0, int FW = 1,
-          int KSB = 0>
+// Two builds of the kernel ship (launch_filter picks one per launch):
+//   GANGS = true   the gang build, every NK of both passes: row-stream gangs (GANG = 2), level 2's
+//                  passing row blocks as a bit mask, an explicit vmcnt(0) in the flush path;
+//   GANGS = false  the small-shard build, emit NK = 12 only: no gang code compiled, level 2's
+//                  passing row blocks as a bool array (L2), no explicit wait in the flush (!FW).
+// Both take their dynamic tail from the 8 XCD-local pools.  The variants that were measured and
+// dropped -- a deferred, staggered or staged emission epilogue, 12-slot rings, one tail counter
+// per query tile or larger tails, the K-split bound -- are recorded in DESIGN.md §5; their code is
+// this file at commit 1028ff6 (template parameters EPI, RING, TAILX, KSB), which
+// tools/microbench/filter_hist times against this one.
+template <bool EMIT, int NK, bool GANGS = true>
 __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
-    constexpr bool DEFER = EPI == 1, STAGE = EPI == 2 && EMIT;
-    // EPI = 3 (lab, stagger): only waves 4-7 -- the SIMD partners of waves 0-3 -- defer their
-    // epilogue, so one wave of each SIMD runs its tile-end VALU work beside the other's MFMAs
-    constexpr bool SPLIT = EPI == 3 && EMIT;
-    // ring slots, slices issued ahead (RING, lab: 12 slots -- slot = slice index within the tile
-    // for NK = 12 -- with A = 9 / 10 / 6 and a smaller emission ring to fit the LDS)
-    constexpr int S = RING ? 12 : 8, A = RING == 1 ? 9 : RING == 2 ? 10 : 6;
+    constexpr int GANG = GANGS ? 2 : 0;  // tiles a gang member may run ahead of the slowest
+    constexpr bool L2 = !GANGS, FW = GANGS;
+    constexpr int S = 8, A = 6;  // ring slots, slices issued ahead
     // the barrier wait's DMA count (slices <= jj + 3 landed: A - 4 younger ones in flight), the
     // last odd slice at which the tile's scale load / claim is younger than the slice waited
     // for, and the slice after the first barrier that has them complete
     constexpr int kWaitN = A - 4, kYoung = A - 4, kClaimUse = ((A - 4) % 2 == 0 ? A - 3 : A - 2) + 1;
     constexpr int BM = 128, BN = kFilterTile, NT = 512, SLOT = BM * kSliceB;
-    constexpr int CAP = RING ? 7 : 10;  // candidate ring entries per (lane, query block)
+    constexpr int CAP = 10;  // candidate ring entries per (lane, query block)
     static_assert(NK % 2 == 0 && NK >= 2 && NK <= 12, "even slice counts up to 768 bytes");
-    // STAGE: per-query LDS lists [BN][QCAP] keys + counts, the stage of raw blocks [NSTG][1 KiB]
-    // + their records [NSTG][4 words], the queries' {scale, tau} [BN][2], the stage count
-    constexpr int QCAP = 32, NSTG = 16;
-    constexpr int ST_QL = 0, ST_STG = ST_QL + BN * QCAP * 8, ST_META = ST_STG + NSTG * 1024,
-                  ST_QPAR = ST_META + NSTG * 16, ST_QCNT = ST_QPAR + BN * 8, ST_CNT = ST_QCNT + BN * 4,
-                  ST_BYTES = ST_CNT + 16;
-    constexpr int EM_BYTES = !EMIT ? 0 : STAGE ? ST_BYTES : NT * 2 * CAP * 8;
+    constexpr int EM_BYTES = EMIT ? NT * 2 * CAP * 8 : 0;
     // SAMPLE, compact: the workgroup's maxima [tile][4][256 queries], written to S at the end
     constexpr int SB_BYTES = EMIT ? 0 : kSampleTilesPerWG * 4 * BN * 4;
     __shared__ __attribute__((aligned(1024))) uint8_t lds[S * SLOT + EM_BYTES + SB_BYTES + 16];
@@ -577,7 +551,6 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     uint32_t* const lds_ids = reinterpret_cast<uint32_t*>(lds + S * SLOT + EM_BYTES + SB_BYTES);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t wu = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool dfr = DEFER || (SPLIT && wu >= 4);  // (wave-uniform) this wave defers its epilogue
     uint64_t* const lkeys = reinterpret_cast<uint64_t*>(lds + S * SLOT) + tid;
     uint32_t ecnt[2] = {0, 0};
 
@@ -610,18 +583,18 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     constexpr uint32_t kEnd = 0xFFFFFFFFu;
     constexpr bool kStaticSched = NK > A;
     const bool dyn = EMIT && kStaticSched && p.tail != nullptr && active;
-    const uint32_t n_st = dyn ? n_rt - n_rt / (TAILX ? TAILX : kTailDiv) : n_rt;
+    const uint32_t n_st = dyn ? n_rt - n_rt / kTailDiv : n_rt;
     const uint32_t my_static = (active && g0 < n_st) ? (n_st - 1 - g0) / RG + 1 : 0;
     // (one lane) claim the next tail tile of this query tile: the counter's old value, turned
     // into a tile id by tail_id() where it is consumed -- not at once, which would wait for the
     // atomic and, in order, for every DMA in flight.  The address is one the compiler cannot
     // prove uniform: the atomic optimizer would otherwise aggregate the atomic across the wave
     // and consume its result immediately.
-    // TAILX: the tail is split into 8 pools of consecutive tiles, pool x claimed first by the
+    // The tail is split into 8 pools of consecutive tiles, pool x claimed first by the
     // workgroups on XCD x (counter tail[x * n_qt + qt]), so that the n_qt workgroups reading a
     // tail tile sit on one XCD and share it through its L2; a workgroup whose own pool is empty
-    // steals from the next XCD's pools (the balancing the tail exists for).  Without TAILX one
-    // counter per query tile hands every tail tile to workgroups of different XCDs.
+    // steals from the next XCD's pools (the balancing the tail exists for).  (One counter per
+    // query tile would hand every tail tile to workgroups of different XCDs.)
     const uint32_t n_tail = n_rt - n_st, pool_sz = (n_tail + 7) / 8;
     uint32_t cpool = xcd, pools_tried = 1;  // (lane 0 of wave 0) the pool claimed from
     auto pool_n = [&](uint32_t x) -> uint32_t {
@@ -631,19 +604,15 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     auto claim_raw = [&]() -> uint32_t {
         uint32_t z;
         asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-        return atomicAdd(p.tail + (TAILX ? cpool * p.n_qt : 0u) + qt + z, 1u);
+        return atomicAdd(p.tail + cpool * p.n_qt + qt + z, 1u);
     };
     auto tail_id = [&](uint32_t v) -> uint32_t {
-        if constexpr (!TAILX) {
-            return n_st + v < n_rt ? n_st + v : kEnd;
-        } else {
-            for (;;) {  // (own pool empty: claim from the next XCD's, synchronously -- rare)
-                if (v < pool_n(cpool)) return n_st + cpool * pool_sz + v;
-                if (pools_tried == 8) return kEnd;
-                ++pools_tried;
-                cpool = (cpool + 1) & 7;
-                v = atomicAdd(p.tail + cpool * p.n_qt + qt, 1u);
-            }
+        for (;;) {  // (own pool empty: claim from the next XCD's, synchronously -- rare)
+            if (v < pool_n(cpool)) return n_st + cpool * pool_sz + v;
+            if (pools_tried == 8) return kEnd;
+            ++pools_tried;
+            cpool = (cpool + 1) & 7;
+            v = atomicAdd(p.tail + cpool * p.n_qt + qt, 1u);
         }
     };
     auto claim = [&]() -> uint32_t { return tail_id(claim_raw()); };
@@ -700,58 +669,6 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
         if constexpr (FW) __builtin_amdgcn_s_waitcnt(0x0F70);
     };
 
-    // STAGE: emission balanced over the workgroup's waves.  A wave whose tile passes level 1
-    // copies each passing 16-row x 16-query block's raw accumulators (1 KiB) to the stage with
-    // a record {first row, first query, block scale}; after the next tile's first barrier EVERY
-    // wave scores a 1/8 share of the staged values (one per thread) and appends the passing
-    // (score, row) keys to per-query LDS lists (an LDS atomic per key), flushed to the global
-    // lists at the end.  The emitting wave no longer holds the workgroup at the next barrier
-    // while it appends (the level-2 skew of the per-lane rings: DESIGN.md §5).
-    uint8_t* const est = lds + S * SLOT;
-    uint64_t* const st_ql = reinterpret_cast<uint64_t*>(est + ST_QL);
-    int* const st_blk = reinterpret_cast<int*>(est + ST_STG);
-    uint32_t* const st_meta = reinterpret_cast<uint32_t*>(est + ST_META);
-    float* const st_qpar = reinterpret_cast<float*>(est + ST_QPAR);
-    uint32_t* const st_qcnt = reinterpret_cast<uint32_t*>(est + ST_QCNT);
-    uint32_t* const st_cnt = reinterpret_cast<uint32_t*>(est + ST_CNT);
-    // one value of a staged or inline block: query ql of the tile (local), corpus row `row`
-    auto st_append = [&](int iv, float scb, uint32_t row, uint32_t ql) {
-        const float v = ((float)iv * scb) * st_qpar[2 * ql];
-        if (v >= st_qpar[2 * ql + 1] && row < p.n_rows) {
-            uint32_t pos;
-            const uint32_t addr = (uint32_t)(uintptr_t)(st_qcnt + ql);
-            asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(pos) : "v"(addr), "v"(1u) : "memory");
-            if (pos < (uint32_t)QCAP) {
-                st_ql[ql * QCAP + pos] = score_key(v, row);
-            } else {  // (list full: straight to the global list)
-                const uint32_t q = qt * BN + ql;
-                const uint32_t gp = atomicAdd(p.cnt + q, 1u);
-                if (gp < p.cap) p.cand[(uint64_t)q * p.cap + gp] = score_key(v, row);
-                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): keep the DMA stream's counted waits exact
-            }
-        }
-    };
-    // every thread: the staged values v = tid, tid + 512, ... of n staged blocks
-    auto st_process = [&](uint32_t n) {
-        for (uint32_t v = tid; v < n * 256; v += NT) {
-            const uint32_t e = v >> 8, i = v & 255, l = i >> 2;
-            const int iv = st_blk[v];
-            const uint32_t* m = st_meta + 4 * e;
-            st_append(iv, __uint_as_float(m[2]), m[0] + 4 * (l >> 4) + (i & 3), m[1] + (l & 15));
-        }
-    };
-    if constexpr (STAGE) {
-        if (lane < 16)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                const uint32_t ql = w * 32 + nb * 16 + lane;
-                st_qpar[2 * ql] = sbq[nb];
-                st_qpar[2 * ql + 1] = tau[nb];
-            }
-        if (tid < BN) st_qcnt[tid] = 0;
-        if (tid == 0) *st_cnt = 0;
-    }
-
     // LDS-DMA: wave w fills rows 16w .. 16w+15 of each slice (1 KiB per instruction); the
     // source chunk is XOR-swizzled so that LDS chunk position p holds global chunk p ^ swz.
     const uint32_t lrow = w * 16 + (lane >> 2);
@@ -803,46 +720,6 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     };
 
     i32x4v_t acc[8][2];
-    // (DEFER) the emission epilogue of the PREVIOUS tile, one 32-row pair at a time (row blocks
-    // 2s, 2s+1: one block scale), placed in front of the next tile's first MFMAs on those row
-    // blocks, whose C = 0 operand overwrites them: the lane's maximum per query block, scored
-    // once, one ballot per pair; a pair that passes appends its passing rows as level 2 does.
-    // Its VALU work runs beside the partner wave's MFMAs instead of in a tile-end phase that
-    // every wave of the workgroup reaches together.
-    auto epi_pair = [&](int s, float scs, uint32_t rte) {
-        int bm[2][2];
-        bool pass = false;
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const i32x4v_t& x = acc[2 * s + h][nb];
-                bm[h][nb] = max(max(x[0], x[1]), max(x[2], x[3]));
-            }
-            const int m = max(bm[0][nb], bm[1][nb]);
-            pass |= ((float)m * scs) * sbq[nb] >= tau[nb];
-        }
-        if (!__ballot(pass)) return;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                if (!__ballot(((float)bm[h][nb] * scs) * sbq[nb] >= tau[nb])) continue;
-                if (__ballot(ecnt[nb] > (uint32_t)(CAP - 4))) flush_ring(nb);  // room for 4 rows
-                const i32x4v_t& x = acc[2 * s + h][nb];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = ((float)x[r] * scs) * sbq[nb];
-                    const uint32_t row = rte * BM + (2 * s + h) * 16 + 4 * (lane >> 4) + r;
-                    lkeys[(nb * CAP + ecnt[nb]) * NT] = score_key(v, row);
-                    ecnt[nb] += (v >= tau[nb] && row < p.n_rows) ? 1u : 0u;
-                }
-            }
-        }
-    };
-    float sc_prev[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-    uint32_t rt_prev = 0;
-    uint32_t n_stg = 0;  // (STAGE) the previous tile's staged block count
     // the first two tiles of the sequence
     uint32_t cur_id = my_rt ? g0 : kEnd, nxt_id = my_rt > 1 ? g0 + RG : kEnd;
     if (dyn && my_static < 2) {
@@ -887,8 +764,7 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     unsigned long long fst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_a, st_b, st_loop0;
     BSR_FST(st_loop0);
 #endif
-    uint32_t t = 0;
-    for (; cur_id != kEnd; ++t) {
+    for (uint32_t t = 0; cur_id != kEnd; ++t) {
         const uint32_t rt = phys(cur_id);
         BSR_FCNT(4);
         if (kStatic && t) {
@@ -930,14 +806,6 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
             const bool bar_slice = (kt & 1) == 1;
 #pragma unroll
             for (int rb = 0; rb < 8; ++rb) {
-                if constexpr ((DEFER || SPLIT) && EMIT && kt == 0) {
-                    if (dfr && (rb & 1) == 0 && t > 0) epi_pair(rb >> 1, sc_prev[rb >> 1], rt_prev);
-                    // pin the first MFMAs on these row blocks below the epilogue (their C = 0
-                    // operand does not read the accumulators, so nothing else orders them, and
-                    // hoisted above it they would need a second set of accumulators)
-                    asm volatile("" : "+v"(fa[rb & 3]));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) {
                     if (kt == 0) {
@@ -948,9 +816,7 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (KSB && (rb & 1)) {
-                    // (lab KSB: this fragment read skipped; the register keeps an older fragment)
-                } else if (rb < 4) {
+                if (rb < 4) {
                     read_frag(jj, rb + 4);
                 } else {
                     read_frag(jj + 1, rb - 4);  // (past the stream's end: unused)
@@ -987,31 +853,9 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
 #endif
                     qs_wait_n(kWaitN + ((EMIT && kt <= kYoung) ? 1 + w0_req : 0));
                 }
-                if constexpr (STAGE) {
-                    // the previous tile's stage: its count read after the kt = 1 barrier (every
-                    // wave's stage writes landed before it), the values scored at kt = 2 (the
-                    // count's read long complete), the count reset after the kt = 3 barrier (every
-                    // wave has read it); the next stage writes follow the kt = 11 barrier
-                    if (kt == 1 && rb == 5) n_stg = min(*st_cnt, (uint32_t)NSTG);
-                    if (kt == 2 && rb == 0 && n_stg) st_process(n_stg);
-                    if (kt == 3 && rb == 5 && tid == 0) {
-                        *st_cnt = 0;
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    }
-                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
-        if constexpr (KSB == 2 && EMIT) {
-            // (lab KSB = 2, timing only) the pair's exchange: 16 KiB of this wave's accumulators to
-            // LDS (the emission rings' space: unused at tau = inf), read back and added
-            i32x4v_t* xs = reinterpret_cast<i32x4v_t*>(lds + S * SLOT + (w % 5) * 16384) + lane;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) xs[i * 64] = acc[i >> 1][i & 1];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i >> 1][i & 1] += xs[(15 - i) * 64];
-        }
         // ---- epilogue: block (rb, nb) holds rows 16rb + 4(lane >> 4) + r, query qq[nb]
         const float sc[4] = {scv.x, scv.y, scv.z, scv.w};
         bool stored = false;
@@ -1070,74 +914,6 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
                 }
                 stored = true;
             }
-        } else if constexpr (STAGE) {
-            // level 1 as below; the passing blocks go to the stage (or, when it is full, are
-            // appended by this wave at once)
-            const float sc_hi = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
-            const float sc_lo = fminf(fminf(sc[0], sc[1]), fminf(sc[2], sc[3]));
-            int mrb[2];
-            bool any = false;
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                int m = acc[0][nb][0];
-#pragma unroll
-                for (int rb = 0; rb < 8; ++rb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) m = (rb | r) ? max(m, acc[rb][nb][r]) : m;
-                mrb[nb] = m;
-                any |= ((float)m * (m >= 0 ? sc_hi : sc_lo)) * sbq[nb] >= tau[nb];
-            }
-            if (__ballot(any)) {
-                uint32_t M = 0;  // (uniform) passing blocks, bit 8 nb + rb
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    if (!__ballot(((float)mrb[nb] * (mrb[nb] >= 0 ? sc_hi : sc_lo)) * sbq[nb] >= tau[nb])) continue;
-#pragma unroll
-                    for (int rb = 0; rb < 8; ++rb) {
-                        const i32x4v_t& x = acc[rb][nb];
-                        const int bm = max(max(x[0], x[1]), max(x[2], x[3]));
-                        if (__ballot(((float)bm * sc[rb >> 1]) * sbq[nb] >= tau[nb])) M |= 1u << (8 * nb + rb);
-                    }
-                }
-                if (M) {
-                    uint32_t base = 0;
-                    if (lane == 0) {
-                        const uint32_t addr = (uint32_t)(uintptr_t)st_cnt;
-                        asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
-                                     : "=v"(base) : "v"(addr), "v"((uint32_t)__builtin_popcount(M)) : "memory");
-                    }
-                    base = __builtin_amdgcn_readfirstlane(__shfl(base, 0, kWave));
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int rb = 0; rb < 8; ++rb) {
-                            if (!((M >> (8 * nb + rb)) & 1u)) continue;
-                            const uint32_t slot = base + (uint32_t)__builtin_popcount(M & ((1u << (8 * nb + rb)) - 1u));
-                            const uint32_t row0 = rt * BM + rb * 16, q0 = w * 32 + nb * 16;
-                            if (slot < (uint32_t)NSTG) {
-                                *reinterpret_cast<i32x4v_t*>(st_blk + slot * 256 + lane * 4) = acc[rb][nb];
-                                if (lane == 0)
-                                    *reinterpret_cast<uint4*>(st_meta + 4 * slot) =
-                                        make_uint4(row0, q0, __float_as_uint(sc[rb >> 1]), 0u);
-                            } else {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r)
-                                    st_append(acc[rb][nb][r], sc[rb >> 1], row0 + 4 * (lane >> 4) + r, q0 + (lane & 15));
-                            }
-                        }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the stage is read after a barrier)
-                }
-            }
-        } else if constexpr (DEFER) {
-            // (the epilogue runs in front of the next tile's first MFMAs, or after the loop)
-            // (held in VGPRs: the loop's scalar registers are spoken for)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(sc_prev[i]) : "s"(sc[i]));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(rt_prev) : "s"(rt));
-        } else if (SPLIT && dfr) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(sc_prev[i]) : "s"(sc[i]));
-            asm volatile("v_mov_b32 %0, %1" : "=v"(rt_prev) : "s"(rt));
         } else {
             // level 1, one ballot per tile: the lane's integer maximum over all its 32 values of
             // each query block, scored with the tile's largest (or, for a negative maximum,
@@ -1215,28 +991,6 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
         if (stored) wait_vm0();  // global stores / atomics count in vmcnt: keep the waits exact
         cur_id = nxt_id;
         nxt_id = req ? __builtin_amdgcn_readfirstlane(lds_ids[t & 1]) : n2;
-    }
-    if constexpr (STAGE) {
-        // the last tile's stage, then the per-query lists to the global lists
-        __syncthreads();
-        const uint32_t n = min(*st_cnt, (uint32_t)NSTG);
-        __syncthreads();  // (everyone has read the count before it can change)
-        st_process(n);
-        __syncthreads();
-        if (tid < BN) {
-            const uint32_t c = min(st_qcnt[tid], (uint32_t)QCAP);
-            if (c) {
-                const uint32_t q = qt * BN + tid;
-                const uint32_t gp = atomicAdd(p.cnt + q, c);
-                for (uint32_t i = 0; i < c; ++i)
-                    if (gp + i < p.cap) p.cand[(uint64_t)q * p.cap + gp + i] = st_ql[tid * QCAP + i];
-            }
-        }
-    }
-    if constexpr ((DEFER || SPLIT) && EMIT) {  // the last tile's epilogue
-        if (dfr && t > 0)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) epi_pair(s, sc_prev[s], rt_prev);
     }
     wait_vm0();  // the stream's trailing DMAs land before the workgroup ends
 #ifdef BSR_FILTER_STAMPS
@@ -2179,19 +1933,19 @@ hipError_t launch_filter_skinny_top(const GemmArgs& a, hipStream_t s) {
 // kernel; other widths: k_filter.  (A one-wave-per-SIMD variant
 // with 64 queries per wave, tools/microbench/k_qs64_lab.hip, measured slower: DESIGN.md §5.)
 // Whether any workgroup of the emit filter can run in a row-stream gang (k_filter_qs16's `gang`
-// condition with its longest static stream).  Otherwise -- every shard of up to ~5.6M rows at 1000
-// queries, and configs[4]'s 16 query tiles -- the launch takes the small-shard build: no gang code
-// (GANG = 0), level 2's bool-array form (L2 = 1) and no explicit wait in the flush (FW = 0): 3-4%
-// faster than the gang build at 1M and 1.25M rows with emission, the same at tau = inf
-// (tools/microbench/filter_hist, profiles/r05c_hist_*, r05e_hist_*).  Round 6: its dynamic tail in
-// the XCD-local pools (TAILX = 8, as the gang build) instead of one counter per query tile -- HBM
-// fetch at the 1.25M-row shard 1.25x -> 1.005x the int8 rows, time within 0.4%
-// (profiles/r06b_fab_125.txt, r06b_fabpmc_1250000.txt: variants "small" / "smallx").  At 10M the
-// gang build stays: its HBM traffic is 1.1x the rows instead of 2x.
+// condition with its longest static stream).  Then the launch takes the gang build
+// k_filter_qs16<EMIT, NK>: at 10M rows its HBM traffic is 1.1x the rows instead of 2x.  Otherwise
+// -- every shard of up to ~5.6M rows at 1000 queries, and configs[4]'s 16 query tiles -- a 768-byte
+// emit launch takes the small-shard build k_filter_qs16<true, 12, false>: 3-4% faster than the gang
+// build at 1M and 1.25M rows with emission, the same at tau = inf (tools/microbench/filter_hist,
+// profiles/r05c_hist_*, r05e_hist_*).  Both claim their dynamic tail from the XCD-local pools: at
+// the 1.25M-row shard HBM fetch is 1.005x the int8 rows, against 1.25x with one counter per query
+// tile (profiles/r06b_fab_125.txt, r06b_fabpmc_1250000.txt).  The builds measured against these two
+// and dropped are in DESIGN.md §5; their code is this file at commit 1028ff6.
 static bool gang_possible(const GemmArgs& a, uint32_t grid) {
     if (!a.tail || a.n_qt < 2 || a.n_qt > 4) return false;
     const uint32_t G = (grid / 8) / a.n_qt, RG = 8 * G;
-    const uint32_t n_rt = (a.n_rows + 127) / 128 - a.s_tiles, n_st = n_rt - n_rt / 8;  // (TAILX = 8)
+    const uint32_t n_rt = (a.n_rows + 127) / 128 - a.s_tiles, n_st = n_rt - n_rt / kTailDiv;
     return RG && n_st && (n_st - 1) / RG + 1 >= kGangMinTiles;
 }
 
@@ -2200,9 +1954,11 @@ static void launch_filter(const GemmArgs& a, hipStream_t s) {
     const uint32_t nk = a.row_bytes / kSliceB, grid = filter_grid(a.n_qt);
     if (nk % 2 == 0 && nk <= 12) {
         const dim3 g(grid), b(512);
-        if (EMIT && nk == 12 && !gang_possible(a, grid)) {
-            BSR_KLAUNCH((k_filter_qs16<EMIT, 12, 0, 8, 0, 0, 1, 0>), g, b, s, a);
-            return;
+        if constexpr (EMIT) {  // (the sample pass has no small-shard build)
+            if (nk == 12 && !gang_possible(a, grid)) {
+                BSR_KLAUNCH((k_filter_qs16<true, 12, false>), g, b, s, a);
+                return;
+            }
         }
         switch (nk) {
             case 2: BSR_KLAUNCH((k_filter_qs16<EMIT, 2>), g, b, s, a); return;
@@ -2213,7 +1969,7 @@ static void launch_filter(const GemmArgs& a, hipStream_t s) {
             default: BSR_KLAUNCH((k_filter_qs16<EMIT, 12>), g, b, s, a); return;
         }
     }
-    BSR_KLAUNCH((k_filter<OpI8, EMIT>), dim3(grid), dim3(kThreads), s, a);
+    BSR_KLAUNCH((k_filter<EMIT>), dim3(grid), dim3(kThreads), s, a);
 }
 hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s) {
     launch_filter<false>(a, s);

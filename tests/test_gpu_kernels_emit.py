@@ -10,7 +10,7 @@ one scale per 32 rows, cnt zeroed as k_select_tau leaves it, tail = cnt + qpad (
 queries with a zero operand, scale 0 and tau = +inf.
 
 Builds reached: k_filter_qs16<true, NK> for NK = 2 .. 10, the small-shard NK = 12 build (the one
-launch_filter picks when no row-stream gang is possible), k_filter<OpI8, true>, k_filter_skinny2<Emit,
+launch_filter picks when no row-stream gang is possible), k_filter<true>, k_filter_skinny2<Emit,
 4 | 8 | 12 | 16>, k_filter_skinny_glds<Emit, 12> and k_filter_skinny<true>.  NOT reached: the gang
 build of k_filter_qs16<true, 12> -- it needs kGangMinTiles = 600 static tiles per row stream, about
 9.8M rows, which no test of a few seconds can hold; tests/test_gpu_full_size.py covers it end to end.
@@ -120,7 +120,7 @@ def test_emit_query_stationary(gpu, row_bytes):
 
 @pytest.mark.parametrize("row_bytes", (64, 192, 1152))
 def test_emit_general_filter(gpu, row_bytes):
-    """k_filter<OpI8, true> (odd slice counts, and more than 12 slices): 256-row tiles."""
+    """k_filter<true> (odd slice counts, and more than 12 slices): 256-row tiles."""
     rng = np.random.default_rng(42000 + row_bytes)
     for n in (1, 127, 129, 257, TAIL12):
         _run_shape(kc.EMIT, rng, n, row_bytes, 250, 256, what=f"rb={row_bytes}")
@@ -182,8 +182,8 @@ def _thresholds_live(M, live, qpad, kind, dense_q=None):
     (kc.EMIT, 768, 500, None),         # ... two query tiles
     (kc.EMIT, 384, 250, None),         # k_filter_qs16<true, 6>
     (kc.EMIT, 100, 250, None),         # k_filter_qs16<true, 2>
-    (kc.EMIT, 130, 250, None),         # k_filter<OpI8, true>, 192-byte rows
-    (kc.EMIT, 1100, 250, None),        # k_filter<OpI8, true>, 1152-byte rows
+    (kc.EMIT, 130, 250, None),         # k_filter<true>, 192-byte rows
+    (kc.EMIT, 1100, 250, None),        # k_filter<true>, 1152-byte rows
     (kc.SKINNY_EMIT, 768, 16, None),   # k_filter_skinny_glds<Emit, 12>
     (kc.SKINNY_EMIT, 768, 16, "0"),    # k_filter_skinny2<Emit, 12>
     (kc.SKINNY_EMIT, 200, 11, None),   # k_filter_skinny2<Emit, 4>

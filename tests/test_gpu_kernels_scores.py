@@ -3,7 +3,7 @@ sample kernels store equals ((float)I * s_block) * s_query of the exact integer 
 for bit, for every build a batch can reach:
 
   k_filter_qs16<false, NK>      NK = 2, 4, 6, 8, 10, 12 (row_bytes 128 .. 768, even slice counts)
-  k_filter<OpI8, false>         row_bytes 64, 192 (odd slice counts), 1152 (more than 12 slices)
+  k_filter<false>               row_bytes 64, 192 (odd slice counts), 1152 (more than 12 slices)
   k_filter_skinny2<Sample, NK>  NK = 4, 8, 12, 16 (batches of <= 16 queries, rows of <= 1024 bytes)
   k_filter_skinny<false>        row_bytes 1152
 

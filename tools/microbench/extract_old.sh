@@ -5,7 +5,7 @@
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
 repo=$(cd "$here/../.." && pwd)
-for spec in r02:48a1e10 static:541899f dyntail:e725bdc r03:c3c64cd xpools:aeb486c gangs:b6d2ae5; do
+for spec in r02:48a1e10 static:541899f dyntail:e725bdc r03:c3c64cd xpools:aeb486c gangs:b6d2ae5 r08:1028ff6; do
   tag=${spec%%:*}; c=${spec##*:}
   d="$here/old/$tag"; mkdir -p "$d"
   for f in k_filter.hip bsr_device.hpp kernels.hpp; do

@@ -76,13 +76,11 @@ int main(int argc, char** argv) {
     struct V { const char* name; void (*k)(bsr::GemmArgs); std::vector<float> t; int rs = 0; };
     std::vector<V> vs = {
         {"product", bsr::k_filter_qs16<true, 12>, {}},
-        // round 6: the K-split wave pair's bound (timing only, tau = inf is the reading)
-        {"ksb1hot", bsr::k_filter_qs16<true, 12, 0, 8, 2, 0, 0, 1, 1>, {}},
-        {"ksb2hot", bsr::k_filter_qs16<true, 12, 0, 8, 2, 0, 0, 1, 2>, {}},
-        // round 6: the small-shard build (what launch_filter takes below ~5.6M rows) with one tail
-        // counter per query tile (the product) and with the XCD-local tail pools
-        {"small", bsr::k_filter_qs16<true, 12, 0, 0, 0, 0, 1, 0>, {}},
-        {"smallx", bsr::k_filter_qs16<true, 12, 0, 8, 0, 0, 1, 0>, {}},
+        // the small-shard build (what launch_filter takes below ~5.6M rows).  (Round 6's rows
+        // "ksb1hot" / "ksb2hot", the K-split wave pair's bound, and "small", this build with one
+        // tail counter per query tile, instantiate parameters the kernel had up to commit 1028ff6;
+        // tools/microbench/filter_hist times kernels of that commit against today's.)
+        {"smallx", bsr::k_filter_qs16<true, 12, false>, {}},
     };
 
     hipEvent_t e0, e1;
@@ -124,10 +122,8 @@ int main(int argc, char** argv) {
     }
     bool same = true;
     for (size_t i = 1; i < vs.size(); ++i) {
-        const bool timing_only = strstr(vs[i].name, "hot") != nullptr;  // (ablations: other data, timing only)
-        printf("emitted sets %s vs %s: %s%s\n", vs[i].name, vs[0].name, sets[0] == sets[i] ? "IDENTICAL" : "DIFFER",
-               timing_only ? " (timing-only ablation)" : "");
-        same &= timing_only || sets[0] == sets[i];
+        printf("emitted sets %s vs %s: %s\n", vs[i].name, vs[0].name, sets[0] == sets[i] ? "IDENTICAL" : "DIFFER");
+        same &= sets[0] == sets[i];
     }
     fflush(stdout);
     if (!same) return 2;

@@ -1,7 +1,9 @@
 // Lab harness (round 5): the small-shard bisection.  The product emit filter k_filter_qs16<true,12>
 // against the same kernel at earlier commits of this repository (tools/microbench/extract_old.sh:
 // round 2's final kernel, the static DMA schedule, the dynamic tail, round 3's final kernel, the
-// XCD-local tail pools, the row-stream gangs), interleaved in one process (same clocks) on a
+// XCD-local tail pools, the row-stream gangs, and r08 = commit 1028ff6, the last one whose kernel
+// carried the lab template parameters EPI / TAILX / GANG / RING / L2 / FW / KSB: the variants
+// measured and dropped are instantiated from there), interleaved in one process (same clocks) on a
 // synthetic int8 shard; every variant must emit the same candidate set per query before it is
 // timed.  Build: make -C tools/microbench filter_hist   Run: ./filter_hist [rows] [queries] [rounds] [tau]
 #include "k_filter.hip"
@@ -11,6 +13,7 @@
 #include "old/r03/k_filter.hip"
 #include "old/xpools/k_filter.hip"
 #include "old/gangs/k_filter.hip"
+#include "old/r08/k_filter.hip"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -85,20 +88,27 @@ int main(int argc, char** argv) {
     const auto g_r03 = as_old<bsr_r03::GemmArgs>(g);
     const auto g_xp = as_old<bsr_xpools::GemmArgs>(g);
     const auto g_gang = as_old<bsr_gangs::GemmArgs>(g);
+    const auto g_r08 = as_old<bsr_r08::GemmArgs>(g);  // (today's GemmArgs: a plain copy)
     const dim3 G(grid), B(512);
     // FOCUS=1 (default): the product against its round-5 candidates and the two fastest earlier
     // kernels; FOCUS=0: every commit of the history as well
     const bool focus = getenv("FOCUS") == nullptr || atoi(getenv("FOCUS")) != 0;
     std::vector<V> vs = {
+        // the two shipped builds (product = the gang build, small = the small-shard build: the row
+        // "g0_l2b_fw0" of profiles/r05c_hist_*, r05e_hist_*) and the same two at r08; parent and
+        // parent_b are one kernel: the gap between their medians is the run's own noise
         {"product", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12>), G, B, 0, 0, g); }, {}},
+        {"parent", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12>), G, B, 0, 0, g_r08); }, {}},
+        {"parent_b", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12>), G, B, 0, 0, g_r08); }, {}},
+        {"small", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, false>), G, B, 0, 0, g); }, {}},
+        {"parent_small", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 8, 0, 0, 1, 0>), G, B, 0, 0, g_r08); }, {}},
         {"static", [&] { hipLaunchKernelGGL((bsr_static::k_filter_qs16<true, 12>), G, B, 0, 0, g_static); }, {}},
         {"dyntail", [&] { hipLaunchKernelGGL((bsr_dyntail::k_filter_qs16<true, 12>), G, B, 0, 0, g_dyn); }, {}},
-        // round-5 variants of the product: GANG = 0 (no gang code compiled), TAILX = 0 (one tail
-        // counter per query tile), L2 = 1 (level 2's bool-array form), FW = 0 (no explicit wait
-        // in the flush)
-        {"g0_l2b_fw0", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, 0, 8, 0, 0, 1, 0>), G, B, 0, 0, g); }, {}},
-        {"g0_t0_l2b_fw0", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, 0, 0, 0, 0, 1, 0>), G, B, 0, 0, g); }, {}},
-        {"g2_l2b_fw0", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, 0, 8, 2, 0, 1, 0>), G, B, 0, 0, g); }, {}},
+        // round-5 variants (r08's parameters): the small-shard build with TAILX = 0 (one tail
+        // counter per query tile); the gang build with L2 = 1 (level 2's bool-array form) and
+        // FW = 0 (no explicit wait in the flush)
+        {"g0_t0_l2b_fw0", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 0, 0, 0, 1, 0>), G, B, 0, 0, g_r08); }, {}},
+        {"g2_l2b_fw0", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 8, 2, 0, 1, 0>), G, B, 0, 0, g_r08); }, {}},
     };
     if (!focus) {
         std::vector<V> more = {
@@ -106,10 +116,10 @@ int main(int argc, char** argv) {
             {"r03", [&] { hipLaunchKernelGGL((bsr_r03::k_filter_qs16<true, 12>), G, B, 0, 0, g_r03); }, {}},
             {"xpools", [&] { hipLaunchKernelGGL((bsr_xpools::k_filter_qs16<true, 12>), G, B, 0, 0, g_xp); }, {}},
             {"gangs", [&] { hipLaunchKernelGGL((bsr_gangs::k_filter_qs16<true, 12>), G, B, 0, 0, g_gang); }, {}},
-            {"g0", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, 0, 8, 0>), G, B, 0, 0, g); }, {}},
-            {"g0_l2b", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, 0, 8, 0, 0, 1>), G, B, 0, 0, g); }, {}},
-            {"g0_fw0", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, 0, 8, 0, 0, 0, 0>), G, B, 0, 0, g); }, {}},
-            {"g0_t0", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, 0, 0, 0>), G, B, 0, 0, g); }, {}},
+            {"g0", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 8, 0>), G, B, 0, 0, g_r08); }, {}},
+            {"g0_l2b", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 8, 0, 0, 1>), G, B, 0, 0, g_r08); }, {}},
+            {"g0_fw0", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 8, 0, 0, 0, 0>), G, B, 0, 0, g_r08); }, {}},
+            {"g0_t0", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 0, 0>), G, B, 0, 0, g_r08); }, {}},
         };
         vs.insert(vs.end(), more.begin(), more.end());
     }
