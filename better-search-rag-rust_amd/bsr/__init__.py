@@ -57,6 +57,7 @@ BSR_PATH_SKINNY_TOP = 32
 BSR_PATH_TOP_RERUN = 64
 BSR_PATH_MASK_LIST = 128    # masked search: exact top-k over the allowed-row list
 BSR_PATH_MASK_FILTER = 256  # masked search: int8 filter, emitted lists cut by the mask
+BSR_PATH_MASK_GROUPS = 512  # bsr_local_top_k_masked_groups ran (with the MASK_LIST / MASK_FILTER bits)
 BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
 BSR_MASK_LIST = 1
 BSR_MASK_FILTER = 2
@@ -136,6 +137,7 @@ def lib() -> ctypes.CDLL:
         "bsr_index_deleted_mask": (ctypes.c_int, [_P, _P, u64]),
         "bsr_local_top_k": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, _P, _P]),
+        "bsr_local_top_k_masked_groups": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
         "bsr_comm_init": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(_P)]),
@@ -158,7 +160,7 @@ def lib() -> ctypes.CDLL:
     }
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
-                "bsr_index_deleted_mask"}
+                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -291,6 +293,26 @@ def pack_allow_mask(n: int, mask=None, ids=None) -> np.ndarray:
     packed = np.zeros(words * 8, np.uint8)
     packed[:(n + 7) // 8] = np.packbits(bits, bitorder="little")
     return packed.view("<u8").astype(np.uint64, copy=False)
+
+
+def pack_allow_masks(n: int, masks=None, ids=None) -> np.ndarray:
+    """G packed allow masks of an n-row shard, uint64 [G][ceil(n / 64)]: row g is
+    pack_allow_mask(n, mask=masks[g]) for a bool array masks [G][n], or
+    pack_allow_mask(n, ids=ids[g]) for a list of G id lists."""
+    n = int(n)
+    if n < 0 or (masks is None) == (ids is None):
+        raise BsrError(-1, "pack_allow_masks takes n >= 0 and exactly one of masks / ids")
+    if masks is not None:
+        bits = np.asarray(masks)
+        if bits.dtype != np.bool_ or bits.ndim != 2 or bits.shape[1] != n:
+            raise BsrError(-1, f"masks must be a bool array of shape (G, {n})")
+        rows = [pack_allow_mask(n, mask=b) for b in bits]
+    else:
+        rows = [pack_allow_mask(n, ids=i) for i in ids]
+    out = np.zeros((len(rows), (n + 63) // 64), np.uint64)
+    for g, r in enumerate(rows):
+        out[g] = r
+    return out
 
 
 def _mask_mode(mode) -> int:
@@ -481,6 +503,67 @@ class Index:
         nw = int(allow_words.numel()) if hasattr(allow_words, "numel") else int(allow_words.size)
         _check(lib().bsr_local_top_k_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), nw,
                                             _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_count)))
+
+    def _allow_group_words(self, allow_masks):
+        """(buffer, masks, words per mask) of a grouped search's allow masks: a bool array [G][n]
+        is packed here; packed uint64 words [G][words] (numpy, or a torch tensor, host or device)
+        pass through."""
+        if hasattr(allow_masks, "data_ptr"):
+            if allow_masks.element_size() != 8 or not allow_masks.is_contiguous() or allow_masks.dim() != 2:
+                raise BsrError(-1, "a tensor of allow masks holds packed 64-bit words [G][words], contiguous")
+            return allow_masks, int(allow_masks.shape[0]), int(allow_masks.shape[1])
+        w = np.asarray(allow_masks)
+        if w.dtype != np.uint64:
+            w = pack_allow_masks(self.get_count(), masks=w)
+        if w.ndim != 2:
+            raise BsrError(-1, "packed allow masks have shape [G][words]")
+        w = np.ascontiguousarray(w)
+        return w, int(w.shape[0]), int(w.shape[1])
+
+    def local_top_k_grouped(self, queries, k: int, allow_masks, query_mask, mask_mode="auto"):
+        """Batched search with one allow mask per group of queries (bsr_local_top_k_masked_groups)
+        -> (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32).  allow_masks: a bool array [G][n], packed
+        uint64 words [G][ceil(n / 64)] (pack_allow_masks), or a torch tensor of packed words;
+        query_mask [Q]: the mask of every query (integers < G, or a 32-bit torch tensor);
+        mask_mode applies per mask group."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.shape[1] != self.dim:
+            raise BsrError(-6, f"query length {q.shape[1]} != dim {self.dim}")
+        nq = q.shape[0]
+        w, n_masks, nw = self._allow_group_words(allow_masks)
+        if hasattr(query_mask, "data_ptr"):
+            if query_mask.element_size() != 4 or not query_mask.is_contiguous():
+                raise BsrError(-1, "a tensor query_mask holds 32-bit mask ids, contiguous")
+            qm, n_qm = query_mask, int(query_mask.numel())
+        else:
+            qm = np.asarray(query_mask)
+            if qm.size and (not np.issubdtype(qm.dtype, np.integer) or int(qm.min()) < 0 or int(qm.max()) > 0xFFFFFFFF):
+                raise BsrError(-1, "query_mask holds mask ids: integers in [0, G)")
+            qm = np.ascontiguousarray(qm.reshape(-1), np.uint32)
+            n_qm = int(qm.size)
+        if n_qm != nq:
+            raise BsrError(-1, f"query_mask has {n_qm} entries for {nq} queries")
+        oi = np.empty((nq, k), np.uint64)
+        od = np.empty((nq, k), np.float32)
+        oc = np.empty(nq, np.uint32)
+        # (an empty shard's masks have no words: a valid, non-null pointer all the same)
+        wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
+        _check(lib().bsr_local_top_k_masked_groups(self._h, _ptr(q), nq, k, wp, nw, n_masks, _ptr(qm),
+                                                   _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(oc)))
+        return oi, od, oc
+
+    def local_top_k_grouped_device(self, queries, nq: int, k: int, out_idx, out_dist, out_count, allow_words,
+                                   query_mask, mask_mode="auto"):
+        """Zero-copy variant of local_top_k_grouped (torch tensors, numpy arrays or raw pointers):
+        allow_words the packed masks [G][ceil(n / 64)] uint64, query_mask [nq] 32-bit mask ids."""
+        shape = tuple(allow_words.shape)
+        if len(shape) != 2:
+            raise BsrError(-1, "packed allow masks have shape [G][words]")
+        _check(lib().bsr_local_top_k_masked_groups(self._h, _ptr(queries), nq, k, _ptr(allow_words), int(shape[1]),
+                                                   int(shape[0]), _ptr(query_mask), _mask_mode(mask_mode),
+                                                   _ptr(out_idx), _ptr(out_dist), _ptr(out_count)))
 
     def last_stats(self) -> SearchStats:
         s = SearchStats()

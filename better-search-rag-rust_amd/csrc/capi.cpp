@@ -30,6 +30,10 @@ int bsr_local_top_k_impl(bsr_index* ix, const float* queries, uint32_t nq, uint3
 int bsr_local_top_k_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
                                 uint64_t allow_words, uint32_t mode, uint64_t* out_idx, float* out_dist,
                                 uint32_t* out_count);
+int bsr_local_top_k_masked_groups_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k,
+                                       const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                       const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                       uint32_t* out_count);
 int bsr_index_collect_profile_impl(bsr_index* ix);
 int bsr_copy_out_impl(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist,
                       uint32_t* out_count);
@@ -337,6 +341,14 @@ int bsr_local_top_k_masked(bsr_index* ix, const float* queries, uint32_t n_queri
                            float* out_dist, uint32_t* out_count) {
     BSR_GUARD(bsr_local_top_k_masked_impl(ix, queries, n_queries, k, allow, allow_words, mode, out_idx, out_dist,
                                           out_count));
+}
+
+int bsr_local_top_k_masked_groups(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                                  const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                  const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                  uint32_t* out_count) {
+    BSR_GUARD(bsr_local_top_k_masked_groups_impl(ix, queries, n_queries, k, allow, allow_words, n_masks, query_mask,
+                                                 mode, out_idx, out_dist, out_count));
 }
 
 // The device merge's limits (k_merge_lists: one wave per query, the concatenation in LDS).

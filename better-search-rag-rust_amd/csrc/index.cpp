@@ -644,8 +644,9 @@ static SampleLayout sample_layout(const bsr_index* ix, uint32_t nq, uint32_t ks)
 // keys per query, the input of a parallel search's global threshold), then the emit pass.
 // Batches of at most 16 queries use the skinny (HBM-bound, no LDS) filter kernels.
 // ks / cap (0: ks_for(k) / cap_for(k)): the masked search's lowered threshold and longer lists.
+// ks_q (optional, device [qpad]): the grouped masked search's per-query depths (ks_in their maximum).
 static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, uint64_t* smax, uint32_t ks_in = 0,
-                       uint32_t cap_in = 0) {
+                       uint32_t cap_in = 0, const uint32_t* ks_q = nullptr) {
     BSR_TRY(filter_buffers(ix, nq, qpad, k, cap_in));
     ix->smp_tiles = 0;
     const bool skinny = nq <= kSkinnyMaxQ;
@@ -689,10 +690,10 @@ static int sample_pass(bsr_index* ix, uint32_t nq, uint32_t qpad, uint32_t k, ui
             return skinny ? launch_filter_skinny_sample(g, ix->stream) : launch_filter_sample(g, ix->stream);
         }, 2));
         BSR_HIP(launch_select_tau(ix->S.as<float>(), s_ld, n_vals, nq, qpad, ix->qflags.as<uint32_t>(), ks,
-                                  ix->tau.as<float>(), ix->cnt.as<uint32_t>(), status, ix->stream, smax));
+                                  ix->tau.as<float>(), ix->cnt.as<uint32_t>(), status, ix->stream, smax, ks_q));
     } else {
         BSR_HIP(launch_select_tau(nullptr, 0, 0, nq, qpad, ix->qflags.as<uint32_t>(), ks, ix->tau.as<float>(),
-                                  ix->cnt.as<uint32_t>(), status, ix->stream, smax));
+                                  ix->cnt.as<uint32_t>(), status, ix->stream, smax, ks_q));
     }
     return BSR_OK;
 }
@@ -996,9 +997,12 @@ static int failed_queries(bsr_index* ix, uint32_t nq, uint32_t nfail, bool* reru
 // A later round (the exact scans of the failed queries) finalizes every query's keys again,
 // counted against n_rows, and reads the result back.  poll: the masked search's form -- its total
 // ends here and the host polls the stream; otherwise a blocking wait.
-static int finalize_and_read(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t n_rows, bool poll) {
+// rows_q (optional, device [nq]): per-query row counts instead of n_rows (the grouped masked search).
+static int finalize_and_read(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t n_rows, bool poll,
+                             const uint32_t* rows_q = nullptr) {
     BSR_HIP(launch_finalize(ix->keys.as<uint64_t>(), nq, k, n_rows, ix->global_offset, ix->d_idx, ix->d_dist,
-                            ix->d_cnt, ix->res[ix->cur ^ 1u].as<uint32_t>(), nullptr, ix->d_status, ix->stream));
+                            ix->d_cnt, ix->res[ix->cur ^ 1u].as<uint32_t>(), nullptr, ix->d_status, ix->stream,
+                            rows_q));
     ix->next_status_clean = true;
     if (poll) ev_end(ix, ix->ev_total);
     BSR_HIP(hipMemcpyAsync(ix->h_res, ix->res[ix->cur].p, ix->res_bytes, hipMemcpyDeviceToHost, ix->stream));
@@ -1340,6 +1344,291 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
 }
 
 // ---------------------------------------------------------------------------------------
+// Grouped masked search (bsr_local_top_k_masked_groups)
+// ---------------------------------------------------------------------------------------
+// The ids one chunk of row lists may hold: BSR_MASK_LIST_BUDGET bytes (read per search), 256 MB
+// by default.  A dense mask per tenant over a large shard would otherwise want n_masks x n ids.
+static uint64_t mask_list_budget_ids() {
+    uint64_t bytes = 256ull << 20;
+    const char* v = getenv("BSR_MASK_LIST_BUDGET");
+    if (v && v[0]) {
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v, &end, 10);
+        if (end != v) bytes = x;
+    }
+    return std::max<uint64_t>(bytes / sizeof(uint32_t), 1);
+}
+
+// The exact list scan of the queries with on_list[q] set, every one over the list of its own mask
+// (DESIGN.md §12).  The masks that have such a query (and a row) are taken in ascending order into
+// chunks whose lists fit the budget (a list longer than the budget is a chunk of its own); a
+// chunk is one scatter launch, and per width qf in {8, 4, 2, 1} one grouped scan and one merge
+// launch for as many query groups as kListPartBytes of partial lists hold.  A mask's queries form
+// full groups of kScanQF and one narrower group of the rest, padded with the group's first id;
+// no group holds queries of two masks.  The launch count depends on the chunks and the batch size,
+// not on n_masks.  keys of queries whose mask allows no row are left as they are (kKeyNone).
+static int run_list_scan_groups(bsr_index* ix, uint32_t nq, uint32_t k, const uint64_t* allow, uint64_t words,
+                                uint32_t n_masks, const std::vector<uint8_t>& on_list) {
+    const std::vector<uint32_t>& qmask = ix->h_grp_qmask;
+    const std::vector<uint32_t>& A = ix->h_grp_out;
+    // the listed queries by mask, ascending within a mask (a counting sort)
+    std::vector<uint32_t> start(n_masks + 1, 0), order;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (on_list[q] && A[qmask[q]]) ++start[qmask[q] + 1];
+    for (uint32_t g = 0; g < n_masks; ++g) start[g + 1] += start[g];
+    order.resize(start[n_masks]);
+    {
+        std::vector<uint32_t> at(start.begin(), start.end() - 1);
+        for (uint32_t q = 0; q < nq; ++q)
+            if (on_list[q] && A[qmask[q]]) order[at[qmask[q]]++] = q;
+    }
+    if (order.empty()) return BSR_OK;
+
+    struct Launch { uint32_t qf, groups, grid; size_t scan0, ids0; };
+    struct Chunk { size_t list0; uint32_t n_lists; std::vector<Launch> launches; };
+    std::vector<Chunk> chunks;
+    std::vector<MaskListDesc>& lists = ix->h_grp_lists;
+    std::vector<ScanGroupDesc>& scans = ix->h_grp_scan;
+    std::vector<int32_t>& ids = ix->h_grp_ids;
+    lists.clear();
+    scans.clear();
+    ids.clear();
+    const uint64_t budget = mask_list_budget_ids();
+    uint64_t list_ids = 0;
+    size_t part_bytes = 0;
+    for (uint32_t g = 0; g < n_masks;) {
+        // the chunk's masks [g, g_end)
+        Chunk c{lists.size(), 0, {}};
+        uint64_t total = 0;
+        uint32_t g_end = g;
+        for (; g_end < n_masks; ++g_end) {
+            if (start[g_end] == start[g_end + 1]) continue;
+            if (c.n_lists && total + A[g_end] > budget) break;
+            lists.push_back(MaskListDesc{total, g_end, A[g_end]});
+            total += A[g_end];
+            ++c.n_lists;
+        }
+        list_ids = std::max(list_ids, total);
+        // its query groups, one width after the other
+        for (uint32_t qf = kScanQF; qf >= 1; qf /= 2) {
+            std::vector<ScanGroupDesc> sg;
+            std::vector<int32_t> gid;
+            uint32_t longest = 0;
+            for (size_t l = c.list0; l < c.list0 + c.n_lists; ++l) {
+                const MaskListDesc& d = lists[l];
+                const uint32_t q0 = start[d.mask], nqg = start[d.mask + 1] - q0, rest = nqg % kScanQF;
+                auto group = [&](uint32_t first, uint32_t cnt) {
+                    sg.push_back(ScanGroupDesc{d.off, d.n_list, cnt});
+                    for (uint32_t j = 0; j < qf; ++j) gid.push_back((int32_t)order[first + (j < cnt ? j : 0)]);
+                    longest = std::max(longest, d.n_list);
+                };
+                if (qf == kScanQF)
+                    for (uint32_t f = 0; f + kScanQF <= nqg; f += kScanQF) group(q0 + f, kScanQF);
+                // (the rest takes the narrowest width that holds it, as launch_scan_list does)
+                if (rest && rest <= qf && rest > qf / 2) group(q0 + nqg - rest, rest);
+            }
+            if (sg.empty()) continue;
+            const uint32_t grid = scan_grid_for(longest);
+            const size_t group_bytes = (size_t)grid * qf * k * sizeof(uint64_t);
+            const uint32_t per = (uint32_t)std::min<size_t>(std::max<size_t>(kListPartBytes / group_bytes, 1), 65535);
+            for (size_t g0 = 0; g0 < sg.size(); g0 += per) {
+                const uint32_t n_g = (uint32_t)std::min<size_t>(per, sg.size() - g0);
+                c.launches.push_back(Launch{qf, n_g, grid, scans.size() + g0, ids.size() + g0 * qf});
+                part_bytes = std::max(part_bytes, group_bytes * n_g);
+            }
+            scans.insert(scans.end(), sg.begin(), sg.end());
+            ids.insert(ids.end(), gid.begin(), gid.end());
+        }
+        if (c.n_lists) chunks.push_back(std::move(c));
+        g = g_end;
+    }
+
+    BSR_TRY(ix->mask_list.ensure((size_t)list_ids * sizeof(uint32_t)));
+    BSR_TRY(ix->part.ensure(part_bytes));
+    BSR_TRY(ix->grp_lists.ensure(lists.size() * sizeof(MaskListDesc)));
+    BSR_TRY(ix->grp_scan.ensure(scans.size() * sizeof(ScanGroupDesc)));
+    BSR_TRY(ix->qids.ensure(ids.size() * sizeof(int32_t)));
+    BSR_HIP(hipMemcpyAsync(ix->grp_lists.p, lists.data(), lists.size() * sizeof(MaskListDesc), hipMemcpyHostToDevice,
+                           ix->stream));
+    BSR_HIP(hipMemcpyAsync(ix->grp_scan.p, scans.data(), scans.size() * sizeof(ScanGroupDesc), hipMemcpyHostToDevice,
+                           ix->stream));
+    BSR_HIP(hipMemcpyAsync(ix->qids.p, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
+    ev_begin(ix, ix->ev_scan, 1);
+    for (const Chunk& c : chunks) {
+        // (the stream orders a chunk's scatter behind the scans of the chunk before it)
+        BSR_HIP(launch_mask_groups_scatter(allow, words, ix->n, ix->dead_bits(), ix->grp_blk.as<uint32_t>(),
+                                           ix->grp_lists.as<MaskListDesc>() + c.list0, c.n_lists,
+                                           ix->mask_list.as<uint32_t>(), ix->stream));
+        for (const Launch& l : c.launches) {
+            const ScanGroupDesc* sg = ix->grp_scan.as<ScanGroupDesc>() + l.scan0;
+            const int32_t* gid = ix->qids.as<int32_t>() + l.ids0;
+            BSR_HIP(launch_scan_list_groups(ix->rows.as<float>(), ix->ld, ix->dim, ix->mask_list.as<uint32_t>(), sg,
+                                            l.groups, l.qf, ix->na.as<float>(), ix->qf32.as<float>(), gid,
+                                            ix->nb.as<float>(), k, l.grid, ix->part.as<uint64_t>(), ix->stream));
+            BSR_HIP(launch_merge_parts_groups(ix->part.as<uint64_t>(), l.grid, gid, l.qf, sg, l.groups, k,
+                                              ix->keys.as<uint64_t>(), ix->stream));
+        }
+    }
+    ev_end(ix, ix->ev_scan);
+    return BSR_OK;
+}
+
+int bsr_index::search_device_masked_groups(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                                           uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
+                                           uint32_t mode) {
+    bsr_index* ix = this;
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (k == 0 || k > ix->cfg.max_k) return set_error(BSR_E_INVALID, "k=%u outside [1, max_k=%u]", k, ix->cfg.max_k);
+    if (n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 (bsr_local_top_k searches without a mask)");
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (allow_words != (n + 63) / 64)
+        return set_error(BSR_E_INVALID, "allow_words=%llu, the index holds %llu rows (%llu words)",
+                         (unsigned long long)allow_words, (unsigned long long)n, (unsigned long long)((n + 63) / 64));
+    if (nq && !allow) return set_error(BSR_E_INVALID, "null allow masks");
+    if (nq && !query_mask) return set_error(BSR_E_INVALID, "null query_mask");
+    BSR_HIP(hipSetDevice(ix->device));
+    stats = bsr_search_stats{};
+    stats.n_queries = nq;
+    stats.filter_op = 0;
+    stats.row_ebound = row_ebound;
+    stats.search_path = BSR_PATH_MASK_GROUPS;
+    BSR_TRY(prepare_result(nq, k));
+    if (nq == 0) return BSR_OK;
+    if (!queries) return set_error(BSR_E_INVALID, "null queries");
+
+    const uint32_t qpad = qpad_for(nq);
+    BSR_TRY(query_buffers(ix, nq, qpad, k));
+    BSR_TRY(mask_aux.ensure(((size_t)qpad + 1) * sizeof(uint32_t)));
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
+    // The masks and the mask ids on the device; the ids on the host too (it forms the query groups).
+    const uint64_t* dallow = allow;
+    if (allow_words && !is_device_ptr(allow)) {
+        const size_t bytes = (size_t)n_masks * allow_words * sizeof(uint64_t);
+        BSR_TRY(mask_dev.ensure(bytes));
+        BSR_HIP(hipMemcpyAsync(mask_dev.p, allow, bytes, hipMemcpyHostToDevice, stream));
+        dallow = mask_dev.as<uint64_t>();
+    }
+    const uint32_t* dqmask = query_mask;
+    h_grp_qmask.resize(nq);
+    if (is_device_ptr(query_mask)) {
+        BSR_HIP(hipMemcpyAsync(h_grp_qmask.data(), query_mask, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               stream));
+    } else {
+        memcpy(h_grp_qmask.data(), query_mask, (size_t)nq * sizeof(uint32_t));
+        BSR_TRY(grp_qmask.ensure((size_t)nq * sizeof(uint32_t)));
+        BSR_HIP(hipMemcpyAsync(grp_qmask.p, h_grp_qmask.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               stream));
+        dqmask = grp_qmask.as<uint32_t>();
+    }
+    // Every A_g (over allow_g & ~dead) and the check of query_mask: two launches, one copy of
+    // n_masks + 1 words, the search's one stream wait before it picks the paths.
+    const uint32_t n_blk = mask_blocks(n);
+    BSR_TRY(grp_blk.ensure((size_t)n_masks * (n_blk + 1) * sizeof(uint32_t)));
+    BSR_TRY(grp_out.ensure(((size_t)n_masks + 1) * sizeof(uint32_t)));
+    h_grp_out.resize((size_t)n_masks + 1);
+    BSR_HIP(launch_mask_groups_count(dallow, allow_words, n_masks, n, dead_bits(), dqmask, nq, grp_blk.as<uint32_t>(),
+                                     grp_out.as<uint32_t>(), stream));
+    BSR_HIP(hipMemcpyAsync(h_grp_out.data(), grp_out.p, ((size_t)n_masks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (h_grp_out[n_masks])
+        return set_error(BSR_E_INVALID, "%u entries of query_mask name no mask (n_masks = %u)", h_grp_out[n_masks],
+                         n_masks);
+
+    // The path of every mask group, from its own A_g and query count.
+    std::vector<uint32_t> nq_g(n_masks, 0), ks_g(n_masks, 0);
+    for (uint32_t q = 0; q < nq; ++q) ++nq_g[h_grp_qmask[q]];
+    uint32_t ks_max = 0, n_list_q = 0;
+    uint64_t min_a = ~0ull;
+    for (uint32_t g = 0; g < n_masks; ++g) {
+        if (!nq_g[g] || !masked_filter_path(ix, mode, h_grp_out[g], nq_g[g], k)) continue;
+        ks_g[g] = masked_ks(k, live_rows(), h_grp_out[g]);
+        ks_max = std::max(ks_max, ks_g[g]);
+        min_a = std::min<uint64_t>(min_a, h_grp_out[g]);
+    }
+    const bool any_filter = ks_max != 0;
+    const uint32_t cap_m = 128u * ks_max;  // (one emission cap for the batch)
+    std::vector<uint8_t> on_list(nq, 0);
+    h_grp_ksq.assign(qpad, 0);
+    h_grp_aq.resize(nq);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint32_t g = h_grp_qmask[q];
+        h_grp_aq[q] = h_grp_out[g];
+        h_grp_ksq[q] = ks_g[g];
+        on_list[q] = ks_g[g] == 0;
+        n_list_q += on_list[q];
+    }
+    // (the fused finalize of the rescore counts min(k, n_rows): every filter group has more than k rows)
+    if (any_filter && min_a < k) return set_error(BSR_E_STATE, "a filter group of %llu rows at k=%u", (unsigned long long)min_a, k);
+    stats.search_path |= (any_filter ? BSR_PATH_MASK_FILTER : 0u) | (n_list_q ? BSR_PATH_MASK_LIST : 0u);
+    stats.n_exact_direct = n_list_q;
+    BSR_TRY(grp_aq.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_HIP(hipMemcpyAsync(grp_aq.p, h_grp_aq.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    // (a query whose mask allows no row is never scanned: its keys stay empty)
+    BSR_HIP(hipMemsetAsync(keys.p, 0xff, (size_t)nq * k * sizeof(uint64_t), stream));
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, any_filter), stream));
+
+    if (any_filter) {
+        // The filter, once over the batch: every query's threshold at its own depth (a list-group
+        // query's at +inf: it emits nothing), the lists cut by the query's own mask, every remaining
+        // row rescored exactly and certified against tau[q] (mode B).
+        BSR_TRY(grp_ksq.ensure((size_t)qpad * sizeof(uint32_t)));
+        BSR_HIP(hipMemcpyAsync(grp_ksq.p, h_grp_ksq.data(), (size_t)qpad * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        BSR_TRY(sample_pass(ix, nq, qpad, k, nullptr, ks_max, cap_m, grp_ksq.as<uint32_t>()));
+        BSR_TRY(emit_pass(ix, nq, qpad, k, cap_m));
+        uint32_t* raw_cnt = mask_aux.as<uint32_t>();
+        uint32_t* items = raw_cnt + qpad;
+        BSR_HIP(launch_mask_cut_groups(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dallow, allow_words, dqmask,
+                                       dead_bits(), n, raw_cnt, items, stream));
+        ev_begin(ix, ev_rescore);
+        RescoreArgs rb = rescore_args(ix, nq, k);
+        rb.n_items_dev = items;
+        rb.qlist = reinterpret_cast<const uint32_t*>(qids_id.as<int32_t>());  // (identity for q < nq)
+        rescore_emitted(rb, ix, cap_m);
+        rb.fail_cnt = d_status + kStFail2;
+        rb.fail_list = fail2.as<uint32_t>();
+        rb.n_rows = min_a;  // (>= k: the count of every filter-group query is k)
+        rescore_bookkeeping(rb, ix, nq, raw_cnt);
+        BSR_HIP(launch_rescore(rb, stream));
+        ev_end(ix, ev_rescore);
+        next_status_clean = true;
+        ev_end(ix, ev_total);
+        // (with list-group queries the rows are read after their scan: the status words alone here)
+        BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, n_list_q ? kStWords * sizeof(uint32_t) : res_bytes, hipMemcpyDeviceToHost,
+                               stream));
+        BSR_HIP(stream_wait(stream));
+        BSR_TRY(check_queries(ix, nq));
+        const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+        stats.n_emitted = st[kStEmitted];
+        const uint32_t nfail = st[kStFail2];
+        if (!nfail && !n_list_q) return BSR_OK;
+        if (nfail) {
+            // Uncertified queries and queries the filter cannot serve join the list scan; the
+            // list-group queries among them (empty lists: mode B fails them) are there already.
+            h_fail.resize(nfail);
+            h_qflags.resize(nq);
+            BSR_HIP(hipMemcpyAsync(h_fail.data(), fail2.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            BSR_HIP(hipMemcpyAsync(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            BSR_HIP(hipStreamSynchronize(stream));
+            for (uint32_t q : h_fail) {
+                if (q >= nq || on_list[q]) continue;
+                on_list[q] = 1;
+                if (h_qflags[q] & kQueryNoApprox) ++stats.n_exact_direct;
+                else ++stats.n_fallback;
+            }
+            stats.search_path |= BSR_PATH_MASK_LIST;
+        }
+    }
+    BSR_TRY(run_list_scan_groups(ix, nq, k, dallow, allow_words, n_masks, on_list));
+    BSR_TRY(finalize_and_read(ix, nq, k, 0, true, grp_aq.as<uint32_t>()));
+    return check_queries(ix, nq);
+}
+
+// ---------------------------------------------------------------------------------------
 // The parallel search's global emission threshold: phase A / phase B
 // ---------------------------------------------------------------------------------------
 bool bsr_index::gtau_eligible(uint32_t nq, uint32_t k) const {
@@ -1464,6 +1753,18 @@ int bsr_local_top_k_masked_impl(bsr_index* ix, const float* queries, uint32_t nq
     if (!ix) return set_error(BSR_E_INVALID, "null index");
     if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
     BSR_TRY(ix->search_device_masked(queries, nq, k, allow, allow_words, mode));
+    BSR_TRY(copy_out(ix, nq, k, out_idx, out_dist, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+int bsr_local_top_k_masked_groups_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k,
+                                       const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                       const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                       uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    BSR_TRY(ix->search_device_masked_groups(queries, nq, k, allow, allow_words, n_masks, query_mask, mode));
     BSR_TRY(copy_out(ix, nq, k, out_idx, out_dist, out_count));
     collect_profile(ix);
     return BSR_OK;

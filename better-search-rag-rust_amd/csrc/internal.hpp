@@ -170,6 +170,23 @@ struct bsr_index {
     bsr::DevBuf mask_list;  // u32 [A]: the allowed rows, ascending
     bsr::DevBuf mask_aux;   // u32 [qpad + 1]: emitted counts before the cut; the rescore's item count
 
+    // The same with one allow mask per group of queries (bsr_local_top_k_masked_groups, DESIGN.md
+    // §12): allow [n_masks][allow_words], query_mask [nq], each host or device.
+    int search_device_masked_groups(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                                    uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
+                                    uint32_t mode);
+    bsr::DevBuf grp_qmask;  // u32 [nq]: a host query_mask's device copy
+    bsr::DevBuf grp_blk;    // u32 [n_masks][mask_blocks(n) + 1]: every mask's block offsets
+    bsr::DevBuf grp_out;    // u32 [n_masks + 1]: A_g; the query_mask entries that name no mask
+    bsr::DevBuf grp_ksq;    // u32 [qpad]: per-query threshold depth (0: the query's group takes the list)
+    bsr::DevBuf grp_aq;     // u32 [nq]: A of the query's mask (the result count's bound)
+    bsr::DevBuf grp_lists;  // MaskListDesc: the lists of every chunk
+    bsr::DevBuf grp_scan;   // ScanGroupDesc: the query groups of every grouped scan launch
+    std::vector<uint32_t> h_grp_qmask, h_grp_out, h_grp_ksq, h_grp_aq;
+    std::vector<int32_t> h_grp_ids;
+    std::vector<bsr::MaskListDesc> h_grp_lists;
+    std::vector<bsr::ScanGroupDesc> h_grp_scan;
+
     // Tombstones (bsr_index_delete): the bitset of deleted rows, allocated by the
     // first delete (ceil(n_pad / 64) words, zero beyond the deleted rows), and what is derived from it.
     bsr::DevBuf dead;

@@ -1093,16 +1093,25 @@ __global__ __launch_bounds__(256, 2) void k_scan_exact(const float* __restrict__
 // (it is also the row this lane will walk) and passes it to the loading threads through LDS,
 // so no row load waits for its id.  blockIdx.y: the query group.
 // ------------------------------------------------------------------------------------
-template <int QF, int E>
+// GRP (the grouped masked search): every blockIdx.y walks a list of its own, the
+// grp[blockIdx.y].n_list ids at list + grp[blockIdx.y].off; the grid's x extent comes from the
+// launch's longest list, and a workgroup without a tile in its list writes empty partial lists
+// (the merge reads them).
+template <int QF, int E, bool GRP = false>
 __global__ __launch_bounds__(256, 2) void k_scan_list(const float* __restrict__ rows, uint32_t ld,
                                                       uint32_t dim, const uint32_t* __restrict__ list,
                                                       uint32_t n_list, const float* __restrict__ na,
                                                       const float* __restrict__ qf32,
                                                       const int32_t* __restrict__ qids_all,
                                                       const float* __restrict__ nb, uint32_t k,
-                                                      uint64_t* __restrict__ part_all) {
+                                                      uint64_t* __restrict__ part_all,
+                                                      const ScanGroupDesc* __restrict__ grp) {
     __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
     __shared__ uint32_t s_ids[256];  // the rows of the tile being loaded
+    if constexpr (GRP) {
+        list += grp[blockIdx.y].off;
+        n_list = grp[blockIdx.y].n_list;
+    }
     float* ldq = lds + 256 * 68;
     const int t = threadIdx.x, w = t >> 6;
     const uint32_t n_tiles = (n_list + 255) / 256;
@@ -1225,14 +1234,23 @@ __global__ __launch_bounds__(256, 2) void k_scan_list(const float* __restrict__ 
 // Per scanned query: merge the per-block lists of k_scan_exact into out_keys[qid].  Four
 // waves each take a quarter of the grid's lists (loads issued 4 deep), then wave 0 merges
 // the four wave lists through LDS.
-template <int E>
+// GRP (the grouped masked search): one launch for every query group of a grouped list scan --
+// blockIdx.y's partial lists, its qf query ids and its own query count grp[blockIdx.y].nq (the
+// ids past it are padding: no output row is written for them).
+template <int E, bool GRP = false>
 __global__ __launch_bounds__(256) void k_merge_parts(const uint64_t* __restrict__ part, uint32_t grid,
                                                      const int32_t* __restrict__ qids, uint32_t qf,
                                                      uint32_t nqf, uint32_t k,
-                                                     uint64_t* __restrict__ out_keys) {
+                                                     uint64_t* __restrict__ out_keys,
+                                                     const ScanGroupDesc* __restrict__ grp) {
     __shared__ uint64_t lk[4][64 * E];
     const uint32_t j = blockIdx.x;
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    if constexpr (GRP) {
+        part += (uint64_t)blockIdx.y * grid * qf * k;
+        qids += (uint64_t)blockIdx.y * qf;
+        nqf = grp[blockIdx.y].nq;
+    }
     if (j >= nqf) return;
     WaveTopK<E> L;
     L.init();
@@ -1266,10 +1284,13 @@ __global__ __launch_bounds__(256) void k_merge_parts(const uint64_t* __restrict_
     }
 }
 
+// n_q (optional): query q's result is counted against n_q[q] rows instead of n (the grouped masked
+// search: the allowed rows of the query's own mask).
 __global__ void k_finalize(const uint64_t* __restrict__ keys, uint32_t nq, uint32_t k, uint64_t n,
                            uint64_t offset, uint64_t* __restrict__ out_idx, float* __restrict__ out_dist,
                            uint32_t* __restrict__ out_count, uint32_t* __restrict__ status,
-                           const uint32_t* __restrict__ emit_cnt, uint32_t* __restrict__ cur_status) {
+                           const uint32_t* __restrict__ emit_cnt, uint32_t* __restrict__ cur_status,
+                           const uint32_t* __restrict__ n_q) {
     const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (e < kStWords) status[e] = 0;  // the status words of the NEXT search's result buffer
     if (emit_cnt && blockIdx.x == 0 && threadIdx.x < kWave) {
@@ -1281,6 +1302,7 @@ __global__ void k_finalize(const uint64_t* __restrict__ keys, uint32_t nq, uint3
     }
     if (e >= (uint64_t)nq * k) return;
     const uint32_t q = (uint32_t)(e / k), i = (uint32_t)(e - (uint64_t)q * k);
+    if (n_q) n = n_q[q];
     const uint32_t cnt = (uint64_t)k < n ? k : (uint32_t)n;
     const uint64_t key = keys[e];
     if (i < cnt && key != kKeyNone) {
@@ -1707,7 +1729,7 @@ static void launch_list_qf(const float* rows, uint32_t ld, uint32_t dim, const u
     const uint32_t e = (k + 63) / 64;
 #define BSR_LIST(E)                                                                                 \
     hipLaunchKernelGGL((k_scan_list<QF, E>), dim3(grid, groups), dim3(256), 0, s, rows, ld, dim, list, \
-                       n_list, na, qf32, qids, nb, k, part)
+                       n_list, na, qf32, qids, nb, k, part, (const ScanGroupDesc*)nullptr)
     switch (e) {
         case 1: BSR_LIST(1); break;
         case 2: BSR_LIST(2); break;
@@ -1737,7 +1759,7 @@ hipError_t launch_merge_parts(const uint64_t* part, uint32_t grid, const int32_t
     const uint32_t e = (k + 63) / 64;
 #define BSR_MERGE(E)                                                                              \
     hipLaunchKernelGGL(k_merge_parts<E>, dim3(nqf), dim3(256), 0, s, part, grid, qids, qf, nqf, k, \
-                       out_keys)
+                       out_keys, (const ScanGroupDesc*)nullptr)
     switch (e) {
         case 1: BSR_MERGE(1); break;
         case 2: BSR_MERGE(2); break;
@@ -1750,10 +1772,64 @@ hipError_t launch_merge_parts(const uint64_t* part, uint32_t grid, const int32_t
 
 hipError_t launch_finalize(const uint64_t* keys, uint32_t nq, uint32_t k, uint64_t n, uint64_t offset,
                            uint64_t* out_idx, float* out_dist, uint32_t* out_count, uint32_t* status,
-                           const uint32_t* emit_cnt, uint32_t* cur_status, hipStream_t s) {
+                           const uint32_t* emit_cnt, uint32_t* cur_status, hipStream_t s, const uint32_t* n_q) {
     const uint64_t total = (uint64_t)nq * k;
     hipLaunchKernelGGL(k_finalize, dim3(grid_for(total, 256)), dim3(256), 0, s, keys, nq, k, n, offset,
-                       out_idx, out_dist, out_count, status, emit_cnt, cur_status);
+                       out_idx, out_dist, out_count, status, emit_cnt, cur_status, n_q);
+    return hipGetLastError();
+}
+
+// The grouped list scan and its merge: `groups` query groups of qf queries each
+// (qf one of 1, 2, 4, 8: the template width; group y's ids at qids[y * qf ..], grp[y].nq <= qf of
+// them its own, the rest padding with ids of the same mask), every group over its own list.
+template <int QF>
+static void launch_list_groups_qf(const float* rows, uint32_t ld, uint32_t dim, const uint32_t* list,
+                                  const ScanGroupDesc* grp, uint32_t groups, const float* na, const float* qf32,
+                                  const int32_t* qids, const float* nb, uint32_t k, uint32_t grid, uint64_t* part,
+                                  hipStream_t s) {
+    const uint32_t e = (k + 63) / 64;
+#define BSR_LIST(E)                                                                                       \
+    hipLaunchKernelGGL((k_scan_list<QF, E, true>), dim3(grid, groups), dim3(256), 0, s, rows, ld, dim, list, \
+                       0u, na, qf32, qids, nb, k, part, grp)
+    switch (e) {
+        case 1: BSR_LIST(1); break;
+        case 2: BSR_LIST(2); break;
+        case 3: BSR_LIST(3); break;
+        default: BSR_LIST(4); break;
+    }
+#undef BSR_LIST
+}
+
+hipError_t launch_scan_list_groups(const float* rows, uint32_t ld, uint32_t dim, const uint32_t* list,
+                                   const ScanGroupDesc* grp, uint32_t groups, uint32_t qf, const float* na,
+                                   const float* qf32, const int32_t* qids, const float* nb, uint32_t k,
+                                   uint32_t grid, uint64_t* part, hipStream_t s) {
+    if (!groups || groups > 65535 || !grid) return hipErrorInvalidValue;
+    switch (qf) {
+        case 1: launch_list_groups_qf<1>(rows, ld, dim, list, grp, groups, na, qf32, qids, nb, k, grid, part, s); break;
+        case 2: launch_list_groups_qf<2>(rows, ld, dim, list, grp, groups, na, qf32, qids, nb, k, grid, part, s); break;
+        case 4: launch_list_groups_qf<4>(rows, ld, dim, list, grp, groups, na, qf32, qids, nb, k, grid, part, s); break;
+        case 8: launch_list_groups_qf<8>(rows, ld, dim, list, grp, groups, na, qf32, qids, nb, k, grid, part, s); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_parts_groups(const uint64_t* part, uint32_t grid, const int32_t* qids, uint32_t qf,
+                                     const ScanGroupDesc* grp, uint32_t groups, uint32_t k, uint64_t* out_keys,
+                                     hipStream_t s) {
+    if (!groups || groups > 65535 || (qf != 1 && qf != 2 && qf != 4 && qf != 8)) return hipErrorInvalidValue;
+    const uint32_t e = (k + 63) / 64;
+#define BSR_MERGE(E)                                                                                        \
+    hipLaunchKernelGGL((k_merge_parts<E, true>), dim3(qf, groups), dim3(256), 0, s, part, grid, qids, qf, 0u, k, \
+                       out_keys, grp)
+    switch (e) {
+        case 1: BSR_MERGE(1); break;
+        case 2: BSR_MERGE(2); break;
+        case 3: BSR_MERGE(3); break;
+        default: BSR_MERGE(4); break;
+    }
+#undef BSR_MERGE
     return hipGetLastError();
 }
 

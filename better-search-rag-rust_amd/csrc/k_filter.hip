@@ -1579,14 +1579,18 @@ __global__ __launch_bounds__(128) void k_filter_skinny_glds(GemmArgs p) {
 // so that about ks * stride rows of the shard or more reach it.  4 waves per query.  Also
 // zeroes the query's candidate counter and (block 0) the emit status words.
 // ------------------------------------------------------------------------------------
-template <int E>  // ks <= 64 E
+// PQ (the grouped masked search; all three kernels): the depth is the query's own,
+// ks_q[q] <= ks (ks: the batch's largest, which picked the kernel's width), and a query with
+// ks_q[q] = 0 gets tau = +INFINITY (its mask group takes the list scan: it emits nothing).
+template <int E, bool PQ = false>  // ks <= 64 E
 __global__ __launch_bounds__(256) void k_select_tau(const float* __restrict__ S, uint32_t s_ld,
                                                     uint32_t n_s, uint32_t nq, uint32_t qpad,
                                                     const uint32_t* __restrict__ qflags,
                                                     uint32_t ks, float* __restrict__ tau,
                                                     uint32_t* __restrict__ cnt,
                                                     uint32_t* __restrict__ status,
-                                                    uint64_t* __restrict__ smax) {
+                                                    uint64_t* __restrict__ smax,
+                                                    const uint32_t* __restrict__ ks_q) {
     __shared__ uint64_t part[4][64 * E];
     const uint32_t q = blockIdx.x;
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
@@ -1595,10 +1599,11 @@ __global__ __launch_bounds__(256) void k_select_tau(const float* __restrict__ S,
         for (uint32_t i = t; i < 8 * kTailCounters + kGangWords; i += blockDim.x) cnt[qpad + i] = 0;
     if (q >= qpad) return;
     if (t == 0) cnt[q] = 0;
+    if constexpr (PQ) ks = ks_q[q];
     // (smax, the global threshold's input: the query's ks best sample keys, or none)
     if (smax && (q >= nq || (qflags[q] & kQueryNoApprox) || n_s < ks))
         for (uint32_t i = t; i < ks; i += blockDim.x) smax[(uint64_t)q * ks + i] = kKeyNone;
-    if (q >= nq || (qflags[q] & kQueryNoApprox)) {
+    if (q >= nq || (qflags[q] & kQueryNoApprox) || (PQ && ks == 0)) {
         if (t == 0) tau[q] = INFINITY;  // never emits: answered by the exact scan
         return;
     }
@@ -1671,11 +1676,12 @@ __global__ __launch_bounds__(256) void k_select_tau(const float* __restrict__ S,
 // whole row in registers -- its lane maxima's ks-th largest as the lower bound, then the offers
 // from the same registers (no second read, no workgroup merge, no barrier).  The selection is
 // exact either way, so tau and the ks best keys are k_select_tau's, bit for bit.
-template <int NV>
+template <int NV, bool PQ = false>
 __global__ __launch_bounds__(256) void k_select_tau_w(const float* __restrict__ S, uint32_t s_ld, uint32_t n_s,
                                                       uint32_t nq, uint32_t qpad, const uint32_t* __restrict__ qflags,
                                                       uint32_t ks, float* __restrict__ tau, uint32_t* __restrict__ cnt,
-                                                      uint32_t* __restrict__ status, uint64_t* __restrict__ smax) {
+                                                      uint32_t* __restrict__ status, uint64_t* __restrict__ smax,
+                                                      const uint32_t* __restrict__ ks_q) {
     const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int t = threadIdx.x, lane = t & 63;
     if (blockIdx.x == 0 && t == 0) { status[kStFail] = 0; status[kStEmitted] = 0; status[kStFail2] = 0; }
@@ -1683,7 +1689,8 @@ __global__ __launch_bounds__(256) void k_select_tau_w(const float* __restrict__ 
         for (uint32_t i = t; i < 8 * kTailCounters + kGangWords; i += blockDim.x) cnt[qpad + i] = 0;
     if (q >= qpad) return;
     if (lane == 0) cnt[q] = 0;
-    const bool none = q >= nq || (qflags[q] & kQueryNoApprox);
+    if constexpr (PQ) ks = ks_q[q];
+    const bool none = q >= nq || (qflags[q] & kQueryNoApprox) || (PQ && ks == 0);
     if (smax && (none || n_s < ks))
         for (uint32_t i = lane; i < ks; i += kWave) smax[(uint64_t)q * ks + i] = kKeyNone;
     if (none) {
@@ -1727,11 +1734,12 @@ __global__ __launch_bounds__(256) void k_select_tau_w(const float* __restrict__ 
 // best.  Exact, so tau and the ks best keys are k_select_tau's, bit for bit
 // (tools/microbench/seltau_ab); timed alone at one query over 9766 values, 13.8 us for one 4-wave
 // workgroup (tools/microbench/seltau_time).
-template <int NV>
+template <int NV, bool PQ = false>
 __global__ __launch_bounds__(1024) void k_select_tau_m(const float* __restrict__ S, uint32_t s_ld, uint32_t n_s,
                                                        uint32_t nq, uint32_t qpad, const uint32_t* __restrict__ qflags,
                                                        uint32_t ks, float* __restrict__ tau, uint32_t* __restrict__ cnt,
-                                                       uint32_t* __restrict__ status, uint64_t* __restrict__ smax) {
+                                                       uint32_t* __restrict__ status, uint64_t* __restrict__ smax,
+                                                       const uint32_t* __restrict__ ks_q) {
     constexpr int NW = 16;
     const uint32_t q = blockIdx.x;
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
@@ -1740,7 +1748,8 @@ __global__ __launch_bounds__(1024) void k_select_tau_m(const float* __restrict__
         for (uint32_t i = t; i < 8 * kTailCounters + kGangWords; i += blockDim.x) cnt[qpad + i] = 0;
     if (q >= qpad) return;
     if (t == 0) cnt[q] = 0;
-    const bool none = q >= nq || (qflags[q] & kQueryNoApprox);
+    if constexpr (PQ) ks = ks_q[q];
+    const bool none = q >= nq || (qflags[q] & kQueryNoApprox) || (PQ && ks == 0);
     if (smax && (none || n_s < ks))
         for (uint32_t i = t; i < ks; i += blockDim.x) smax[(uint64_t)q * ks + i] = kKeyNone;
     if (none) {
@@ -1985,10 +1994,11 @@ hipError_t launch_sample_fixup(const GemmArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_sample_fixup, dim3(a.n_q), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_select_tau(const float* S, uint32_t s_ld, uint32_t n_s, uint32_t nq, uint32_t qpad,
-                             const uint32_t* qflags, uint32_t ks, float* tau, uint32_t* cnt, uint32_t* status,
-                             hipStream_t s, uint64_t* smax) {
-    if (ks > 2 * kWave) return hipErrorInvalidValue;
+// PQ: the same kernel choice with the per-query depths ks_q.
+template <bool PQ>
+static void launch_select_tau_pq(const float* S, uint32_t s_ld, uint32_t n_s, uint32_t nq, uint32_t qpad,
+                                 const uint32_t* qflags, uint32_t ks, float* tau, uint32_t* cnt, uint32_t* status,
+                                 hipStream_t s, uint64_t* smax, const uint32_t* ks_q) {
     // (BSR_SELECT_TAU_M=0: the 4-wave kernel instead; =2 (lab): the 16-wave kernel for every batch
     // size, for A/B runs)
     static const int m_on = [] {
@@ -1996,17 +2006,24 @@ hipError_t launch_select_tau(const float* S, uint32_t s_ld, uint32_t n_s, uint32
         return v && v[0] == '0' ? 0 : v && v[0] == '2' ? 2 : 1;
     }();
     if (m_on && ks <= kWave && (qpad <= 16 || m_on == 2) && n_s > 32 * kWave && n_s <= 16 * 16 * kWave)
-        hipLaunchKernelGGL(k_select_tau_m<16>, dim3(qpad), dim3(1024), 0, s, S, s_ld, n_s, nq, qpad, qflags, ks,
-                           tau, cnt, status, smax);
+        hipLaunchKernelGGL((k_select_tau_m<16, PQ>), dim3(qpad), dim3(1024), 0, s, S, s_ld, n_s, nq, qpad, qflags, ks,
+                           tau, cnt, status, smax, ks_q);
     else if (ks <= kWave && n_s <= 32 * kWave && qpad % 4 == 0)
-        hipLaunchKernelGGL(k_select_tau_w<32>, dim3(qpad / 4), dim3(256), 0, s, S, s_ld, n_s, nq, qpad, qflags, ks,
-                           tau, cnt, status, smax);
+        hipLaunchKernelGGL((k_select_tau_w<32, PQ>), dim3(qpad / 4), dim3(256), 0, s, S, s_ld, n_s, nq, qpad, qflags,
+                           ks, tau, cnt, status, smax, ks_q);
     else if (ks > kWave)
-        hipLaunchKernelGGL(k_select_tau<2>, dim3(qpad), dim3(256), 0, s, S, s_ld, n_s, nq, qpad, qflags, ks, tau,
-                           cnt, status, smax);
+        hipLaunchKernelGGL((k_select_tau<2, PQ>), dim3(qpad), dim3(256), 0, s, S, s_ld, n_s, nq, qpad, qflags, ks, tau,
+                           cnt, status, smax, ks_q);
     else
-        hipLaunchKernelGGL(k_select_tau<1>, dim3(qpad), dim3(256), 0, s, S, s_ld, n_s, nq, qpad, qflags, ks, tau,
-                           cnt, status, smax);
+        hipLaunchKernelGGL((k_select_tau<1, PQ>), dim3(qpad), dim3(256), 0, s, S, s_ld, n_s, nq, qpad, qflags, ks, tau,
+                           cnt, status, smax, ks_q);
+}
+hipError_t launch_select_tau(const float* S, uint32_t s_ld, uint32_t n_s, uint32_t nq, uint32_t qpad,
+                             const uint32_t* qflags, uint32_t ks, float* tau, uint32_t* cnt, uint32_t* status,
+                             hipStream_t s, uint64_t* smax, const uint32_t* ks_q) {
+    if (ks > 2 * kWave || (ks_q && smax)) return hipErrorInvalidValue;
+    if (ks_q) launch_select_tau_pq<true>(S, s_ld, n_s, nq, qpad, qflags, ks, tau, cnt, status, s, smax, ks_q);
+    else launch_select_tau_pq<false>(S, s_ld, n_s, nq, qpad, qflags, ks, tau, cnt, status, s, smax, ks_q);
     return hipGetLastError();
 }
 hipError_t launch_global_tau(const uint64_t* g, uint32_t P, uint32_t qpad, uint32_t nq, uint32_t ks,

@@ -578,6 +578,111 @@ __global__ __launch_bounds__(256) void k_mask_cut(uint64_t* __restrict__ cand, u
 }
 
 // ------------------------------------------------------------------------------------
+// Grouped masked search: n_masks allow masks of `words` words each and a mask id
+// per query.  The kernels above with blockIdx.y (or the query) picking the mask, and the index's
+// tombstones taken out as the words are read (dead: nullable) -- no copy of the masks is made.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t group_word(const uint64_t* __restrict__ allow, const uint64_t* __restrict__ dead,
+                                               uint64_t w, uint64_t n) {
+    const uint64_t x = mask_word(allow, w, n);
+    return dead && x ? x & ~dead[w] : x;
+}
+
+// blockIdx.y = the mask: blk[y * stride + blockIdx.x] = the block's allowed live rows.
+__global__ __launch_bounds__(256) void k_mask_groups_count(const uint64_t* __restrict__ allow, uint64_t words,
+                                                           uint64_t n, const uint64_t* __restrict__ dead,
+                                                           uint32_t* __restrict__ blk, uint32_t stride) {
+    __shared__ uint32_t s_wave[4];
+    const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
+    uint32_t total;
+    (void)block_exclusive_256((uint32_t)__popcll(group_word(allow + blockIdx.y * words, dead, w, n)), s_wave, &total);
+    if (threadIdx.x == 0) blk[(uint64_t)blockIdx.y * stride + blockIdx.x] = total;
+}
+
+// blockIdx.x = the mask g < n_masks: k_mask_scan over its row of blk, out[g] = A_g.  The extra
+// workgroup blockIdx.x = n_masks counts the entries of query_mask that name no mask into
+// out[n_masks] (the host refuses the call before any kernel indexes a mask with one).
+__global__ __launch_bounds__(256) void k_mask_groups_scan(uint32_t* __restrict__ blk_all, uint32_t n_blk,
+                                                          uint32_t n_masks, const uint32_t* __restrict__ query_mask,
+                                                          uint32_t nq, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_wave[4];
+    uint32_t carry = 0;
+    if (blockIdx.x == n_masks) {
+        for (uint32_t base = 0; base < nq; base += 256) {
+            const uint32_t q = base + threadIdx.x;
+            uint32_t total;
+            (void)block_exclusive_256(q < nq && query_mask[q] >= n_masks ? 1u : 0u, s_wave, &total);
+            carry += total;
+        }
+        if (threadIdx.x == 0) out[n_masks] = carry;
+        return;
+    }
+    uint32_t* blk = blk_all + (uint64_t)blockIdx.x * (n_blk + 1);
+    for (uint32_t base = 0; base < n_blk; base += 256) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < n_blk ? blk[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_256(v, s_wave, &total);
+        if (i < n_blk) blk[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        blk[n_blk] = carry;
+        out[blockIdx.x] = carry;
+    }
+}
+
+// blockIdx.y = the list: the ids of mask d[y].mask, ascending, at list + d[y].off.
+__global__ __launch_bounds__(256) void k_mask_groups_scatter(const uint64_t* __restrict__ allow, uint64_t words,
+                                                             uint64_t n, const uint64_t* __restrict__ dead,
+                                                             const uint32_t* __restrict__ blk, uint32_t stride,
+                                                             const MaskListDesc* __restrict__ d,
+                                                             uint32_t* __restrict__ list) {
+    __shared__ uint32_t s_wave[4];
+    const MaskListDesc me = d[blockIdx.y];
+    const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
+    uint64_t x = group_word(allow + (uint64_t)me.mask * words, dead, w, n);
+    uint32_t total;
+    uint32_t pos = blk[(uint64_t)me.mask * stride + blockIdx.x] + block_exclusive_256((uint32_t)__popcll(x), s_wave, &total);
+    uint32_t* out = list + me.off;
+    while (x) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(x);
+        x &= x - 1;
+        if (pos < me.n_list) out[pos] = (uint32_t)(w * 64 + b);
+        ++pos;
+    }
+}
+
+// k_mask_cut with the query's own mask, allow + query_mask[q] * words, less the deleted rows.
+__global__ __launch_bounds__(256) void k_mask_cut_groups(uint64_t* __restrict__ cand, uint32_t* __restrict__ cnt,
+                                                         uint32_t cap, uint32_t nq, const uint64_t* __restrict__ allow,
+                                                         uint64_t words, const uint32_t* __restrict__ query_mask,
+                                                         const uint64_t* __restrict__ dead, uint64_t n,
+                                                         uint32_t* __restrict__ raw, uint32_t* __restrict__ items) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *items = nq;
+    if (q >= nq) return;
+    const uint32_t c = cnt[q];
+    if (lane == 0) raw[q] = c;
+    if (c > cap) return;
+    const uint64_t* mine = allow + (uint64_t)query_mask[q] * words;
+    uint64_t* keys = cand + (uint64_t)q * cap;
+    uint32_t out = 0;
+    for (uint32_t base = 0; base < c; base += kWave) {
+        const uint32_t i = base + lane;
+        const uint64_t key = i < c ? keys[i] : kKeyNone;
+        const uint32_t row = key_row(key);
+        bool keep = key != kKeyNone && row < n && ((mine[row >> 6] >> (row & 63)) & 1ull);
+        if (keep && dead) keep = !((dead[row >> 6] >> (row & 63)) & 1ull);
+        const uint64_t m = __ballot(keep);
+        if (keep) keys[out + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = key;
+        out += (uint32_t)__popcll(m);
+    }
+    if (lane == 0) cnt[q] = out;
+}
+
+// ------------------------------------------------------------------------------------
 // Tombstones: the index's bitset of deleted rows -- bit (i & 63) of word (i >> 6)
 // set = local row i is deleted; bits at positions >= n are never set.  A delete is two launches
 // around the host's read of the first one's count: the check counts the ids outside
@@ -727,6 +832,39 @@ hipError_t launch_mask_list_count(const uint64_t* allow, uint64_t n, uint32_t* b
 hipError_t launch_mask_list_scatter(const uint64_t* allow, uint64_t n, const uint32_t* blk, uint32_t n_list,
                                     uint32_t* list, hipStream_t s) {
     hipLaunchKernelGGL(k_mask_scatter, dim3(mask_blocks(n)), dim3(256), 0, s, allow, n, blk, n_list, list);
+    return hipGetLastError();
+}
+// (a grid's y extent is at most 65535: more masks or lists than that take a launch per 65535)
+constexpr uint32_t kGridYMax = 65535;
+hipError_t launch_mask_groups_count(const uint64_t* allow, uint64_t words, uint32_t n_masks, uint64_t n,
+                                    const uint64_t* dead, const uint32_t* query_mask, uint32_t nq, uint32_t* blk,
+                                    uint32_t* out, hipStream_t s) {
+    if (!n_masks || words != (n + 63) / 64) return hipErrorInvalidValue;
+    const uint32_t n_blk = mask_blocks(n), stride = n_blk + 1;
+    for (uint32_t g0 = 0; g0 < n_masks; g0 += kGridYMax) {
+        const uint32_t g = n_masks - g0 < kGridYMax ? n_masks - g0 : kGridYMax;
+        hipLaunchKernelGGL(k_mask_groups_count, dim3(n_blk, g), dim3(256), 0, s, allow + (uint64_t)g0 * words, words, n,
+                           dead, blk + (uint64_t)g0 * stride, stride);
+    }
+    hipLaunchKernelGGL(k_mask_groups_scan, dim3(n_masks + 1), dim3(256), 0, s, blk, n_blk, n_masks, query_mask, nq, out);
+    return hipGetLastError();
+}
+hipError_t launch_mask_groups_scatter(const uint64_t* allow, uint64_t words, uint64_t n, const uint64_t* dead,
+                                      const uint32_t* blk, const MaskListDesc* d, uint32_t n_lists, uint32_t* list,
+                                      hipStream_t s) {
+    const uint32_t n_blk = mask_blocks(n);
+    for (uint32_t l0 = 0; l0 < n_lists; l0 += kGridYMax) {
+        const uint32_t l = n_lists - l0 < kGridYMax ? n_lists - l0 : kGridYMax;
+        hipLaunchKernelGGL(k_mask_groups_scatter, dim3(n_blk, l), dim3(256), 0, s, allow, words, n, dead, blk,
+                           n_blk + 1, d + l0, list);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_mask_cut_groups(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
+                                  uint64_t words, const uint32_t* query_mask, const uint64_t* dead, uint64_t n,
+                                  uint32_t* raw, uint32_t* items, hipStream_t s) {
+    hipLaunchKernelGGL(k_mask_cut_groups, dim3((nq + 3) / 4), dim3(256), 0, s, cand, cnt, cap, nq, allow, words,
+                       query_mask, dead, n, raw, items);
     return hipGetLastError();
 }
 hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,

@@ -96,6 +96,28 @@ hipError_t launch_mask_list_scatter(const uint64_t* allow, uint64_t n, const uin
 hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
                            uint64_t n, uint32_t* raw, uint32_t* items, hipStream_t s);
 
+// Grouped masked search: n_masks allow masks of `words` = ceil(n / 64) words each,
+// allow[g * words ..], and query_mask[q] < n_masks naming query q's.  dead (nullable): the index's
+// bitset of deleted rows -- every kernel forms allow_g[w] & ~dead[w] as it reads.
+// The counts, two launches: blk[g * (mask_blocks(n) + 1) ..] receives mask g's exclusive block
+// prefixes; out[g] = A_g, the rows mask g allows, and out[n_masks] = the entries of
+// query_mask[0 .. nq) that name no mask (>= n_masks; no kernel indexes a mask with one).
+hipError_t launch_mask_groups_count(const uint64_t* allow, uint64_t words, uint32_t n_masks, uint64_t n,
+                                    const uint64_t* dead, const uint32_t* query_mask, uint32_t nq, uint32_t* blk,
+                                    uint32_t* out, hipStream_t s);
+// One list per entry of d[0 .. n_lists): the ids of mask d[y].mask, ascending, at list + d[y].off
+// (d[y].n_list = A of that mask).
+struct MaskListDesc { uint64_t off; uint32_t mask, n_list; };
+hipError_t launch_mask_groups_scatter(const uint64_t* allow, uint64_t words, uint64_t n, const uint64_t* dead,
+                                      const uint32_t* blk, const MaskListDesc* d, uint32_t n_lists, uint32_t* list,
+                                      hipStream_t s);
+// launch_mask_cut with query q's own mask.
+hipError_t launch_mask_cut_groups(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
+                                  uint64_t words, const uint32_t* query_mask, const uint64_t* dead, uint64_t n,
+                                  uint32_t* raw, uint32_t* items, hipStream_t s);
+// A query group of the grouped list scan (launch_scan_list_groups): its list and its own queries.
+struct ScanGroupDesc { uint64_t off; uint32_t n_list, nq; };
+
 // Tombstones.  dead: the index's bitset of deleted rows, bit (i & 63) of word
 // (i >> 6) set = local row i is deleted; no bit at a position >= n is ever set.
 // *bad += the ids outside [lo, lo + n).
@@ -195,9 +217,12 @@ constexpr uint64_t kSkinnyTopMinRows = 2u << 20;
 // words kStFail / kStEmitted / kStFail2 for the emit pass and rescores that follow.
 // smax (optional): the query's ks best sample keys [qpad][ks] (kKeyNone where there are none),
 // the input of the global threshold of a parallel search.
+// ks_q (optional, [qpad], grouped masked search): query q's own depth ks_q[q] <= ks (ks then only
+// picks the kernel's width); ks_q[q] = 0: tau[q] = +INFINITY, the query emits nothing.  No smax.
 hipError_t launch_select_tau(const float* S, uint32_t s_ld, uint32_t n_s, uint32_t nq,
                              uint32_t qpad, const uint32_t* qflags, uint32_t ks, float* tau,
-                             uint32_t* cnt, uint32_t* status, hipStream_t s, uint64_t* smax = nullptr);
+                             uint32_t* cnt, uint32_t* status, hipStream_t s, uint64_t* smax = nullptr,
+                             const uint32_t* ks_q = nullptr);
 // tau[q] = the ks-th best of the all-gathered sample keys g[P][qpad][ks] (parallel search,
 // DESIGN.md §6); INFINITY for padding / no-filter queries.
 hipError_t launch_global_tau(const uint64_t* g, uint32_t P, uint32_t qpad, uint32_t nq, uint32_t ks,
@@ -374,10 +399,25 @@ hipError_t launch_merge(const MergeArgs& a, hipStream_t s);
 // result buffer the next search will use.
 // status: the NEXT search's status words (zeroed); emit_cnt (optional): per-query emitted
 // counts, summed into cur_status[kStEmitted].
+// n_q (optional): query q's rows are counted against n_q[q] instead of n (grouped masked search).
 hipError_t launch_finalize(const uint64_t* keys, uint32_t nq, uint32_t k, uint64_t n,
                            uint64_t offset, uint64_t* out_idx, float* out_dist,
                            uint32_t* out_count, uint32_t* status, const uint32_t* emit_cnt,
-                           uint32_t* cur_status, hipStream_t s);
+                           uint32_t* cur_status, hipStream_t s, const uint32_t* n_q = nullptr);
+// The grouped masked search's list scan: launch_scan_list with a list per query
+// group -- group y (blockIdx.y) scans the grp[y].n_list ids at list + grp[y].off for the qf
+// queries qids[y * qf ..] (qf one of 1, 2, 4, 8; the first grp[y].nq are the group's own, the rest
+// padding with ids of the same mask) and writes its partial lists to part + y * grid * qf * k.
+// grid: scan_grid_for(the launch's longest list); a workgroup without a tile in its group's list
+// writes empty partial lists.  launch_merge_parts_groups merges every group's lists in one launch
+// into out_keys[id] for the group's own queries.
+hipError_t launch_scan_list_groups(const float* rows, uint32_t ld, uint32_t dim, const uint32_t* list,
+                                   const ScanGroupDesc* grp, uint32_t groups, uint32_t qf, const float* na,
+                                   const float* qf32, const int32_t* qids, const float* nb, uint32_t k,
+                                   uint32_t grid, uint64_t* part, hipStream_t s);
+hipError_t launch_merge_parts_groups(const uint64_t* part, uint32_t grid, const int32_t* qids, uint32_t qf,
+                                     const ScanGroupDesc* grp, uint32_t groups, uint32_t k, uint64_t* out_keys,
+                                     hipStream_t s);
 hipError_t launch_cosine_pair(const float* a, uint32_t la, const float* b, uint32_t lb,
                               float* out, hipStream_t s);
 

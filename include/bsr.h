@@ -119,6 +119,7 @@ typedef struct {
 #define BSR_PATH_TOP_RERUN 64u   /* ... left a query uncertified: the batch ran again, thresholded */
 #define BSR_PATH_MASK_LIST   128u /* masked search: exact top-k over the allowed-row list */
 #define BSR_PATH_MASK_FILTER 256u /* masked search: int8 filter, emitted lists cut by the mask */
+#define BSR_PATH_MASK_GROUPS 512u /* bsr_local_top_k_masked_groups ran (with MASK_LIST / MASK_FILTER bits) */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -217,6 +218,35 @@ int bsr_local_top_k(bsr_index* ix, const float* queries, uint32_t n_queries, uin
 int bsr_local_top_k_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
                            const uint64_t* allow, uint64_t allow_words, uint32_t mode,
                            uint64_t* out_idx, float* out_dist, uint32_t* out_count);
+
+/* ---- a-2, one allow mask per group of queries: a batch that mixes tenants or
+ * metadata filters in ONE call -- one filter pass over the shard and one batched list scan
+ * instead of a bsr_local_top_k_masked call per distinct mask.
+ * allow is [n_masks][allow_words] bitsets, each laid out as bsr_local_top_k_masked's
+ * (allow_words must equal ceil(n / 64), bits at positions >= n are ignored); query_mask[q] <
+ * n_masks names query q's mask.  allow and query_mask are, independently, host or device memory,
+ * detected per call (device memory produced on a non-default stream must be complete before the
+ * call, as queries).  A mask that no query names is legal.  Query q gets the reference's result
+ * over a store that holds only the rows of its mask that are not deleted, each keeping its global
+ * index: out_count[q] = min(k, A_g) entries in (distance asc, global index asc) order with the
+ * exact f32 distances, (~0, +inf) past the count; A_g = 0 is not an error.  The result is
+ * bit-identical to bsr_local_top_k_masked called once per mask with that mask's queries.
+ * BSR_E_INVALID: n_masks == 0, a null allow or query_mask (with n_queries > 0), a wrong
+ * allow_words, an unknown mode, a query_mask entry >= n_masks (checked on the device before any
+ * mask is indexed with it).  Every other status as bsr_local_top_k_masked.
+ * mode applies per mask group, with A_g and the number of queries that name the mask:
+ *   BSR_MASK_LIST    every group takes the list scan;
+ *   BSR_MASK_FILTER  a group takes the filter where bsr_local_top_k_masked could (above), the list
+ *                    scan otherwise;
+ *   BSR_MASK_AUTO    bsr_local_top_k_masked's rule per group.
+ * search_path carries BSR_PATH_MASK_GROUPS with BSR_PATH_MASK_FILTER and / or BSR_PATH_MASK_LIST;
+ * n_exact_direct counts the queries sent to the list scan by design, n_fallback the uncertified
+ * ones.  The row lists of a batch are built in chunks of at most BSR_MASK_LIST_BUDGET bytes of
+ * ids (environment, read per search; default 256 MB).  Never graph-replayed. */
+int bsr_local_top_k_masked_groups(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                                  const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                  const uint32_t* query_mask, uint32_t mode,
+                                  uint64_t* out_idx, float* out_dist, uint32_t* out_count);
 
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]

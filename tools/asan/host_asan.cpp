@@ -111,6 +111,10 @@ static void test_interval(std::mt19937_64& rng) {
     uint32_t mc = 0;
     EXPECT(bsr_local_top_k_masked(nullptr, q, 1, 2, &allow, 1, BSR_MASK_AUTO, mi, md, &mc) == BSR_E_INVALID,
            "masked search accepted a null index");
+    const uint32_t qm = 0;
+    EXPECT(bsr_local_top_k_masked_groups(nullptr, q, 1, 2, &allow, 1, 1, &qm, BSR_MASK_AUTO, mi, md, &mc) ==
+               BSR_E_INVALID,
+           "grouped masked search accepted a null index");
 }
 
 // ---- P ranks as P threads over an in-process host all-gather ---------------------------------
