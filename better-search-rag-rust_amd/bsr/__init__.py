@@ -135,6 +135,7 @@ def lib() -> ctypes.CDLL:
         "bsr_index_delete": (ctypes.c_int, [_P, _P, u64, ctypes.POINTER(u64)]),
         "bsr_index_live_count": (ctypes.c_int, [_P, ctypes.POINTER(u64)]),
         "bsr_index_deleted_mask": (ctypes.c_int, [_P, _P, u64]),
+        "bsr_index_update": (ctypes.c_int, [_P, _P, _P, u64]),
         "bsr_local_top_k": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, _P, _P]),
         "bsr_local_top_k_masked_groups": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
@@ -160,7 +161,7 @@ def lib() -> ctypes.CDLL:
     }
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
-                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups"}
+                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -406,14 +407,12 @@ class Index:
             raise BsrError(-1, "Index not found")
         return rows[0]
 
-    # ---- tombstones (bsr_index_delete, DESIGN.md §11) ----
-    def delete(self, ids) -> int:
-        """Mark rows as deleted; every search then answers over the live rows alone.  ids: GLOBAL
-        indices as the searches return them (global_offset + local row) -- an int, a sequence or
-        numpy array of integers, or a torch tensor of 64-bit integers (host or device) -- in any
-        order, duplicates allowed.  All or nothing: an id outside the shard raises BsrError(-1)
-        and no row changes.  Returns the number of rows that went live -> deleted in this call."""
-        if hasattr(ids, "data_ptr"):  # a torch tensor, passed through as a pointer
+    @staticmethod
+    def _global_ids(ids):
+        """(buffer, count) of a list of GLOBAL row ids: an int, a sequence or numpy array of integers
+        (copied to uint64), or a torch tensor of 64-bit integers, host or device (passed through as
+        a pointer).  Ids that are no non-negative integers raise BsrError(-1)."""
+        if hasattr(ids, "data_ptr"):
             if ids.is_floating_point() or ids.is_complex() or ids.element_size() != 8:
                 raise BsrError(-1, "a tensor of ids holds 64-bit integers")
             ids = ids.reshape(-1)
@@ -422,19 +421,40 @@ class Index:
             n = int(ids.numel())
             if n and ids.dtype.is_signed and bool((ids < 0).any()):
                 raise BsrError(-1, "negative row id")
-            buf = ids
-        else:
-            a = np.asarray(ids)
-            if a.size and not np.issubdtype(a.dtype, np.integer):
-                raise BsrError(-1, "ids must be integers")
-            a = a.reshape(-1)
-            if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
-                raise BsrError(-1, "negative row id")
-            buf = np.ascontiguousarray(a, np.uint64) if a.size else np.zeros(0, np.uint64)
-            n = int(buf.size)
+            return ids, n
+        a = np.asarray(ids)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise BsrError(-1, "ids must be integers")
+        a = a.reshape(-1)
+        if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
+            raise BsrError(-1, "negative row id")
+        buf = np.ascontiguousarray(a, np.uint64) if a.size else np.zeros(0, np.uint64)
+        return buf, int(buf.size)
+
+    # ---- tombstones (bsr_index_delete, DESIGN.md §11) ----
+    def delete(self, ids) -> int:
+        """Mark rows as deleted; every search then answers over the live rows alone.  ids: GLOBAL
+        indices as the searches return them (global_offset + local row) -- an int, a sequence or
+        numpy array of integers, or a torch tensor of 64-bit integers (host or device) -- in any
+        order, duplicates allowed.  All or nothing: an id outside the shard raises BsrError(-1)
+        and no row changes.  Returns the number of rows that went live -> deleted in this call."""
+        buf, n = self._global_ids(ids)
         out = ctypes.c_uint64(0)
         _check(lib().bsr_index_delete(self._h, _ptr(buf) if n else None, n, ctypes.byref(out)))
         return int(out.value)
+
+    # ---- in-place update (bsr_index_update, DESIGN.md §13) ----
+    def update(self, ids, rows) -> None:
+        """Replace stored rows, keeping their ids: row j of rows replaces the row with GLOBAL index
+        ids[j].  ids as delete takes them, but each at most once; rows as load takes them ([len(ids)]
+        [dim]: a numpy array, or a contiguous torch tensor of the index's dtype, host or device).
+        All or nothing: an id outside the shard or named twice raises BsrError(-1), a NaN / Inf
+        among the rows BsrError(-2), and nothing changes.  Tombstones stay as they are."""
+        buf, n = self._global_ids(ids)
+        rows, n_rows = self._rows(rows)  # (a row length other than dim: BsrError(-6))
+        if n_rows != n:
+            raise BsrError(-1, f"{n} ids but {n_rows} rows")
+        _check(lib().bsr_index_update(self._h, _ptr(buf) if n else None, _ptr(rows) if n else None, n))
 
     def live_count(self) -> int:
         """Rows not deleted: get_count() minus the tombstones."""

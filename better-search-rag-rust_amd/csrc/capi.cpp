@@ -25,6 +25,7 @@ int bsr_index_append_impl(bsr_index* ix, const void* rows, uint64_t n_rows);
 int bsr_index_get_many_impl(const bsr_index* ix, uint64_t offset, uint64_t count, float* out);
 int bsr_index_delete_impl(bsr_index* ix, const uint64_t* ids, uint64_t n_ids, uint64_t* out_deleted);
 int bsr_index_deleted_mask_impl(const bsr_index* ix, uint64_t* out_words, uint64_t words);
+int bsr_index_update_impl(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids);
 int bsr_local_top_k_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx,
                          float* out_dist, uint32_t* out_count);
 int bsr_local_top_k_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
@@ -329,6 +330,9 @@ int bsr_index_live_count(const bsr_index* ix, uint64_t* out) {
 }
 int bsr_index_deleted_mask(const bsr_index* ix, uint64_t* out_words, uint64_t words) {
     BSR_GUARD(bsr_index_deleted_mask_impl(ix, out_words, words));
+}
+int bsr_index_update(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids) {
+    BSR_GUARD(bsr_index_update_impl(ix, ids, rows, n_ids));
 }
 
 int bsr_local_top_k(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint64_t* out_idx,

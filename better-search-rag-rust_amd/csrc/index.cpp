@@ -505,6 +505,107 @@ int bsr_index_deleted_mask_impl(const bsr_index* ix, uint64_t* out_words, uint64
 }
 
 // ---------------------------------------------------------------------------------------
+// in-place update (bsr_index_update)
+// ---------------------------------------------------------------------------------------
+// Rows replaced by global id.  One check launch and one host read decide all or nothing before a
+// stored byte changes; then the scatter, the norms of the named rows, and the operand of the
+// touched 32-row blocks and sample groups rebuilt by the load's own device functions from
+// ascending lists (the list kernels of the masked search over the check's bitsets; their counts
+// stay on the device, the grids cover the lists' capacity).  No kernel walks the shard's rows:
+// O(n_ids ld + touched blocks 32 ld + n / 64), plus dead_zero_operand's O(n / 64 + n_dead ld) when
+// the shard has tombstones -- the requantised blocks would bring a deleted row's operand back.
+int bsr_index::update_rows(const uint64_t* ids, const void* new_rows, uint64_t n_ids) {
+    bsr_index* ix = this;
+    if (!loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (!n_ids) return BSR_OK;
+    if (!ids || !new_rows) return set_error(BSR_E_INVALID, "null %s", ids ? "rows" : "ids");
+    if (n_ids >> 32) return set_error(BSR_E_INVALID, "n_ids=%llu: at most 2^32 - 1 ids per call", (unsigned long long)n_ids);
+    BSR_HIP(hipSetDevice(device));
+    const bool bf16 = cfg.dtype == BSR_BF16;
+    const bool ids_dev = is_device_ptr(ids), rows_dev = is_device_ptr(new_rows);
+    // (device inputs may be in flight on any stream of the caller: the load / append rule)
+    if (ids_dev || rows_dev) BSR_HIP(hipDeviceSynchronize());
+    const uint64_t* dids = ids;
+    if (!ids_dev) {
+        BSR_TRY(upd_ids.ensure((size_t)n_ids * sizeof(uint64_t)));
+        BSR_HIP(hipMemcpyAsync(upd_ids.p, ids, (size_t)n_ids * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        dids = upd_ids.as<uint64_t>();
+    }
+    const void* src = new_rows;
+    if (!rows_dev) {
+        const size_t bytes = (size_t)n_ids * dim * (bf16 ? 2 : 4);
+        BSR_TRY(tmp.ensure(bytes));
+        BSR_HIP(hipMemcpyAsync(tmp.p, new_rows, bytes, hipMemcpyHostToDevice, stream));
+        src = tmp.p;
+    }
+    // every buffer is sized before the check, so that nothing can fail between the first stored
+    // byte and the last
+    const uint64_t nb = (n + kQuantBlock - 1) / kQuantBlock;                                  // 32-row blocks
+    const uint64_t ng = ((n + kSampleStride - 1) / kSampleStride + kSampleScaleRows - 1) / kSampleScaleRows;  // sample groups
+    const uint64_t w_rows = n_pad / 64, w_blk = (nb + 63) / 64, w_grp = (ng + 63) / 64;
+    const uint32_t cap_b = (uint32_t)std::min<uint64_t>(n_ids, nb), cap_g = (uint32_t)std::min<uint64_t>(n_ids, ng);
+    const uint32_t mb_b = mask_blocks(nb), mb_g = mask_blocks(ng);
+    BSR_TRY(upd_bits.ensure((size_t)(w_rows + w_blk + w_grp) * sizeof(uint64_t)));
+    BSR_TRY(upd_cnt.ensure(kUpdCounts * sizeof(uint64_t)));
+    BSR_TRY(upd_blk.ensure(((size_t)mb_b + 1 + mb_g + 1) * sizeof(uint32_t)));
+    BSR_TRY(upd_list.ensure(((size_t)cap_b + cap_g) * sizeof(uint32_t)));
+    uint64_t* touched = upd_bits.as<uint64_t>();
+    uint64_t* blocks = touched + w_rows;
+    uint64_t* groups = blocks + w_blk;
+    uint32_t* blk_b = upd_blk.as<uint32_t>();
+    uint32_t* blk_g = blk_b + mb_b + 1;
+    uint32_t* list_b = upd_list.as<uint32_t>();
+    uint32_t* list_g = list_b + cap_b;
+    BSR_HIP(hipMemsetAsync(upd_bits.p, 0, (size_t)(w_rows + w_blk + w_grp) * sizeof(uint64_t), stream));
+    BSR_HIP(hipMemsetAsync(upd_cnt.p, 0, kUpdCounts * sizeof(uint64_t), stream));
+    BSR_HIP(launch_upd_check(dids, n_ids, global_offset, n, src, dim, bf16, touched, blocks, groups,
+                             upd_cnt.as<uint64_t>(), stream));
+    uint64_t h[kUpdCounts] = {0, 0, 0, 0};
+    BSR_HIP(hipMemcpyAsync(h, upd_cnt.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (h[kUpdBadId])
+        return set_error(BSR_E_INVALID, "%llu of the ids lie outside [%llu, %llu): no row was updated",
+                         (unsigned long long)h[kUpdBadId], (unsigned long long)global_offset,
+                         (unsigned long long)(global_offset + n));
+    if (h[kUpdDupId])
+        return set_error(BSR_E_INVALID, "%llu of the ids name a row a second time: no row was updated",
+                         (unsigned long long)h[kUpdDupId]);
+    if (h[kUpdNonFinite])
+        return set_error(BSR_E_NONFINITE, "%llu NaN/Inf among the incoming values: no row was updated",
+                         (unsigned long long)h[kUpdNonFinite]);
+
+    float* slab = rows.as<float>();
+    uint32_t* fl = flags.as<uint32_t>();
+    BSR_HIP(launch_upd_scatter(dids, n_ids, global_offset, src, dim, ld, bf16, slab, stream));
+    BSR_HIP(launch_upd_row_norms(slab, dids, n_ids, global_offset, dim, ld, na.as<float>(), fl, stream));
+    BSR_HIP(launch_mask_list_count(blocks, nb, blk_b, stream));
+    BSR_HIP(launch_mask_list_scatter(blocks, nb, blk_b, cap_b, list_b, stream));
+    BSR_HIP(launch_upd_rows_to_i8(slab, n, dim, ld, fop.as<int8_t>(), ascale.as<float>(), fl + 1, list_b, blk_b + mb_b,
+                                  cap_b, stream));
+    if (h[kUpdSampleRows]) {  // (no row the fop_s sample reads: nothing of it changes)
+        BSR_HIP(launch_mask_list_count(groups, ng, blk_g, stream));
+        BSR_HIP(launch_mask_list_scatter(groups, ng, blk_g, cap_g, list_g, stream));
+        BSR_HIP(launch_upd_rows_to_i8_sample(slab, n, dim, ld, fop_s.as<int8_t>(), ascale_s.as<float>(), list_g,
+                                             blk_g + mb_g, cap_g, stream));
+    }
+    // tombstones stay as they are: the deleted rows' operand is zeroed again (as after an append)
+    if (n_dead) BSR_TRY(dead_zero_operand(ix));
+    // the flags are sticky (only a load clears them) and ea_max only grows (atomicMax)
+    uint32_t f[2] = {0, 0};
+    BSR_HIP(hipMemcpyAsync(f, flags.p, sizeof f, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    row_flags = f[0];
+    memcpy(&row_ebound, &f[1], sizeof(float));
+    approx_ok = !(f[0] & (kRowNormOvf | kRowNormRange)) && !(cfg.flags & BSR_FLAG_EXACT_ONLY);
+    return BSR_OK;
+}
+
+int bsr_index_update_impl(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    return ix->update_rows(ids, rows, n_ids);
+}
+
+// ---------------------------------------------------------------------------------------
 // search
 // ---------------------------------------------------------------------------------------
 // Exact full scan of n_ids queries whose ids are the device list `ids` (groups of kScanQF;

@@ -207,6 +207,17 @@ struct bsr_index {
     int tombstones_after_append();  // the bitset grown to the new rows, the operand zeroed again
     int ensure_live_list();         // live_list, built from ~dead when it is not there
 
+    // In-place update (bsr_index_update): rows replaced by global id, the derived
+    // state of their blocks rebuilt from lists.  A captured search graph bakes in nothing an update
+    // changes (rows, na, fop, the scales and ea_max are read through the same pointers; approx_ok is
+    // read per search, before the graph is looked up), so SearchKey has no update generation.
+    int update_rows(const uint64_t* ids, const void* new_rows, uint64_t n_ids);
+    bsr::DevBuf upd_ids;    // an update's host ids on the device
+    bsr::DevBuf upd_bits;   // u64: touched rows [n_pad / 64] | touched blocks | touched sample groups
+    bsr::DevBuf upd_cnt;    // u64 [kUpdCounts]
+    bsr::DevBuf upd_blk;    // u32: block prefixes of the blocks' and of the groups' bitset (launch_mask_list_count)
+    bsr::DevBuf upd_list;   // u32: the touched blocks, then the touched sample groups, each ascending
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

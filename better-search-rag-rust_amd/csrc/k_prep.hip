@@ -67,13 +67,13 @@ __global__ void k_widen_bf16_rows(const uint16_t* __restrict__ src, uint64_t n, 
 // touched 64 rows per wave-instruction and fetched 3.6x the slab.)  Requires ld % 64 == 0
 // (rows zero-padded to ld, kLdAlign).
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_row_norms(const float* __restrict__ rows, uint64_t n, uint32_t dim,
-                                                   uint32_t ld, float* __restrict__ na, uint32_t* flags) {
+// The body, shared with the update's k_upd_row_norms: the wave's 64 rows are slab rows row_of(0 ..
+// 63) (row_of(i) < 0: no row), lane i's magnitude goes to na[row_of(i)].
+template <class RowOf>
+__device__ __forceinline__ void row_norms_wave(const float* __restrict__ rows, uint32_t dim, uint32_t ld,
+                                               float* __restrict__ na, uint32_t* flags, float* t, RowOf row_of) {
     constexpr int kCols = 64, kPitch = kCols + 1;  // odd pitch: lane l reads bank (l + j) % 32
-    __shared__ float tile[4][64 * kPitch];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t r0 = ((uint64_t)blockIdx.x * 4 + w) * 64;
-    float* t = tile[w];
+    const int lane = threadIdx.x & 63;
     float acc = -0.0f;
     bool bad = false;
     for (uint32_t c0 = 0; c0 < dim; c0 += kCols) {
@@ -83,7 +83,8 @@ __global__ __launch_bounds__(256) void k_row_norms(const float* __restrict__ row
         for (int i = 0; i < 16; ++i) {
             const uint32_t rr = i * 4 + (lane >> 4);
             float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (r0 + rr < n) v = *reinterpret_cast<const float4*>(rows + (r0 + rr) * ld + c0 + col);
+            const int64_t r = row_of(rr);
+            if (r >= 0) v = *reinterpret_cast<const float4*>(rows + (uint64_t)r * ld + c0 + col);
             float* d = t + rr * kPitch + col;
             d[0] = v.x;
             d[1] = v.y;
@@ -99,9 +100,9 @@ __global__ __launch_bounds__(256) void k_row_norms(const float* __restrict__ row
         }
         __syncthreads();
     }
-    const uint64_t r = r0 + lane;
+    const int64_t r = row_of((uint32_t)lane);
     uint32_t f = 0;
-    if (r < n) {
+    if (r >= 0) {
         const float m = __builtin_sqrtf(acc);
         na[r] = m;
         if (bad) f |= kRowNonFinite;
@@ -110,6 +111,15 @@ __global__ __launch_bounds__(256) void k_row_norms(const float* __restrict__ row
     }
     const uint32_t any = __reduce_or_sync(~0ull, f);
     if (any && lane_id() == 0) atomicOr(flags, any);
+}
+
+__global__ __launch_bounds__(256) void k_row_norms(const float* __restrict__ rows, uint64_t n, uint32_t dim,
+                                                   uint32_t ld, float* __restrict__ na, uint32_t* flags) {
+    __shared__ float tile[4][64 * 65];
+    const int w = threadIdx.x >> 6;
+    const uint64_t r0 = ((uint64_t)blockIdx.x * 4 + w) * 64;
+    row_norms_wave(rows, dim, ld, na, flags, tile[w],
+                   [&](uint32_t i) -> int64_t { return r0 + i < n ? (int64_t)(r0 + i) : -1; });
 }
 
 // ------------------------------------------------------------------------------------
@@ -151,14 +161,14 @@ __device__ __forceinline__ int8_t quant_i8(double x, double s) {
     return (int8_t)(int)qd;
 }
 
-__global__ __launch_bounds__(256) void k_rows_to_i8(const float* __restrict__ rows, uint64_t n,
-                                                    uint32_t dim, uint32_t ld,
-                                                    int8_t* __restrict__ out,
-                                                    float* __restrict__ scales,
-                                                    uint32_t* __restrict__ ea_max) {
+// The workgroup's body for 32-row block blk, shared by the load (k_rows_to_i8: every block) and the
+// update (k_upd_rows_to_i8: the touched blocks): what either writes for a block is the same bytes.
+__device__ __forceinline__ void rows_to_i8_block(const float* __restrict__ rows, uint64_t n, uint32_t dim,
+                                                 uint32_t ld, int8_t* __restrict__ out,
+                                                 float* __restrict__ scales, uint32_t* __restrict__ ea_max,
+                                                 const uint64_t blk) {
     __shared__ double s_inv[kQuantBlock];
     __shared__ double s_wmax[4];
-    const uint64_t blk = blockIdx.x;
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
     constexpr int kRowsPerWave = kQuantBlock / 4;
     double wmax = 0.0;
@@ -217,14 +227,22 @@ __global__ __launch_bounds__(256) void k_rows_to_i8(const float* __restrict__ ro
     if (lane == 0) atomicMax(ea_max, __float_as_uint(f32_round_up(ew * (1.0 + 1e-9) + 1e-12)));
 }
 
+__global__ __launch_bounds__(256) void k_rows_to_i8(const float* __restrict__ rows, uint64_t n,
+                                                    uint32_t dim, uint32_t ld,
+                                                    int8_t* __restrict__ out,
+                                                    float* __restrict__ scales,
+                                                    uint32_t* __restrict__ ea_max) {
+    rows_to_i8_block(rows, n, dim, ld, out, scales, ea_max, blockIdx.x);
+}
+
 // The sample operand: kSampleScaleRows sampled rows (corpus rows kSampleStride apart) per
 // workgroup, one scale for all of them; rows past the corpus are zero.
-__global__ __launch_bounds__(256) void k_rows_to_i8_sample(const float* __restrict__ rows, uint64_t n,
-                                                           uint32_t dim, uint32_t ld, int8_t* __restrict__ out,
-                                                           float* __restrict__ scales) {
+// (the body for group blk, shared by k_rows_to_i8_sample and the update's k_upd_rows_to_i8_sample)
+__device__ __forceinline__ void rows_to_i8_sample_group(const float* __restrict__ rows, uint64_t n, uint32_t dim,
+                                                        uint32_t ld, int8_t* __restrict__ out,
+                                                        float* __restrict__ scales, const uint64_t blk) {
     __shared__ double s_inv[kSampleScaleRows];
     __shared__ double s_wmax[4];
-    const uint64_t blk = blockIdx.x;
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
     constexpr int kRowsPerWave = kSampleScaleRows / 4;
     double wmax = 0.0;
@@ -268,6 +286,12 @@ __global__ __launch_bounds__(256) void k_rows_to_i8_sample(const float* __restri
             *reinterpret_cast<char4*>(out + rs * ld + c0) = make_char4(qv[0], qv[1], qv[2], qv[3]);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_rows_to_i8_sample(const float* __restrict__ rows, uint64_t n,
+                                                           uint32_t dim, uint32_t ld, int8_t* __restrict__ out,
+                                                           float* __restrict__ scales) {
+    rows_to_i8_sample_group(rows, n, dim, ld, out, scales, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------
@@ -797,6 +821,200 @@ __global__ __launch_bounds__(256) void k_dead_andnot(const uint64_t* __restrict_
                                                      uint64_t* __restrict__ out) {
     for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < words; w += (uint64_t)gridDim.x * blockDim.x)
         out[w] = (allow ? allow[w] : ~0ull) & ~dead[w];
+}
+
+// ------------------------------------------------------------------------------------
+// In-place update (bsr_index_update): rows of the loaded shard replaced by id.  The
+// check touches no stored byte; the scatter, the norms of the listed rows and the requantisation
+// of the touched blocks and sample groups (from lists, ascending) follow only when it counted
+// nothing.  Work: O(n_ids ld + touched blocks 32 ld + n / 64), no pass over the shard's rows.
+// ------------------------------------------------------------------------------------
+// The check, one launch.  The ids: cnt[kUpdBadId] += those outside [lo, lo + n); the bit of every
+// other in `touched` (atomicOr; zeroed by the caller), cnt[kUpdDupId] += those that find it set;
+// the first id of a 32-row block -- it finds the block's half of the word clear -- sets the
+// block's bit in `blocks`; a row the fop_s sample reads (local index a multiple of kSampleStride)
+// sets its group's bit in `groups` and counts in cnt[kUpdSampleRows].  The values: cnt[kUpdNonFinite]
+// += the NaN / Inf among the n_vals incoming values (bf16: after widening, i.e. the same exponent
+// test on the upper half), read 16 bytes at a time when vec (the base is 16-byte aligned).
+template <bool BF16>
+__global__ __launch_bounds__(256) void k_upd_check(const uint64_t* __restrict__ ids, uint64_t n_ids, uint64_t lo,
+                                                   uint64_t n, const void* __restrict__ src, uint64_t n_vals, bool vec,
+                                                   uint64_t* __restrict__ touched, uint64_t* __restrict__ blocks,
+                                                   uint64_t* __restrict__ groups, unsigned long long* __restrict__ cnt) {
+    static_assert(kSampleStride == kQuantBlock && kQuantBlock == 32, "a block is half a word of the bitset");
+    const uint64_t tid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, nthr = (uint64_t)gridDim.x * blockDim.x;
+    auto plus = [](uint32_t x, uint32_t y) { return x + y; };
+    auto orbit = [](uint64_t* words, uint64_t i) {
+        return (uint64_t)atomicOr(reinterpret_cast<unsigned long long*>(words + (i >> 6)), 1ull << (i & 63));
+    };
+    uint32_t bad = 0, dup = 0, smp = 0, nonf = 0;
+    for (uint64_t i = tid; i < n_ids; i += nthr) {
+        const uint64_t id = ids[i];
+        if (id < lo || id - lo >= n) { ++bad; continue; }
+        const uint64_t r = id - lo;
+        const uint64_t old = orbit(touched, r);
+        if ((old >> (r & 63)) & 1ull) { ++dup; continue; }
+        if (!(uint32_t)(old >> (r & 32))) (void)orbit(blocks, r / kQuantBlock);
+        if (r % kSampleStride == 0) {
+            ++smp;
+            (void)orbit(groups, r / (kSampleStride * (uint64_t)kSampleScaleRows));
+        }
+    }
+    constexpr uint32_t kPer16 = BF16 ? 8 : 4;
+    auto word_bad = [](uint32_t w) -> uint32_t {
+        if (BF16) return ((w & 0x7f80u) == 0x7f80u ? 1u : 0u) + ((w & 0x7f800000u) == 0x7f800000u ? 1u : 0u);
+        return (w & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+    };
+    const uint64_t n16 = vec ? n_vals / kPer16 : 0;
+    const uint4* s16 = static_cast<const uint4*>(src);
+    for (uint64_t u = tid; u < n16; u += nthr) {
+        const uint4 v = s16[u];
+        nonf += word_bad(v.x) + word_bad(v.y) + word_bad(v.z) + word_bad(v.w);
+    }
+    for (uint64_t e = n16 * kPer16 + tid; e < n_vals; e += nthr) {
+        if (BF16) nonf += (static_cast<const uint16_t*>(src)[e] & 0x7f80u) == 0x7f80u ? 1u : 0u;
+        else nonf += (static_cast<const uint32_t*>(src)[e] & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+    }
+    bad = wave_reduce_u32(bad, plus);
+    dup = wave_reduce_u32(dup, plus);
+    smp = wave_reduce_u32(smp, plus);
+    nonf = wave_reduce_u32(nonf, plus);
+    if ((threadIdx.x & 63) == 0) {
+        if (bad) atomicAdd(cnt + kUpdBadId, (unsigned long long)bad);
+        if (dup) atomicAdd(cnt + kUpdDupId, (unsigned long long)dup);
+        if (nonf) atomicAdd(cnt + kUpdNonFinite, (unsigned long long)nonf);
+        if (smp) atomicAdd(cnt + kUpdSampleRows, (unsigned long long)smp);
+    }
+}
+
+// The scatter: one wave per incoming row j -> slab row ids[j] - lo, 16-byte stores along the whole
+// padded row (zeros past dim).  f32: 4 columns per lane and step; bf16: 8, widened exactly
+// (bits << 16, as k_widen_bf16_rows).  vec: the incoming rows are 16-byte aligned (the base is,
+// and dim is a multiple of the columns of one 16-byte load) and are read 16 bytes at a time.
+// The check found every id in range and none twice: no two waves write one row.
+template <bool BF16>
+__global__ __launch_bounds__(256) void k_upd_scatter(const uint64_t* __restrict__ ids, uint64_t n_ids, uint64_t lo,
+                                                     const void* __restrict__ src, uint32_t dim, uint32_t ld, bool vec,
+                                                     float* __restrict__ rows) {
+    const int lane = threadIdx.x & 63;
+    for (uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < n_ids; j += (uint64_t)gridDim.x * 4) {
+        float* dst = rows + (ids[j] - lo) * ld;
+        if (BF16) {
+            const uint16_t* a = static_cast<const uint16_t*>(src) + j * dim;
+            for (uint32_t c0 = lane * 8; c0 < ld; c0 += 8 * kWave) {
+                uint16_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (vec && c0 < dim) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(a + c0);
+                    h[0] = (uint16_t)v.x; h[1] = (uint16_t)(v.x >> 16); h[2] = (uint16_t)v.y; h[3] = (uint16_t)(v.y >> 16);
+                    h[4] = (uint16_t)v.z; h[5] = (uint16_t)(v.z >> 16); h[6] = (uint16_t)v.w; h[7] = (uint16_t)(v.w >> 16);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        if (c0 + i < dim) h[i] = a[c0 + i];
+                }
+                *reinterpret_cast<float4*>(dst + c0) =
+                    make_float4(bf16_to_f32(h[0]), bf16_to_f32(h[1]), bf16_to_f32(h[2]), bf16_to_f32(h[3]));
+                *reinterpret_cast<float4*>(dst + c0 + 4) =
+                    make_float4(bf16_to_f32(h[4]), bf16_to_f32(h[5]), bf16_to_f32(h[6]), bf16_to_f32(h[7]));
+            }
+        } else {
+            const float* a = static_cast<const float*>(src) + j * dim;
+            for (uint32_t c0 = lane * 4; c0 < ld; c0 += 4 * kWave) {
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (vec && c0 < dim) {
+                    v = *reinterpret_cast<const float4*>(a + c0);
+                } else {
+                    if (c0 < dim) v.x = a[c0];
+                    if (c0 + 1 < dim) v.y = a[c0 + 1];
+                    if (c0 + 2 < dim) v.z = a[c0 + 2];
+                    if (c0 + 3 < dim) v.w = a[c0 + 3];
+                }
+                *reinterpret_cast<float4*>(dst + c0) = v;
+            }
+        }
+    }
+}
+
+// k_row_norms over the listed rows: a wave owns 64 consecutive entries of ids and gathers their
+// slab rows through LDS, 16 lanes per 256-byte row segment, as k_row_norms stages its own; the
+// arithmetic and the flag rules are row_norms_wave's, the flags OR-ed into flags[0].
+__global__ __launch_bounds__(256) void k_upd_row_norms(const float* __restrict__ rows, const uint64_t* __restrict__ ids,
+                                                       uint64_t n_ids, uint64_t lo, uint32_t dim, uint32_t ld,
+                                                       float* __restrict__ na, uint32_t* flags) {
+    __shared__ float tile[4][64 * 65];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t j = ((uint64_t)blockIdx.x * 4 + w) * 64 + lane;
+    const uint64_t mine = j < n_ids ? ids[j] - lo : ~0ull;  // (the lane's slab row; ~0: none)
+    row_norms_wave(rows, dim, ld, na, flags, tile[w], [&](uint32_t i) -> int64_t { return (int64_t)shfl64(mine, (int)i); });
+}
+
+// k_rows_to_i8 / k_rows_to_i8_sample from a list: workgroup b < *count takes block / group list[b]
+// (ascending: launch_mask_list_scatter over the check's bitsets); the grid covers the list's
+// capacity and the workgroups past the device-side count leave at once.
+__global__ __launch_bounds__(256) void k_upd_rows_to_i8(const float* __restrict__ rows, uint64_t n, uint32_t dim,
+                                                        uint32_t ld, int8_t* __restrict__ out,
+                                                        float* __restrict__ scales, uint32_t* __restrict__ ea_max,
+                                                        const uint32_t* __restrict__ list,
+                                                        const uint32_t* __restrict__ count) {
+    if (blockIdx.x >= *count) return;
+    rows_to_i8_block(rows, n, dim, ld, out, scales, ea_max, list[blockIdx.x]);
+}
+__global__ __launch_bounds__(256) void k_upd_rows_to_i8_sample(const float* __restrict__ rows, uint64_t n,
+                                                               uint32_t dim, uint32_t ld, int8_t* __restrict__ out,
+                                                               float* __restrict__ scales,
+                                                               const uint32_t* __restrict__ list,
+                                                               const uint32_t* __restrict__ count) {
+    if (blockIdx.x >= *count) return;
+    rows_to_i8_sample_group(rows, n, dim, ld, out, scales, list[blockIdx.x]);
+}
+
+hipError_t launch_upd_check(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, const void* src,
+                            uint32_t dim, bool bf16, uint64_t* touched, uint64_t* blocks, uint64_t* groups,
+                            uint64_t* cnt, hipStream_t s) {
+    const uint64_t n_vals = n_ids * dim;
+    const bool vec = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+    const uint32_t grid = grid_for(std::max<uint64_t>(n_ids, n_vals / (bf16 ? 8 : 4)), 256, 2048);
+    unsigned long long* c = reinterpret_cast<unsigned long long*>(cnt);
+    if (bf16)
+        hipLaunchKernelGGL(k_upd_check<true>, dim3(grid), dim3(256), 0, s, ids, n_ids, lo, n, src, n_vals, vec, touched,
+                           blocks, groups, c);
+    else
+        hipLaunchKernelGGL(k_upd_check<false>, dim3(grid), dim3(256), 0, s, ids, n_ids, lo, n, src, n_vals, vec, touched,
+                           blocks, groups, c);
+    return hipGetLastError();
+}
+hipError_t launch_upd_scatter(const uint64_t* ids, uint64_t n_ids, uint64_t lo, const void* src, uint32_t dim,
+                              uint32_t ld, bool bf16, float* rows, hipStream_t s) {
+    if (ld % kLdAlign != 0 || dim > ld) return hipErrorInvalidValue;
+    const bool vec = (reinterpret_cast<uintptr_t>(src) & 15u) == 0 && dim % (bf16 ? 8 : 4) == 0;
+    const uint32_t grid = grid_for(n_ids, 4, 8192);
+    if (bf16)
+        hipLaunchKernelGGL(k_upd_scatter<true>, dim3(grid), dim3(256), 0, s, ids, n_ids, lo, src, dim, ld, vec, rows);
+    else
+        hipLaunchKernelGGL(k_upd_scatter<false>, dim3(grid), dim3(256), 0, s, ids, n_ids, lo, src, dim, ld, vec, rows);
+    return hipGetLastError();
+}
+hipError_t launch_upd_row_norms(const float* rows, const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint32_t dim,
+                                uint32_t ld, float* na, uint32_t* flags, hipStream_t s) {
+    hipLaunchKernelGGL(k_upd_row_norms, dim3((uint32_t)((n_ids + 255) / 256)), dim3(256), 0, s, rows, ids, n_ids, lo,
+                       dim, ld, na, flags);
+    return hipGetLastError();
+}
+hipError_t launch_upd_rows_to_i8(const float* rows, uint64_t n, uint32_t dim, uint32_t ld, int8_t* out, float* scales,
+                                 uint32_t* ea_max, const uint32_t* list, const uint32_t* count, uint32_t cap,
+                                 hipStream_t s) {
+    if (cap)
+        hipLaunchKernelGGL(k_upd_rows_to_i8, dim3(cap), dim3(256), 0, s, rows, n, dim, ld, out, scales, ea_max, list,
+                           count);
+    return hipGetLastError();
+}
+hipError_t launch_upd_rows_to_i8_sample(const float* rows, uint64_t n, uint32_t dim, uint32_t ld, int8_t* out,
+                                        float* scales, const uint32_t* list, const uint32_t* count, uint32_t cap,
+                                        hipStream_t s) {
+    if (cap)
+        hipLaunchKernelGGL(k_upd_rows_to_i8_sample, dim3(cap), dim3(256), 0, s, rows, n, dim, ld, out, scales, list,
+                           count);
+    return hipGetLastError();
 }
 
 hipError_t launch_dead_check(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, uint32_t* bad,

@@ -138,6 +138,33 @@ hipError_t launch_dead_zero_fop(const uint64_t* dead, uint64_t n, const uint32_t
 // out = allow & ~dead over the mask's ceil(n / 64) words (allow = nullptr: ~dead, the live rows).
 hipError_t launch_dead_andnot(const uint64_t* allow, const uint64_t* dead, uint64_t n, uint64_t* out, hipStream_t s);
 
+// In-place update (bsr_index_update): n_ids incoming rows src [n_ids][dim] (f32, or
+// bf16 bits) replace the slab rows ids[j] - lo.  Every kernel is driven by the ids or by a list
+// built from them: none walks the shard's rows.
+// The check writes only its own scratch: the bits of the named rows in `touched` (ceil(n / 64)
+// words), of their 32-row blocks in `blocks` and of the fop_s sample groups (kSampleScaleRows
+// sampled rows = 4,096 corpus rows) whose sampled row is named in `groups`, all zeroed by the
+// caller, and the four counts of cnt (u64, zeroed by the caller).
+enum UpdCount : uint32_t { kUpdBadId = 0, kUpdDupId = 1, kUpdNonFinite = 2, kUpdSampleRows = 3, kUpdCounts = 4 };
+hipError_t launch_upd_check(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, const void* src,
+                            uint32_t dim, bool bf16, uint64_t* touched, uint64_t* blocks, uint64_t* groups,
+                            uint64_t* cnt, hipStream_t s);
+// rows[ids[j] - lo][0 .. ld) = src[j] widened exactly, zeros past dim (the ids checked: in range, distinct).
+hipError_t launch_upd_scatter(const uint64_t* ids, uint64_t n_ids, uint64_t lo, const void* src, uint32_t dim,
+                              uint32_t ld, bool bf16, float* rows, hipStream_t s);
+// launch_row_norms over the rows ids[j] - lo alone: na[row], the flags OR-ed into flags[0].
+hipError_t launch_upd_row_norms(const float* rows, const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint32_t dim,
+                                uint32_t ld, float* na, uint32_t* flags, hipStream_t s);
+// launch_rows_to_i8 / launch_rows_to_i8_sample for the *count blocks / groups list[0 .. *count)
+// (count on the device; cap >= *count workgroups are launched).  What a block or group receives is
+// what the load's kernel writes for it: the same device function.
+hipError_t launch_upd_rows_to_i8(const float* rows, uint64_t n, uint32_t dim, uint32_t ld, int8_t* out, float* scales,
+                                 uint32_t* ea_max, const uint32_t* list, const uint32_t* count, uint32_t cap,
+                                 hipStream_t s);
+hipError_t launch_upd_rows_to_i8_sample(const float* rows, uint64_t n, uint32_t dim, uint32_t ld, int8_t* out,
+                                        float* scales, const uint32_t* list, const uint32_t* count, uint32_t cap,
+                                        hipStream_t s);
+
 // ---- MFMA candidate filter (k_filter.hip) ---------------------------------------------
 struct GemmArgs {
     const uint8_t* A;       // filter rows [n_pad][row_bytes]

@@ -186,6 +186,34 @@ int bsr_index_live_count(const bsr_index* ix, uint64_t* out);          /* n - de
  * BSR_E_STATE. */
 int bsr_index_deleted_mask(const bsr_index* ix, uint64_t* out_words, uint64_t words);
 
+/* ---- in-place update: rows of a loaded shard replaced, their ids kept.
+ * Row j of rows ([n_ids][dim] row-major: f32, or bf16 bits when cfg.dtype == BSR_BF16) replaces the
+ * stored row ids[j]; ids are GLOBAL indices as bsr_index_delete takes them.  ids and rows are,
+ * independently, host or device memory; with a device input the call synchronizes the device
+ * before reading (the load / append rule), and it synchronizes with the index's stream before
+ * returning: a one-time mutation.
+ * All or nothing, checked on the device before any stored byte changes: an id outside
+ * [global_offset, global_offset + n), or the same id twice in one call (no "last wins") ->
+ * BSR_E_INVALID; a NaN or Inf in any incoming value (a bf16 row: after widening) ->
+ * BSR_E_NONFINITE; the index then answers every search exactly as before the call.  Not loaded:
+ * BSR_E_STATE.  n_ids = 0: BSR_OK.  Null ids or rows with n_ids > 0, or n_ids >= 2^32:
+ * BSR_E_INVALID.
+ * After BSR_OK bsr_index_get_many returns the new values, bsr_index_count and the global offset
+ * are unchanged, and every search -- plain, masked, grouped, parallel -- returns the reference's
+ * result over the modified store: the magnitudes, the filter operand, its scales and the
+ * certification bound of the touched 32-row blocks are rebuilt by the load's own kernels' code.
+ * Zero rows are legal (distance 1.0).  Tombstones are untouched: an updated row that is deleted
+ * stays deleted (its new values are stored and bsr_index_get_many shows them).
+ * The norm flags are sticky: an updated row whose magnitude overflows or leaves [1e-18, 1e18]
+ * sends every later search to the exact scan, as a load of that row would, and replacing that row
+ * again does not bring the filter back (a load does).  bsr_search_stats.row_ebound only grows.
+ * Cost: O(n_ids ld + touched 32-row blocks x 32 ld + n / 64), no pass over the shard's rows; while
+ * the shard has tombstones, O(n / 64 + n_dead ld) more, as bsr_index_delete (the operand of every
+ * deleted row is zeroed again).  A captured search graph bakes in nothing an update changes and
+ * replays on; only an update that had to grow its own scratch buffers (the first of its size)
+ * makes the searches re-capture, as any allocation does. */
+int bsr_index_update(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids);
+
 /* ---- a-2: compute_local_top_k for n_queries queries (row-major [n_queries][dim] f32).
  * out_idx/out_dist are [n_queries][k]; row q holds out_count[q] = min(k, n_rows) entries
  * in (distance asc, global index asc) order.  Indices are global (offset added). ------ */

@@ -115,6 +115,8 @@ static void test_interval(std::mt19937_64& rng) {
     EXPECT(bsr_local_top_k_masked_groups(nullptr, q, 1, 2, &allow, 1, 1, &qm, BSR_MASK_AUTO, mi, md, &mc) ==
                BSR_E_INVALID,
            "grouped masked search accepted a null index");
+    // the in-place update likewise (everything past the null check needs a device)
+    EXPECT(bsr_index_update(nullptr, mi, q, 1) == BSR_E_INVALID, "update accepted a null index");
 }
 
 // ---- P ranks as P threads over an in-process host all-gather ---------------------------------
