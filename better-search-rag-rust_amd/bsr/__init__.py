@@ -61,6 +61,7 @@ BSR_PATH_MASK_GROUPS = 512  # bsr_local_top_k_masked_groups ran (with the MASK_L
 BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
 BSR_MASK_LIST = 1
 BSR_MASK_FILTER = 2
+BSR_COMPACT_SHRINK = 1  # bsr_index_compact flag: also give back the HBM the dropped rows held
 _MASK_MODES = {"auto": BSR_MASK_AUTO, "list": BSR_MASK_LIST, "filter": BSR_MASK_FILTER}
 FILTER_I8 = 0
 ROOT = 0  # src/mpi_helpers/mod.rs:8
@@ -136,7 +137,8 @@ def lib() -> ctypes.CDLL:
         "bsr_index_live_count": (ctypes.c_int, [_P, ctypes.POINTER(u64)]),
         "bsr_index_deleted_mask": (ctypes.c_int, [_P, _P, u64]),
         "bsr_index_update": (ctypes.c_int, [_P, _P, _P, u64]),
-        "bsr_local_top_k": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
+        "bsr_index_compact": (ctypes.c_int, [_P, u64, u32, _P, u64, ctypes.POINTER(u64)]),
+        "bsr_local_top_k":(ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, _P, _P]),
         "bsr_local_top_k_masked_groups": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
@@ -161,7 +163,7 @@ def lib() -> ctypes.CDLL:
     }
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
-                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update"}
+                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -455,6 +457,31 @@ class Index:
         if n_rows != n:
             raise BsrError(-1, f"{n} ids but {n_rows} rows")
         _check(lib().bsr_index_update(self._h, _ptr(buf) if n else None, _ptr(rows) if n else None, n))
+
+    # ---- compaction (bsr_index_compact) ----
+    def compact(self, global_offset=None, shrink: bool = False) -> np.ndarray:
+        """Drop the deleted rows on the device: afterwards the index is what a fresh one is after
+        load(live rows, global_offset) -- the live rows packed in their old order, no tombstones,
+        every search bit-identical to that index.  global_offset: the new global index of local row
+        0 (None keeps the current one; it is applied even when no row is deleted).  shrink: also
+        give back the HBM the dropped rows held (otherwise later appends reuse it).  Returns the
+        uint64 [live] array of old global ids: entry j is the id, before the call, of the row that
+        now has the id global_offset + j.  A global_offset that is no non-negative integer below
+        2^64 raises BsrError(-1)."""
+        if global_offset is None:
+            off = self.global_offset()
+        else:
+            if isinstance(global_offset, (bool, np.bool_)) or not isinstance(global_offset, (int, np.integer)):
+                raise BsrError(-1, "global_offset must be an integer")
+            off = int(global_offset)
+            if off < 0 or off >= 1 << 64:
+                raise BsrError(-1, "global_offset must lie in [0, 2^64)")
+        live = self.live_count()
+        out = np.empty(max(live, 1), np.uint64)
+        cnt = ctypes.c_uint64(0)
+        _check(lib().bsr_index_compact(self._h, off, BSR_COMPACT_SHRINK if shrink else 0, _ptr(out), live,
+                                       ctypes.byref(cnt)))
+        return out[:int(cnt.value)]
 
     def live_count(self) -> int:
         """Rows not deleted: get_count() minus the tombstones."""

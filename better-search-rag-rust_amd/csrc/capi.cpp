@@ -26,6 +26,8 @@ int bsr_index_get_many_impl(const bsr_index* ix, uint64_t offset, uint64_t count
 int bsr_index_delete_impl(bsr_index* ix, const uint64_t* ids, uint64_t n_ids, uint64_t* out_deleted);
 int bsr_index_deleted_mask_impl(const bsr_index* ix, uint64_t* out_words, uint64_t words);
 int bsr_index_update_impl(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids);
+int bsr_index_compact_impl(bsr_index* ix, uint64_t new_global_offset, uint32_t flags, uint64_t* out_old_ids,
+                           uint64_t out_capacity, uint64_t* out_count);
 int bsr_local_top_k_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx,
                          float* out_dist, uint32_t* out_count);
 int bsr_local_top_k_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
@@ -333,6 +335,10 @@ int bsr_index_deleted_mask(const bsr_index* ix, uint64_t* out_words, uint64_t wo
 }
 int bsr_index_update(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids) {
     BSR_GUARD(bsr_index_update_impl(ix, ids, rows, n_ids));
+}
+int bsr_index_compact(bsr_index* ix, uint64_t new_global_offset, uint32_t flags, uint64_t* out_old_ids,
+                      uint64_t out_capacity, uint64_t* out_count) {
+    BSR_GUARD(bsr_index_compact_impl(ix, new_global_offset, flags, out_old_ids, out_capacity, out_count));
 }
 
 int bsr_local_top_k(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint64_t* out_idx,

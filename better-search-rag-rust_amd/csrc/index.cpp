@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <time.h>
 
 #include <algorithm>
 
@@ -603,6 +604,176 @@ int bsr_index::update_rows(const uint64_t* ids, const void* new_rows, uint64_t n
 int bsr_index_update_impl(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids) {
     if (!ix) return set_error(BSR_E_INVALID, "null index");
     return ix->update_rows(ids, rows, n_ids);
+}
+
+// ---------------------------------------------------------------------------------------
+// compaction (bsr_index_compact)
+// ---------------------------------------------------------------------------------------
+// The rows one chunk of the in-place move stages: BSR_COMPACT_STAGE_BYTES (read per call), 256 MB
+// by default, at least kRowPad rows.
+static uint64_t compact_stage_rows(const bsr_index* ix) {
+    uint64_t bytes = 256ull << 20;
+    const char* v = getenv("BSR_COMPACT_STAGE_BYTES");
+    if (v && v[0]) {
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v, &end, 10);
+        if (end != v) bytes = x;
+    }
+    return std::max<uint64_t>(bytes / ((size_t)ix->ld * sizeof(float)), kRowPad);
+}
+static double host_ms() {
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
+}
+
+// The live rows L[0 .. live) (ascending; ensure_live_list) become rows 0 .. live - 1.  L[j] >= j, so
+// rows[j] = rows[L[j]] in one parallel launch would overwrite sources not yet read (row 0 deleted
+// alone: every destination is its neighbour's source).  The move therefore runs in chunks of
+// destinations [j0, j1), each gathered into the staging buffer and copied back, in stream order:
+// a source inside the chunk's destination range is a row j' <= L[j'] < j1 -- staged by this
+// chunk or moved by an earlier one -- and everything behind j1 is still untouched.  Rows before the
+// first deleted row stay where they are.  A shrink that saves bytes gathers straight into the new,
+// smaller slab instead (two buffers: no hazard, no staging).  What the rows imply -- magnitudes,
+// operand, scales, sample, error bound, flags -- is rebuilt by index_finish_load: the index is then
+// what a load of the live rows leaves, by construction.
+int bsr_index::compact_rows(uint64_t new_global_offset, uint32_t fl, uint64_t* out_old_ids, uint64_t out_capacity,
+                            uint64_t* out_count) {
+    bsr_index* ix = this;
+    if (!loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (fl & ~BSR_COMPACT_SHRINK) return set_error(BSR_E_INVALID, "unknown flag bits 0x%x", fl & ~BSR_COMPACT_SHRINK);
+    const uint64_t live = live_rows();
+    if (out_old_ids && out_capacity < live)
+        return set_error(BSR_E_INVALID, "out_capacity=%llu, the index holds %llu live rows: nothing was moved",
+                         (unsigned long long)out_capacity, (unsigned long long)live);
+    if (new_global_offset > UINT64_MAX - live)
+        return set_error(BSR_E_INVALID, "new_global_offset + %llu live rows overflows", (unsigned long long)live);
+    BSR_HIP(hipSetDevice(device));
+    const double t0 = host_ms();
+    const size_t row_bytes = (size_t)ld * sizeof(float);
+    const uint64_t old_pad = n_pad, old_off = global_offset;
+    const uint64_t new_pad = round_up(std::max<uint64_t>(live, 1), kRowPad);
+    const bool trim = (fl & BSR_COMPACT_SHRINK) && new_pad * row_bytes < rows.bytes;  // (a smaller slab saves bytes)
+    const bool out_dev = out_old_ids && is_device_ptr(out_old_ids);
+
+    if (!n_dead && !trim) {
+        // nothing to drop: the identity map, and the offset -- baked into every captured graph
+        // (launch_finalize's and the rescore's argument), so a change makes them stale
+        if (out_old_ids && live) {
+            if (out_dev) {
+                BSR_HIP(launch_compact_ids(nullptr, live, old_off, out_old_ids, nullptr, stream));
+                BSR_HIP(hipStreamSynchronize(stream));
+            } else {
+                for (uint64_t j = 0; j < live; ++j) out_old_ids[j] = old_off + j;
+            }
+        }
+        if (new_global_offset != old_off) {
+            global_offset = new_global_offset;
+            ++dead_gen;
+        }
+        if (out_count) *out_count = live;
+        return BSR_OK;
+    }
+
+    // The list, the id map and the first row that moves; then every buffer the move needs -- all
+    // before a stored byte changes (a failure up to here leaves the index as it was).
+    const uint32_t* list = nullptr;
+    uint64_t* dids = out_dev ? out_old_ids : nullptr;
+    uint32_t first32 = ~0u;
+    if (live) {
+        if (n_dead) {
+            BSR_TRY(ensure_live_list());
+            list = live_list.as<uint32_t>();
+        }
+        if (out_old_ids && !out_dev) {
+            BSR_TRY(tmp.ensure((size_t)live * sizeof(uint64_t)));
+            dids = tmp.as<uint64_t>();
+        }
+        BSR_TRY(cmp_first.ensure(sizeof(uint32_t)));
+        BSR_HIP(hipMemsetAsync(cmp_first.p, 0xff, sizeof(uint32_t), stream));
+        BSR_HIP(launch_compact_ids(list, live, old_off, dids, cmp_first.as<uint32_t>(), stream));
+        BSR_HIP(hipMemcpyAsync(&first32, cmp_first.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        if (out_old_ids && !out_dev)
+            BSR_HIP(hipMemcpyAsync(out_old_ids, tmp.p, (size_t)live * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    const uint64_t first = std::min<uint64_t>(first32, live);  // rows [0, first) stay put
+    uint64_t chunk = 0;
+    DevBuf small;
+    if (trim) {
+        BSR_TRY(small.ensure(new_pad * row_bytes));
+    } else if (first < live) {
+        chunk = std::min<uint64_t>(compact_stage_rows(ix), live - first);
+        BSR_TRY(cmp_stage.ensure(chunk * row_bytes));
+    }
+    const double t1 = host_ms();
+    double t2 = t1;
+
+    auto move_and_rebuild = [&]() -> int {
+        float* slab = rows.as<float>();
+        if (trim) {
+            float* dst = small.as<float>();
+            if (first) BSR_HIP(hipMemcpyAsync(dst, slab, first * row_bytes, hipMemcpyDeviceToDevice, stream));
+            if (first < live) BSR_HIP(launch_compact_gather(slab, list + first, live - first, ld, dst + first * ld, stream));
+            if (new_pad > live)
+                BSR_HIP(hipMemsetAsync(dst + live * ld, 0, (new_pad - live) * row_bytes, stream));
+            BSR_HIP(hipStreamSynchronize(stream));
+            std::swap(rows.p, small.p);
+            std::swap(rows.bytes, small.bytes);
+            small.release();  // (the old slab, before the rebuild allocates)
+        } else {
+            float* stage = cmp_stage.as<float>();
+            for (uint64_t j0 = first; j0 < live; j0 += chunk) {
+                const uint64_t cnt = std::min<uint64_t>(chunk, live - j0);
+                BSR_HIP(launch_compact_gather(slab, list + j0, cnt, ld, stage, stream));
+                BSR_HIP(hipMemcpyAsync(slab + j0 * ld, stage, cnt * row_bytes, hipMemcpyDeviceToDevice, stream));
+            }
+            // zero padded, over everything the shard held: an append that does not regrow the slab
+            // finds clean pad rows
+            if (old_pad > live)
+                BSR_HIP(hipMemsetAsync(slab + live * ld, 0, (old_pad - live) * row_bytes, stream));
+            BSR_HIP(hipStreamSynchronize(stream));
+        }
+        t2 = host_ms();
+        n = live;
+        n_pad = new_pad;
+        global_offset = new_global_offset;
+        clear_tombstones();
+        ++dead_gen;  // (the row count, the offset, the bitset: every captured graph is stale)
+        if (fl & BSR_COMPACT_SHRINK) {
+            // what index_finish_load sizes again, released where it is larger than that
+            const uint64_t n_s_pad = round_up(std::max<uint64_t>((n + kSampleStride - 1) / kSampleStride, 1), kSampleScaleRows);
+            auto drop = [](DevBuf& b, size_t need) { if (b.bytes > std::max<size_t>(need, 16)) b.release(); };
+            drop(na, n_pad * sizeof(float));
+            drop(fop, (size_t)n_pad * op_row_bytes);
+            drop(ascale, n_pad / kQuantBlock * sizeof(float));
+            drop(fop_s, (size_t)n_s_pad * op_row_bytes);
+            drop(ascale_s, (size_t)(n_s_pad / kSampleScaleRows) * sizeof(float));
+            cmp_stage.release();
+            live_list.release();
+            live_mask.release();
+        }
+        return index_finish_load(ix);
+    };
+    const int r = move_and_rebuild();
+    if (r != BSR_OK) {
+        // rows may be half moved and the derived state does not match them: empty until a load
+        loaded = false;
+        clear_tombstones();
+        return r;
+    }
+    if (out_count) *out_count = live;
+    const char* trace = getenv("BSR_COMPACT_TRACE");  // (tools/bench_compact.py: host clocks around the waits)
+    if (trace && trace[0] && trace[0] != '0')
+        fprintf(stderr, "bsr_index_compact: live=%llu first=%llu list_ms=%.3f move_ms=%.3f rebuild_ms=%.3f\n",
+                (unsigned long long)live, (unsigned long long)first, t1 - t0, t2 - t1, host_ms() - t2);
+    return BSR_OK;
+}
+
+int bsr_index_compact_impl(bsr_index* ix, uint64_t new_global_offset, uint32_t flags, uint64_t* out_old_ids,
+                           uint64_t out_capacity, uint64_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    return ix->compact_rows(new_global_offset, flags, out_old_ids, out_capacity, out_count);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -218,6 +218,14 @@ struct bsr_index {
     bsr::DevBuf upd_blk;    // u32: block prefixes of the blocks' and of the groups' bitset (launch_mask_list_count)
     bsr::DevBuf upd_list;   // u32: the touched blocks, then the touched sample groups, each ascending
 
+    // Compaction (bsr_index_compact): the deleted rows dropped, the live rows packed
+    // in place in ascending order (chunks through the bounded staging buffer), the derived state
+    // rebuilt by index_finish_load, the tombstones cleared and the global offset replaced.
+    int compact_rows(uint64_t new_global_offset, uint32_t flags, uint64_t* out_old_ids, uint64_t out_capacity,
+                     uint64_t* out_count);
+    bsr::DevBuf cmp_stage;  // f32 [chunk rows][ld]: BSR_COMPACT_STAGE_BYTES (read per call), kept
+    bsr::DevBuf cmp_first;  // u32: the first row that moves
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

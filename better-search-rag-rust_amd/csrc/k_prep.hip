@@ -968,6 +968,86 @@ __global__ __launch_bounds__(256) void k_upd_rows_to_i8_sample(const float* __re
     rows_to_i8_sample_group(rows, n, dim, ld, out, scales, list[blockIdx.x]);
 }
 
+// ------------------------------------------------------------------------------------
+// Compaction (bsr_index_compact): the live rows list[0 .. cnt) of the slab, ascending,
+// packed.  k_compact_gather copies slab row list[j] to row j of ANOTHER buffer (the staging buffer
+// of a chunk, or the smaller slab of a shrink): list[j] >= j, so a gather within the slab would
+// overwrite rows other lanes have not read yet -- the host moves chunk by chunk through the
+// staging buffer, in stream order.  LPR lanes per row (16 for rows of fewer than 64 16-byte units),
+// the row index read once per row, 16-byte loads and stores, four in flight per lane; every offset
+// is a 64-bit count of 16-byte units.  No LDS.
+// ------------------------------------------------------------------------------------
+template <int LPR>
+__global__ __launch_bounds__(256) void k_compact_gather(const uint4* __restrict__ rows,
+                                                        const uint32_t* __restrict__ list, uint64_t cnt,
+                                                        uint32_t units, uint4* __restrict__ out) {
+    const uint32_t sub = threadIdx.x % LPR;
+    const uint64_t step = (uint64_t)gridDim.x * (256 / LPR);
+    for (uint64_t j = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / LPR; j < cnt; j += step) {
+        const uint4* __restrict__ src = rows + (uint64_t)list[j] * units;
+        uint4* __restrict__ dst = out + j * units;
+        uint32_t u = sub;
+        for (; u + 3 * LPR < units; u += 4 * LPR) {
+            const uint4 v0 = src[u], v1 = src[u + LPR], v2 = src[u + 2 * LPR], v3 = src[u + 3 * LPR];
+            dst[u] = v0;
+            dst[u + LPR] = v1;
+            dst[u + 2 * LPR] = v2;
+            dst[u + 3 * LPR] = v3;
+        }
+        for (; u < units; u += LPR) dst[u] = src[u];
+    }
+}
+
+// The id map: out[j] = lo + list[j], the global index before the compaction of the row that becomes
+// local row j (out may be null; list = nullptr: the identity, no row moves), and *first = the
+// lowest j with list[j] != j (atomicMin; preset to ~0 by the caller): the rows before it stay put.
+__global__ __launch_bounds__(256) void k_compact_ids(const uint32_t* __restrict__ list, uint64_t cnt, uint64_t lo,
+                                                     uint64_t* __restrict__ out, uint32_t* __restrict__ first) {
+    uint32_t mine = ~0u;
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < cnt; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = list ? list[j] : j;
+        if (out) out[j] = lo + r;
+        if (r != j && mine == ~0u) mine = (uint32_t)j;
+    }
+    mine = wave_reduce_u32(mine, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
+    if ((threadIdx.x & 63) == 0 && mine != ~0u) atomicMin(first, mine);
+}
+
+// The gather's grid follows the device (workgroups per compute unit), not the row count.
+static uint32_t compact_grid(uint64_t groups_needed) {
+    static const uint32_t cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+            n = 256;
+        (void)hipGetLastError();
+        return (uint32_t)n;
+    }();
+    const uint64_t cap = (uint64_t)cus * 8;
+    return (uint32_t)(groups_needed < 1 ? 1 : groups_needed > cap ? cap : groups_needed);
+}
+hipError_t launch_compact_gather(const float* rows, const uint32_t* list, uint64_t cnt, uint32_t ld, float* out,
+                                 hipStream_t s) {
+    if (ld % kLdAlign != 0 || !ld) return hipErrorInvalidValue;
+    if (!cnt) return hipSuccess;
+    const uint32_t units = ld / 4;  // 16-byte units per row (a multiple of 16)
+    const uint4* src = reinterpret_cast<const uint4*>(rows);
+    uint4* dst = reinterpret_cast<uint4*>(out);
+    if (units < 64)
+        hipLaunchKernelGGL(k_compact_gather<16>, dim3(compact_grid((cnt + 15) / 16)), dim3(256), 0, s, src, list, cnt,
+                           units, dst);
+    else
+        hipLaunchKernelGGL(k_compact_gather<64>, dim3(compact_grid((cnt + 3) / 4)), dim3(256), 0, s, src, list, cnt,
+                           units, dst);
+    return hipGetLastError();
+}
+hipError_t launch_compact_ids(const uint32_t* list, uint64_t cnt, uint64_t lo, uint64_t* out, uint32_t* first,
+                              hipStream_t s) {
+    if (!cnt) return hipSuccess;
+    hipLaunchKernelGGL(k_compact_ids, dim3(grid_for(cnt, 256, 2048)), dim3(256), 0, s, list, cnt, lo, out, first);
+    return hipGetLastError();
+}
+
 hipError_t launch_upd_check(const uint64_t* ids, uint64_t n_ids, uint64_t lo, uint64_t n, const void* src,
                             uint32_t dim, bool bf16, uint64_t* touched, uint64_t* blocks, uint64_t* groups,
                             uint64_t* cnt, hipStream_t s) {

@@ -165,6 +165,17 @@ hipError_t launch_upd_rows_to_i8_sample(const float* rows, uint64_t n, uint32_t 
                                         float* scales, const uint32_t* list, const uint32_t* count, uint32_t cap,
                                         hipStream_t s);
 
+// Compaction (bsr_index_compact).  out[j][0 .. ld) = rows[list[j]][0 .. ld) for
+// j < cnt: slab rows gathered, packed, into ANOTHER buffer (out must not overlap rows: list[j] >= j
+// makes an in-slab gather a race; the host moves chunks through a staging buffer in stream order).
+// ld % kLdAlign == 0; the grid is sized by the device.
+hipError_t launch_compact_gather(const float* rows, const uint32_t* list, uint64_t cnt, uint32_t ld, float* out,
+                                 hipStream_t s);
+// out[j] = lo + list[j] for j < cnt (out nullable; list = nullptr: the identity), and *first =
+// min(*first, the lowest j with list[j] != j) -- preset *first to ~0.
+hipError_t launch_compact_ids(const uint32_t* list, uint64_t cnt, uint64_t lo, uint64_t* out, uint32_t* first,
+                              hipStream_t s);
+
 // ---- MFMA candidate filter (k_filter.hip) ---------------------------------------------
 struct GemmArgs {
     const uint8_t* A;       // filter rows [n_pad][row_bytes]

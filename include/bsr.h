@@ -169,7 +169,7 @@ int bsr_index_get_many(const bsr_index* ix, uint64_t offset, uint64_t count, flo
  * result over a store that holds only the live rows, each keeping its global index:
  * out_count[q] = min(k, live), entries past the count (~0, +inf); zero live rows is not an error.
  * bsr_index_load clears the tombstones; bsr_index_append keeps them, and the appended rows are
- * live.  There is no undelete and no compaction.  The plain search keeps its fast path (graph
+ * live.  There is no undelete; bsr_index_compact drops the deleted rows.  The plain search keeps its fast path (graph
  * replay from the second search of a shape after a delete); a parallel search takes the standard
  * path (BSR_PATH_GLOBAL_TAU clear) while any row of this rank's shard is deleted.
  *
@@ -213,6 +213,37 @@ int bsr_index_deleted_mask(const bsr_index* ix, uint64_t* out_words, uint64_t wo
  * replays on; only an update that had to grow its own scratch buffers (the first of its size)
  * makes the searches re-capture, as any allocation does. */
 int bsr_index_update(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids);
+
+/* ---- compaction: the deleted rows of a loaded shard dropped, on the device.
+ * After BSR_OK the index is what a fresh index of the same config is after bsr_index_load of the
+ * live rows at new_global_offset: the live rows packed in ascending order of their old position,
+ * their values what bsr_index_get_many returned before the call; bsr_index_count =
+ * bsr_index_live_count = the old live count; bsr_index_deleted_mask all zero; every search -- plain,
+ * masked, grouped, parallel (BSR_PATH_GLOBAL_TAU eligible again) -- and bsr_search_stats.row_ebound
+ * bit-identical to that fresh index; the sticky norm flags and the growing row_ebound of
+ * bsr_index_update reset, as a load resets them (the derived state is rebuilt by the load's kernels).
+ * out_old_ids (optional; host or device memory, out_capacity entries): out_old_ids[j] = the global
+ * index, before the call, of the row whose global index is now new_global_offset + j.  NULL:
+ * out_capacity is ignored.  *out_count (optional) = the new row count.
+ * All or nothing, checked before any stored byte changes: null index, unknown flag bits, a non-null
+ * out_old_ids with out_capacity below the live count, new_global_offset + live overflowing 64
+ * bits -> BSR_E_INVALID; not loaded -> BSR_E_STATE.  A HIP failure after the move has begun leaves
+ * the index unloaded (as a failed bsr_index_append does): load it again.
+ * new_global_offset is always applied -- a rank without tombstones whose lower neighbours shrank
+ * still rebases (ranks compact with the exclusive prefix sum of all ranks' live counts as their
+ * offsets).  No tombstones and the same offset: a no-op that writes the identity map, allocates
+ * nothing and keeps the captured search graphs; any other compaction makes them stale (the next
+ * search launches directly, the one after captures).  Zero live rows is legal: the index stays
+ * loaded with 0 rows.  The move is in place, through a staging buffer of BSR_COMPACT_STAGE_BYTES
+ * (environment, read per call; default 256 MB, at least 256 rows) that the index keeps.
+ * Without BSR_COMPACT_SHRINK every allocation keeps its size and later appends reuse it; with it
+ * the slab and the derived buffers are reallocated at the new size where that saves bytes (the old
+ * and the new slab exist together during the call) and the staging buffer is released.
+ * A one-time mutation like load, append, delete and update: it synchronizes with the index's
+ * stream.  Cost: one pass over the rows from the first deleted row on, plus the load's rebuild. */
+#define BSR_COMPACT_SHRINK 1u /* also give back the HBM the dropped rows held */
+int bsr_index_compact(bsr_index* ix, uint64_t new_global_offset, uint32_t flags, uint64_t* out_old_ids,
+                      uint64_t out_capacity, uint64_t* out_count);
 
 /* ---- a-2: compute_local_top_k for n_queries queries (row-major [n_queries][dim] f32).
  * out_idx/out_dist are [n_queries][k]; row q holds out_count[q] = min(k, n_rows) entries
