@@ -409,7 +409,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_filter(GemmArgs p) {
 // (2) only if some lane reaches tau: per 16-row block its maximum, then its rows.  Passing
 // (score, row) keys go to a private per-lane LDS ring (CAP entries per query block, entry e
 // of thread t at [e][t], count in a register): no atomics and no waits in the loop; flushed
-// to the per-query global lists at the end or when a block could overfill it.
+// to the per-query global lists at the end or when a block could overfill it.  The 768-byte gang
+// build queues level 2 instead: the passing lanes store their raw values in a per-wave LDS queue,
+// scored and appended when it is flushed (QUEUE, below).
 // SAMPLE: every tile row is one sampled corpus row; the scores (or one maximum per 32
 // sampled rows) go to S.
 // Sample tiles (GemmArgs::s_tiles): SAMPLE reads one emit tile in 32 of the
@@ -522,7 +524,9 @@ extern "C" int bsr_lab_filter_stamps(unsigned long long* out, int reset) {
 #endif
 // Two builds of the kernel ship (launch_filter picks one per launch):
 //   GANGS = true   the gang build, every NK of both passes: row-stream gangs (GANG = 2), level 2's
-//                  passing row blocks as a bit mask, an explicit vmcnt(0) in the flush path;
+//                  passing row blocks as a bit mask, an explicit vmcnt(0) in the flush path; its
+//                  768-byte emit build (the shards gangs run on) queues level 2 (QUEUE): raw records
+//                  in a per-wave LDS queue, scored at the flush -- about -2% at 10M rows;
 //   GANGS = false  the small-shard build, emit NK = 12 only: no gang code compiled, level 2's
 //                  passing row blocks as a bool array (L2), no explicit wait in the flush (!FW).
 // Both take their dynamic tail from the 8 XCD-local pools.  The variants that were measured and
@@ -542,7 +546,15 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     constexpr int BM = 128, BN = kFilterTile, NT = 512, SLOT = BM * kSliceB;
     constexpr int CAP = 10;  // candidate ring entries per (lane, query block)
     static_assert(NK % 2 == 0 && NK >= 2 && NK <= 12, "even slice counts up to 768 bytes");
-    constexpr int EM_BYTES = EMIT ? NT * 2 * CAP * 8 : 0;
+    // The 768-byte gang build queues level 2 instead (below): a per-wave LDS queue of QD raw records
+    // (128 bytes of integer accumulators at a stride of REC_B -- the flush's lane-per-record
+    // reads then spread over the LDS banks -- and a HDR_B-byte header each) and the workgroup's table of
+    // its 256 thresholds and query scales take the place of the per-lane rings.
+    constexpr bool QUEUE = GANGS && EMIT && NK == 12;
+    constexpr int QD = kEmitQueueDepth, REC_B = 144, HDR_B = 32, QW_BYTES = QD * (REC_B + HDR_B);
+    static_assert(QD >= 1 && QD <= kWave, "the flush takes one record per lane");
+    constexpr int EM_BYTES = QUEUE ? 8 * QW_BYTES + 2 * BN * 4 : EMIT ? NT * 2 * CAP * 8 : 0;
+    static_assert(S * SLOT + EM_BYTES + 16 <= 160 * 1024, "the ring, the queues and the table fit one CU's LDS");
     // SAMPLE, compact: the workgroup's maxima [tile][4][256 queries], written to S at the end
     constexpr int SB_BYTES = EMIT ? 0 : kSampleTilesPerWG * 4 * BN * 4;
     __shared__ __attribute__((aligned(1024))) uint8_t lds[S * SLOT + EM_BYTES + SB_BYTES + 16];
@@ -667,6 +679,72 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
         // atomic's return complete on this path: otherwise every join after a flush branch
         // (each level-2 append) carries a vmcnt(0) that drains the whole DMA stream
         if constexpr (FW) __builtin_amdgcn_s_waitcnt(0x0F70);
+    };
+    // QUEUE: level 2 only enqueues.  A lane whose level-1 test passes stores the 32 raw integer
+    // values of its query block (record i of the wave at qrec + i * REC_B, value 4 rb + r =
+    // acc[rb][nb][r]) and a header {physical tile, nb << 6 | lane, -, -, the tile's four block
+    // scales}; the scores and the exact per-row test happen when the queue is flushed -- when it is
+    // full, and at the end -- so a wave in level 2 holds the other seven at the next barrier for a
+    // few LDS stores instead of the row-block tests and appends.  The flush needs tau and the query
+    // scale of a record's query: the workgroup's table, of which each wave fills and reads its own
+    // 32 entries (no barrier).
+    uint8_t* const qrec = lds + S * SLOT + wu * QW_BYTES;
+    uint8_t* const qhdr = qrec + QD * REC_B;
+    float* const tab_tau = reinterpret_cast<float*>(lds + S * SLOT + 8 * QW_BYTES);
+    float* const tab_bs = tab_tau + BN;
+    uint32_t nrec = 0;  // records queued (wave-uniform)
+    if constexpr (QUEUE) {
+        if (lane < 16) {
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                tab_tau[wu * 32 + nb * 16 + lane] = tau[nb];
+                tab_bs[wu * 32 + nb * 16 + lane] = sbq[nb];
+            }
+        }
+    }
+    // The flush: lane j takes record j (QD <= 64).  It scores the record's 32 values as the product
+    // does, keeps the passing ones as a bit mask, claims their places in its query's list with one
+    // atomicAdd -- the wave's atomics in flight together: one round trip per flush -- and stores
+    // their keys, one loop step per passing row (typically one to three).  Keys, counts and
+    // overflow behaviour are flush_ring's.  The only VMEM is the atomics and the appends; the
+    // vmcnt(0) at the end is the builtin (see flush_ring).  (Measured first: the wave walking the
+    // records one at a time, 32 lanes on a record's 32 values -- ~600 cycles per record, every one
+    // of them spent by the seven other waves at the next barrier)
+    auto flush_queue = [&]() {
+        if ((uint32_t)lane < nrec) {
+            const uint8_t* hd = qhdr + lane * HDR_B;
+            const uint2 h = *reinterpret_cast<const uint2*>(hd);
+            const float4 s4 = *reinterpret_cast<const float4*>(hd + 16);
+            const uint32_t ql = wu * 32 + (h.y >> 6) * 16 + (h.y & 15u);
+            const float tq = tab_tau[ql], sq = tab_bs[ql];
+            const uint32_t row0 = h.x * BM + 4 * ((h.y >> 4) & 3u);  // value 4 rb + r: row row0 + 16 rb + r
+            const uint8_t* rr = qrec + lane * REC_B;
+            uint32_t pm = 0;
+#pragma unroll 1  // (a loop: the flush must not cost the main loop registers)
+            for (int rb = 0; rb < 8; ++rb) {
+                const i32x4v_t x = *reinterpret_cast<const i32x4v_t*>(rr + rb * 16);
+                const float scr = (rb >> 1) == 0 ? s4.x : (rb >> 1) == 1 ? s4.y : (rb >> 1) == 2 ? s4.z : s4.w;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = ((float)x[r] * scr) * sq;
+                    pm |= (v >= tq && row0 + rb * 16 + r < p.n_rows) ? 1u << (rb * 4 + r) : 0u;
+                }
+            }
+            if (pm) {
+                const uint32_t q = qt * BN + ql;
+                uint32_t gp = atomicAdd(p.cnt + q, (uint32_t)__builtin_popcount(pm));
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // (the claim is in: no wait inside the store loop)
+                for (; pm; pm &= pm - 1, ++gp) {
+                    const uint32_t i = (uint32_t)__builtin_ctz(pm);
+                    const int I = *reinterpret_cast<const int*>(rr + i * 4);
+                    const float scr = (i >> 3) == 0 ? s4.x : (i >> 3) == 1 ? s4.y : (i >> 3) == 2 ? s4.z : s4.w;
+                    const float v = ((float)I * scr) * sq;
+                    if (gp < p.cap) p.cand[(uint64_t)q * p.cap + gp] = score_key(v, row0 + (i >> 2) * 16 + (i & 3));
+                }
+            }
+        }
+        nrec = 0;
+        __builtin_amdgcn_s_waitcnt(0x0F70);
     };
 
     // LDS-DMA: wave w fills rows 16w .. 16w+15 of each slice (1 KiB per instruction); the
@@ -927,6 +1005,7 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
             fst[7] += 1;
 #endif
             int mrb[2];  // (unused lanes' values are never read)
+            bool l1p[2];  // (QUEUE) the lane's level-1 result per query block
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 int m = acc[0][nb][0];
@@ -935,7 +1014,8 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) m = (rb | r) ? max(m, acc[rb][nb][r]) : m;
                 mrb[nb] = m;
-                any |= ((float)m * (m >= 0 ? sc_hi : sc_lo)) * sbq[nb] >= tau[nb];
+                l1p[nb] = ((float)m * (m >= 0 ? sc_hi : sc_lo)) * sbq[nb] >= tau[nb];
+                any |= l1p[nb];
             }
             const bool l2 = __ballot(any) != 0;
 #ifdef BSR_FILTER_STAMPS
@@ -945,39 +1025,77 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
 #endif
             if (l2) {
                 BSR_FCNT(1);
-                // level 2: per (query block, 16-row block) its maximum against tau -- eight
-                // independent scores, then one uniform branch per passing row block -- and that
-                // block's 4 rows appended without branches (every key is written to the next
-                // ring slot, the count advances only for passing rows)
+                if constexpr (QUEUE) {
+                    // level 2, queued: per query block the passing lanes take consecutive slots of
+                    // the wave's queue (ballot + mbcnt) and store their raw values and a header:
+                    // no per-row test, no float work.  The two uniform branches: some lane passes,
+                    // the queue is full -- then flush and go on with the lanes not yet queued.
+                    const uint64_t lbit = 1ull << lane;
 #pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    if (!__ballot(((float)mrb[nb] * (mrb[nb] >= 0 ? sc_hi : sc_lo)) * sbq[nb] >= tau[nb])) continue;
-                    BSR_FCNT(2);
-                    uint32_t pm = 0;  // the lane's passing row blocks
-                    bool pass_rb[8];
+                    for (int nb = 0; nb < 2; ++nb) {
+                        uint64_t bal = __ballot(l1p[nb]);
+                        while (bal) {
+                            if (nrec == (uint32_t)QD) {
+                                flush_queue();
+                                stored = true;
+                            }
+                            const uint32_t rank =
+                                __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                            const bool mine = (bal & lbit) && rank < (uint32_t)QD - nrec;
+                            if (mine) {
+                                const uint32_t sl = nrec + rank;
 #pragma unroll
-                    for (int rb = 0; rb < 8; ++rb) {
-                        const i32x4v_t& x = acc[rb][nb];
-                        const int bm = max(max(x[0], x[1]), max(x[2], x[3]));
-                        if constexpr (L2) pass_rb[rb] = ((float)bm * sc[rb >> 1]) * sbq[nb] >= tau[nb];
-                        else pm |= (((float)bm * sc[rb >> 1]) * sbq[nb] >= tau[nb]) ? 1u << rb : 0u;
-                    }
-#pragma unroll
-                    for (int rb = 0; rb < 8; ++rb) {
-                        if (!__ballot(L2 ? pass_rb[rb] : ((pm >> rb) & 1u))) continue;
-                        BSR_FCNT(3);
-                        if (__ballot(ecnt[nb] > (uint32_t)(CAP - 4))) {  // room for 4 rows (rarely not)
-                            flush_ring(nb);
-                            stored = true;
+                                for (int rb = 0; rb < 8; ++rb)
+                                    *reinterpret_cast<i32x4v_t*>(qrec + sl * REC_B + rb * 16) = acc[rb][nb];
+                                // (the header through the accumulators' vector type: in front of a
+                                // store through HIP's uint4 / float4 hipcc put a vmcnt(0), which
+                                // drains the DMA stream on every enqueue)
+                                const i32x4v_t hv = {(int)rt, nb << 6 | lane, 0, 0};
+                                const i32x4v_t sv = {(int)__float_as_uint(scv.x), (int)__float_as_uint(scv.y),
+                                                     (int)__float_as_uint(scv.z), (int)__float_as_uint(scv.w)};
+                                *reinterpret_cast<i32x4v_t*>(qhdr + sl * HDR_B) = hv;
+                                *reinterpret_cast<i32x4v_t*>(qhdr + sl * HDR_B + 16) = sv;
+                            }
+                            const uint64_t took = __ballot(mine);
+                            nrec += (uint32_t)__builtin_popcountll(took);
+                            bal &= ~took;
                         }
-                        const i32x4v_t& x = acc[rb][nb];
-                        const float scr = sc[rb >> 1];
+                    }
+                } else {
+                    // level 2: per (query block, 16-row block) its maximum against tau -- eight
+                    // independent scores, then one uniform branch per passing row block -- and that
+                    // block's 4 rows appended without branches (every key is written to the next
+                    // ring slot, the count advances only for passing rows)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float v = ((float)x[r] * scr) * sbq[nb];
-                            const uint32_t row = rt * BM + rb * 16 + 4 * (lane >> 4) + r;
-                            lkeys[(nb * CAP + ecnt[nb]) * NT] = score_key(v, row);
-                            ecnt[nb] += (v >= tau[nb] && row < p.n_rows) ? 1u : 0u;
+                    for (int nb = 0; nb < 2; ++nb) {
+                        if (!__ballot(((float)mrb[nb] * (mrb[nb] >= 0 ? sc_hi : sc_lo)) * sbq[nb] >= tau[nb])) continue;
+                        BSR_FCNT(2);
+                        uint32_t pm = 0;  // the lane's passing row blocks
+                        bool pass_rb[8];
+#pragma unroll
+                        for (int rb = 0; rb < 8; ++rb) {
+                            const i32x4v_t& x = acc[rb][nb];
+                            const int bm = max(max(x[0], x[1]), max(x[2], x[3]));
+                            if constexpr (L2) pass_rb[rb] = ((float)bm * sc[rb >> 1]) * sbq[nb] >= tau[nb];
+                            else pm |= (((float)bm * sc[rb >> 1]) * sbq[nb] >= tau[nb]) ? 1u << rb : 0u;
+                        }
+#pragma unroll
+                        for (int rb = 0; rb < 8; ++rb) {
+                            if (!__ballot(L2 ? pass_rb[rb] : ((pm >> rb) & 1u))) continue;
+                            BSR_FCNT(3);
+                            if (__ballot(ecnt[nb] > (uint32_t)(CAP - 4))) {  // room for 4 rows (rarely not)
+                                flush_ring(nb);
+                                stored = true;
+                            }
+                            const i32x4v_t& x = acc[rb][nb];
+                            const float scr = sc[rb >> 1];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float v = ((float)x[r] * scr) * sbq[nb];
+                                const uint32_t row = rt * BM + rb * 16 + 4 * (lane >> 4) + r;
+                                lkeys[(nb * CAP + ecnt[nb]) * NT] = score_key(v, row);
+                                ecnt[nb] += (v >= tau[nb] && row < p.n_rows) ? 1u : 0u;
+                            }
                         }
                     }
                 }
@@ -1002,8 +1120,12 @@ __global__ __launch_bounds__(512, 1) void k_filter_qs16(GemmArgs p) {
     }
 #endif
     if constexpr (EMIT) {
-        flush_ring(0);
-        flush_ring(1);
+        if constexpr (QUEUE) {
+            flush_queue();
+        } else {
+            flush_ring(0);
+            flush_ring(1);
+        }
 #ifdef BSR_FILTER_COUNTERS
         if (lane == 0) {
             for (int i = 0; i < 4; ++i) atomicAdd(&g_filter_counters[i], fcnt[i]);
@@ -1986,6 +2108,11 @@ hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s) {
 }
 hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s) {
     launch_filter<true>(a, s);
+    return hipGetLastError();
+}
+hipError_t launch_filter_emit_gang(const GemmArgs& a, hipStream_t s) {
+    if (a.row_bytes != 12 * kSliceB) return hipErrorInvalidValue;
+    BSR_KLAUNCH((k_filter_qs16<true, 12, true>), dim3(filter_grid(a.n_qt)), dim3(512), s, a);
     return hipGetLastError();
 }
 hipError_t launch_sample_fixup(const GemmArgs& a, hipStream_t s) {

@@ -227,8 +227,17 @@ constexpr uint32_t kGangWords = 2 * 256;
 // small-shard build at 2.5M rows, 0.8% at 5M, 0-1% faster at 10M -- profiles/r05hm_hist_*,
 // r05e_hist_10m.txt; the threshold was 256, ~2.5M rows)
 constexpr uint32_t kGangMinTiles = 600;
+// The 768-byte gang build's emission queue: records per wave (one record = the 32 integer values
+// of one lane's query block on one tile; at most 64: the flush takes one record per lane).  32, 48
+// and 64 timed in one process at 10M rows lie within the run's spread of each other
+// (profiles/r10_emit_queue.txt); a wave queues ~125 records per launch at the bench's rate.
+constexpr int kEmitQueueDepth = 48;
 hipError_t launch_filter_sample(const GemmArgs& a, hipStream_t s);
 hipError_t launch_filter_emit(const GemmArgs& a, hipStream_t s);
+// The 768-byte gang build k_filter_qs16<true, 12, true> whatever the shard size (the kernel-level
+// tests' entry; 768-byte rows only).  Below kGangMinTiles static tiles per row stream no workgroup
+// runs in a gang, so the throttle is idle and the launch emits what launch_filter_emit emits.
+hipError_t launch_filter_emit_gang(const GemmArgs& a, hipStream_t s);
 // The sample tiles' share of the emission (a.s_tiles != 0; after the threshold is final, before
 // the rescore): for every query q < a.n_q and sample value S[q][j] >= tau[q] (ties included),
 // the 32 rows of that block are scored as the emit pass scores them and those reaching tau[q]

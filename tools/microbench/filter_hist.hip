@@ -1,12 +1,19 @@
 // Lab harness (round 5): the small-shard bisection.  The product emit filter k_filter_qs16<true,12>
 // against the same kernel at earlier commits of this repository (tools/microbench/extract_old.sh:
 // round 2's final kernel, the static DMA schedule, the dynamic tail, round 3's final kernel, the
-// XCD-local tail pools, the row-stream gangs, and r08 = commit 1028ff6, the last one whose kernel
+// XCD-local tail pools, the row-stream gangs, r08 = commit 1028ff6, the last one whose kernel
 // carried the lab template parameters EPI / TAILX / GANG / RING / L2 / FW / KSB: the variants
-// measured and dropped are instantiated from there), interleaved in one process (same clocks) on a
-// synthetic int8 shard; every variant must emit the same candidate set per query before it is
-// timed.  Build: make -C tools/microbench filter_hist   Run: ./filter_hist [rows] [queries] [rounds] [tau]
+// measured and dropped are instantiated from there, and r09 = commit f7be914, the gang build with
+// per-lane emission rings, the parent of the queued level 2), interleaved in one process (same
+// clocks) on a synthetic int8 shard; every variant must emit the same candidate set per query before
+// it is timed.  qd32 / qd64: the working tree's kernel at other emission-queue depths (the product's: 48).
+// Build: make -C tools/microbench filter_hist (or filter_hist_lean: the product, r09 and the queue
+// depths only)   Run: ./filter_hist [rows] [queries] [rounds] [tau ...]
 #include "k_filter.hip"
+#include "old/r09/k_filter.hip"
+#include "old/qd32/k_filter.hip"
+#include "old/qd64/k_filter.hip"
+#ifndef HIST_LEAN
 #include "old/r02/k_filter.hip"
 #include "old/static/k_filter.hip"
 #include "old/dyntail/k_filter.hip"
@@ -14,6 +21,7 @@
 #include "old/xpools/k_filter.hip"
 #include "old/gangs/k_filter.hip"
 #include "old/r08/k_filter.hip"
+#endif
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -54,7 +62,11 @@ static GA as_old(const bsr::GemmArgs& g) {
 int main(int argc, char** argv) {
     const uint32_t n = argc > 1 ? atoi(argv[1]) : 1000000, nq = argc > 2 ? atoi(argv[2]) : 1000;
     const int rounds = argc > 3 ? atoi(argv[3]) : 15;
-    const float tau_emit = argc > 4 ? atof(argv[4]) : 0.1284f;
+    // (the thresholds timed after tau = inf; the emitted sets are compared at the first)
+    std::vector<float> taus;
+    for (int i = 4; i < argc; ++i) taus.push_back((float)atof(argv[i]));
+    if (taus.empty()) taus.push_back(0.1284f);
+    const float tau_emit = taus[0];
     const uint32_t ld = 768, qpad = (nq + 255) / 256 * 256, npad = (n + 255) / 256 * 256, cap = 1024;
     const uint32_t n_cnt = qpad + 8 * bsr::kTailCounters + bsr::kGangWords;
     uint8_t *A8, *B8;
@@ -82,6 +94,10 @@ int main(int argc, char** argv) {
     const double ops = 2.0 * nq * (double)n * ld;
 
     struct V { const char* name; std::function<void()> launch; std::vector<float> t; };
+    const auto g_r09 = as_old<bsr_r09::GemmArgs>(g);  // (today's GemmArgs: a plain copy, as the queue depths')
+    const auto g_qd32 = as_old<bsr_qd32::GemmArgs>(g);
+    const auto g_qd64 = as_old<bsr_qd64::GemmArgs>(g);
+#ifndef HIST_LEAN
     const auto g_r02 = as_old<bsr_r02::GemmArgs>(g);
     const auto g_static = as_old<bsr_static::GemmArgs>(g);
     const auto g_dyn = as_old<bsr_dyntail::GemmArgs>(g);
@@ -89,18 +105,24 @@ int main(int argc, char** argv) {
     const auto g_xp = as_old<bsr_xpools::GemmArgs>(g);
     const auto g_gang = as_old<bsr_gangs::GemmArgs>(g);
     const auto g_r08 = as_old<bsr_r08::GemmArgs>(g);  // (today's GemmArgs: a plain copy)
+#endif
     const dim3 G(grid), B(512);
     // FOCUS=1 (default): the product against its round-5 candidates and the two fastest earlier
     // kernels; FOCUS=0: every commit of the history as well
     const bool focus = getenv("FOCUS") == nullptr || atoi(getenv("FOCUS")) != 0;
     std::vector<V> vs = {
         // the two shipped builds (product = the gang build, small = the small-shard build: the row
-        // "g0_l2b_fw0" of profiles/r05c_hist_*, r05e_hist_*) and the same two at r08; parent and
-        // parent_b are one kernel: the gap between their medians is the run's own noise
+        // "g0_l2b_fw0" of profiles/r05c_hist_*, r05e_hist_*), the gang build at r09 (parent and
+        // parent_b are one kernel: the gap between their medians is the run's own noise), the
+        // product at queue depths 32 and 64, and the two builds at r08
         {"product", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12>), G, B, 0, 0, g); }, {}},
-        {"parent", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12>), G, B, 0, 0, g_r08); }, {}},
-        {"parent_b", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12>), G, B, 0, 0, g_r08); }, {}},
+        {"parent", [&] { hipLaunchKernelGGL((bsr_r09::k_filter_qs16<true, 12>), G, B, 0, 0, g_r09); }, {}},
+        {"parent_b", [&] { hipLaunchKernelGGL((bsr_r09::k_filter_qs16<true, 12>), G, B, 0, 0, g_r09); }, {}},
+        {"qd32", [&] { hipLaunchKernelGGL((bsr_qd32::k_filter_qs16<true, 12>), G, B, 0, 0, g_qd32); }, {}},
+        {"qd64", [&] { hipLaunchKernelGGL((bsr_qd64::k_filter_qs16<true, 12>), G, B, 0, 0, g_qd64); }, {}},
         {"small", [&] { hipLaunchKernelGGL((bsr::k_filter_qs16<true, 12, false>), G, B, 0, 0, g); }, {}},
+#ifndef HIST_LEAN
+        {"r08", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12>), G, B, 0, 0, g_r08); }, {}},
         {"parent_small", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 8, 0, 0, 1, 0>), G, B, 0, 0, g_r08); }, {}},
         {"static", [&] { hipLaunchKernelGGL((bsr_static::k_filter_qs16<true, 12>), G, B, 0, 0, g_static); }, {}},
         {"dyntail", [&] { hipLaunchKernelGGL((bsr_dyntail::k_filter_qs16<true, 12>), G, B, 0, 0, g_dyn); }, {}},
@@ -109,7 +131,9 @@ int main(int argc, char** argv) {
         // FW = 0 (no explicit wait in the flush)
         {"g0_t0_l2b_fw0", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 0, 0, 0, 1, 0>), G, B, 0, 0, g_r08); }, {}},
         {"g2_l2b_fw0", [&] { hipLaunchKernelGGL((bsr_r08::k_filter_qs16<true, 12, 0, 8, 2, 0, 1, 0>), G, B, 0, 0, g_r08); }, {}},
+#endif
     };
+#ifndef HIST_LEAN
     if (!focus) {
         std::vector<V> more = {
             {"r02", [&] { hipLaunchKernelGGL((bsr_r02::k_filter_qs16<true, 12>), G, B, 0, 0, g_r02); }, {}},
@@ -123,6 +147,9 @@ int main(int argc, char** argv) {
         };
         vs.insert(vs.end(), more.begin(), more.end());
     }
+#else
+    (void)focus;
+#endif
 
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0));
@@ -169,18 +196,26 @@ int main(int argc, char** argv) {
     fflush(stdout);
     if (!same) return 2;
     for (int i = 0; i < 60; ++i) run(vs[i % vs.size()], tau_emit);  // settle the clock
-    for (float tv : {INFINITY, tau_emit}) {
+    taus.insert(taus.begin(), INFINITY);
+    for (float tv : taus) {
         for (auto& v : vs) v.t.clear();
         for (int r = 0; r < rounds; ++r)
             for (size_t j = 0; j < vs.size(); ++j) {  // rotate the order every round
                 V& v = vs[(j + r) % vs.size()];
                 v.t.push_back(run(v, tv));
             }
+        {  // (the rate this threshold emits at: the last launch's counters)
+            std::vector<uint32_t> hc(qpad);
+            CHECK(hipMemcpy(hc.data(), cnt, qpad * 4, hipMemcpyDeviceToHost));
+            double tot = 0;
+            for (uint32_t q = 0; q < nq; ++q) tot += hc[q];
+            printf("tau=%g: emitted per query %.1f\n", tv, tot / nq);
+        }
         for (auto& v : vs) {
             std::sort(v.t.begin(), v.t.end());
             const float med = v.t[v.t.size() / 2];
-            printf("%-12s rows %9u tau=%-8g median %7.4f ms  min %7.4f ms  %7.1f TOP/s = %.4f of the int8 peak\n",
-                   v.name, n, tv, med, v.t[0], ops / (med * 1e-3) / 1e12, ops / (med * 1e-3) / 5.0e15);
+            printf("%-12s rows %9u tau=%-8g median %7.4f ms  min %7.4f  max %7.4f ms  %7.1f TOP/s = %.4f of the int8 peak\n",
+                   v.name, n, tv, med, v.t[0], v.t.back(), ops / (med * 1e-3) / 1e12, ops / (med * 1e-3) / 5.0e15);
         }
         fflush(stdout);
     }
