@@ -809,11 +809,6 @@ static int run_exact_rounds(bsr_index* ix, const int32_t* ids, uint32_t n_ids, u
     return run_list_scan(ix, ids, n_ids, k, ix->live_list.as<uint32_t>(), (uint32_t)ix->live_rows());
 }
 
-static uint32_t kp_for(uint32_t k) { return 64u * ((3u * k + 34u + 63u) / 64u) - 1u; }
-static uint32_t cap_for(uint32_t k) { return 16u * (kp_for(k) + 1u); }
-
-static uint32_t ks_for(uint32_t k) { return (kp_for(k) + 1u) / 8u; }
-
 // The self-thresholded single-query path (round 6, DESIGN.md §5 tiny batches): batches of <= 16
 // queries over shards of >= kSkinnyTopMinRows rows, k' <= 63, rows of <= 16 K slices, with the
 // tiny-batch rescore kernel (BSR_SKINNY_TOP=0 turns it off, for A/B runs).  No sample pass and

@@ -1613,6 +1613,9 @@ hipError_t launch_rescore(const RescoreArgs& a_in, hipStream_t s) {
     if (!a_in.n_items) return hipSuccess;
     RescoreArgs a = a_in;
     a.solo = 0;
+    // (the global threshold's rescore knows no tombstones: k_rescore_flat does not read `dead`, and
+    // a global-threshold search is only taken by an index without a deleted row)
+    if (a.excl_out && a.dead) return hipErrorInvalidValue;
     const uint32_t e = (a.k + 63) / 64;
     // the first pass (mode S) of a tiny batch: one workgroup per query, one wave per chunk
     // (BSR_RESCORE_KP=0: the one-wave kernel instead, for A/B runs; read per call, as top_slots

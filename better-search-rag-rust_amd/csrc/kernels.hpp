@@ -332,6 +332,7 @@ struct RescoreArgs {
     uint64_t offset, n_rows;    // global index of local row 0; the shard's live rows (count = min(k, n_rows))
     // Tombstones (k_rescore, k_rescore_kp): the index's bitset of deleted rows --
     // a candidate whose bit is set offers no key.  nullptr: no row of the index is deleted.
+    // (Not with excl_out: k_rescore_flat does not read it, and launch_rescore refuses the pair.)
     const uint64_t* dead;
     // (optional) the host mirror of the same rows (fine-grained pinned memory): every result row
     // is written there too, by the wave that finalizes it, so the publish copies only the status
@@ -358,6 +359,7 @@ struct RescoreArgs {
     // pub_bytes of the packed result buffer pub_src to host memory pub_dst (fine-grained pinned)
     // and then sets *pub_flag = 1 with a system-scope release, so the host sees the result
     // without waiting for the stream's completion signal and without a D2H copy node.
+    // (pub_bytes: a multiple of 16 -- the copy moves whole 16-byte units and drops a remainder.)
     const uint8_t* pub_src;
     uint8_t* pub_dst;
     size_t pub_bytes;
@@ -373,6 +375,11 @@ constexpr uint32_t kTicketLeaves = 8, kTicketStride = 16, kTicketWords = (kTicke
 constexpr uint32_t kRescoreAllGrid = 128;
 // Candidate lists up to this many keys (k <= 10) are selected inside the rescore kernel.
 constexpr uint32_t kFusedSelectCap = 1024;
+// The candidate stage's sizes for a top-k: k' candidates per query, lists of cap keys, the
+// threshold's depth ks in the sample.
+static inline uint32_t kp_for(uint32_t k) { return 64u * ((3u * k + 34u + 63u) / 64u) - 1u; }
+static inline uint32_t cap_for(uint32_t k) { return 16u * (kp_for(k) + 1u); }
+static inline uint32_t ks_for(uint32_t k) { return (kp_for(k) + 1u) / 8u; }
 hipError_t launch_rescore(const RescoreArgs& a, hipStream_t s);
 // whether launch_rescore takes k_rescore_kp for a tiny batch's first pass (BSR_RESCORE_KP != 0)
 bool rescore_kp_enabled();
