@@ -60,6 +60,17 @@ void DevBuf::release() {
     p = nullptr;
     bytes = 0;
 }
+int DevBuf::grow(size_t need, size_t keep, hipStream_t s) {
+    if (p && bytes >= need) return BSR_OK;
+    DevBuf grown;
+    BSR_TRY(grown.ensure(need));
+    BSR_HIP(hipMemsetAsync(grown.p, 0, need, s));
+    if (p && keep) BSR_HIP(hipMemcpyAsync(grown.p, p, keep, hipMemcpyDeviceToDevice, s));
+    BSR_HIP(hipStreamSynchronize(s));
+    std::swap(p, grown.p);
+    std::swap(bytes, grown.bytes);
+    return BSR_OK;
+}
 
 // Completion of a search's work on its stream, polled (hipStreamQuery) rather than blocked on:
 // a blocking synchronize wakes the host ~15 us after the GPU finishes (measured: the D2H copy
@@ -186,6 +197,42 @@ static inline void ev_collect(Events& e, double& ms, uint64_t& n, uint64_t launc
 }
 
 // ---------------------------------------------------------------------------------------
+// small helpers
+// ---------------------------------------------------------------------------------------
+// An input that may be host memory, on the device: a device pointer (dev) as it is, host memory
+// copied into buf on the index's stream.
+template <class T>
+static int on_device(bsr_index* ix, DevBuf& buf, const T* src, size_t bytes, bool dev, const T** out) {
+    *out = src;
+    if (dev) return BSR_OK;
+    BSR_TRY(buf.ensure(bytes));
+    BSR_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ix->stream));
+    *out = buf.as<T>();
+    return BSR_OK;
+}
+// A byte budget from the environment (read per call): a decimal number, else the default.
+static uint64_t env_bytes(const char* name, uint64_t dflt) {
+    const char* v = getenv(name);
+    if (v && v[0]) {
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v, &end, 10);
+        if (end != v) return x;
+    }
+    return dflt;
+}
+// The device's row flags and int8 row error bound, read back (one stream wait), and what follows
+// from them: whether the filter may serve this index.
+static int read_row_state(bsr_index* ix) {
+    uint32_t f[2] = {0, 0};
+    BSR_HIP(hipMemcpyAsync(f, ix->flags.p, sizeof f, hipMemcpyDeviceToHost, ix->stream));
+    BSR_HIP(hipStreamSynchronize(ix->stream));
+    ix->row_flags = f[0];
+    memcpy(&ix->row_ebound, &f[1], sizeof(float));
+    ix->approx_ok = !(f[0] & (kRowNormOvf | kRowNormRange)) && !(ix->cfg.flags & BSR_FLAG_EXACT_ONLY);
+    return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // load / append
 // ---------------------------------------------------------------------------------------
 static int index_prepare_rows(bsr_index* ix, const void* rows, uint64_t n_rows, uint64_t first_row) {
@@ -193,17 +240,12 @@ static int index_prepare_rows(bsr_index* ix, const void* rows, uint64_t n_rows, 
     float* dst = ix->rows.as<float>() + first_row * ix->ld;
     const bool dev = is_device_ptr(rows);
     const size_t elem = ix->cfg.dtype == BSR_BF16 ? 2 : 4;
-    const void* src = rows;
+    const void* src = nullptr;
     // Device rows may still be in flight on ANY stream of the caller (a torch side stream, a
     // communication stream): the ABI has no stream argument, and a load runs once, outside
     // any timed region, so a full device synchronize costs nothing and removes the hazard.
     if (dev) BSR_HIP(hipDeviceSynchronize());
-    if (!dev) {
-        BSR_TRY(ix->tmp.ensure(n_rows * (size_t)ix->dim * elem));
-        BSR_HIP(hipMemcpyAsync(ix->tmp.p, rows, n_rows * (size_t)ix->dim * elem, hipMemcpyHostToDevice,
-                               ix->stream));
-        src = ix->tmp.p;
-    }
+    BSR_TRY(on_device(ix, ix->tmp, rows, n_rows * (size_t)ix->dim * elem, dev, &src));
     if (ix->cfg.dtype == BSR_BF16)
         BSR_HIP(launch_widen_bf16_rows(static_cast<const uint16_t*>(src), n_rows, ix->dim, ix->ld, dst, ix->stream));
     else
@@ -226,23 +268,17 @@ static int index_finish_load(bsr_index* ix) {
     // The sample pass reads every kSampleStride-th row: those rows, contiguous (1/32 of the
     // operand bytes), so that it streams whole rows, quantized with one scale per filter tile
     // of sampled rows (its epilogue then takes integer maxima).
-    const uint64_t n_s = (ix->n + kSampleStride - 1) / kSampleStride;
-    const uint64_t n_s_pad = round_up(std::max<uint64_t>(n_s, 1), kSampleScaleRows);
+    const uint64_t n_s_pad = sample_rows_pad(ix->n);
     BSR_TRY(ix->fop_s.ensure((size_t)n_s_pad * ix->op_row_bytes));
     BSR_TRY(ix->ascale_s.ensure((size_t)(n_s_pad / kSampleScaleRows) * sizeof(float)));
     BSR_HIP(launch_rows_to_i8_sample(ix->rows.as<float>(), ix->n, ix->dim, ix->ld, ix->fop_s.as<int8_t>(),
                                      ix->ascale_s.as<float>(), ix->stream));
-    uint32_t f[2] = {0, 0};
-    BSR_HIP(hipMemcpyAsync(f, ix->flags.p, sizeof f, hipMemcpyDeviceToHost, ix->stream));
-    BSR_HIP(hipStreamSynchronize(ix->stream));
-    ix->row_flags = f[0];
-    memcpy(&ix->row_ebound, &f[1], sizeof(float));
-    if (f[0] & kRowNonFinite) {
+    BSR_TRY(read_row_state(ix));
+    if (ix->row_flags & kRowNonFinite) {
         ix->loaded = false;
         ix->n = 0;
         return set_error(BSR_E_NONFINITE, "corpus contains NaN/Inf (the reference panics on NaN distances)");
     }
-    ix->approx_ok = !(f[0] & (kRowNormOvf | kRowNormRange)) && !(ix->cfg.flags & BSR_FLAG_EXACT_ONLY);
     ix->loaded = true;
     return BSR_OK;
 }
@@ -328,17 +364,8 @@ int bsr_index_append_impl(bsr_index* ix, const void* rows, uint64_t n_rows) {
     const uint64_t new_n = old_n + n_rows;
     if (new_n >= (1ull << 31)) return set_error(BSR_E_INVALID, "shard too large");
     const uint64_t new_pad = round_up(new_n, kRowPad);
-    if (new_pad * (size_t)ix->ld * sizeof(float) > ix->rows.bytes) {
-        DevBuf grown;
-        BSR_TRY(grown.ensure(new_pad * (size_t)ix->ld * sizeof(float)));
-        BSR_HIP(hipMemsetAsync(grown.p, 0, new_pad * (size_t)ix->ld * sizeof(float), ix->stream));
-        if (old_n)
-            BSR_HIP(hipMemcpyAsync(grown.p, ix->rows.p, old_n * (size_t)ix->ld * sizeof(float),
-                                   hipMemcpyDeviceToDevice, ix->stream));
-        BSR_HIP(hipStreamSynchronize(ix->stream));
-        std::swap(ix->rows.p, grown.p);
-        std::swap(ix->rows.bytes, grown.bytes);
-    }
+    const size_t row_bytes = (size_t)ix->ld * sizeof(float);
+    BSR_TRY(ix->rows.grow(new_pad * row_bytes, old_n * row_bytes, ix->stream));
     ix->n = new_n;
     ix->n_pad = new_pad;
     // the tombstones are kept and the appended rows are live; the requantised operand of the
@@ -373,17 +400,7 @@ int bsr_index_get_many_impl(const bsr_index* ix, uint64_t offset, uint64_t count
 // The bitset sized for the padded shard: allocated zeroed, or grown with its contents kept (the
 // stream is idle when the old allocation is freed).
 static int dead_reserve(bsr_index* ix) {
-    const size_t need = ix->n_pad / 64 * sizeof(uint64_t);
-    if (ix->dead.p && ix->dead.bytes >= need) return BSR_OK;
-    DevBuf grown;
-    BSR_TRY(grown.ensure(need));
-    BSR_HIP(hipMemsetAsync(grown.p, 0, need, ix->stream));
-    if (ix->dead.p)
-        BSR_HIP(hipMemcpyAsync(grown.p, ix->dead.p, ix->dead.bytes, hipMemcpyDeviceToDevice, ix->stream));
-    BSR_HIP(hipStreamSynchronize(ix->stream));
-    std::swap(ix->dead.p, grown.p);
-    std::swap(ix->dead.bytes, grown.bytes);
-    return BSR_OK;
+    return ix->dead.grow(ix->n_pad / 64 * sizeof(uint64_t), ix->dead.bytes, ix->stream);
 }
 
 // A deleted row scores exactly 0 in the emit, fix-up and TOP kernels and in the sample tiles, and
@@ -391,12 +408,11 @@ static int dead_reserve(bsr_index* ix) {
 // leaves tau0's order statistics and the candidate lists.  (Speed only: the exact kernels drop it
 // whatever it scores.)  After every delete, and after an append -- index_finish_load requantises
 // the shard.  Walks the whole bitset and rewrites every deleted row: O(n_dead ld), whatever the
-// number of ids of the delete.  The masked search's allow & ~dead buffer is sized here too, so
-// that no search allocates -- and invalidates the captured graphs -- because of tombstones.
+// number of ids of the delete.
 static int dead_zero_operand(bsr_index* ix) {
-    BSR_TRY(ix->mask_eff.ensure((size_t)((ix->n + 63) / 64) * sizeof(uint64_t)));
     BSR_TRY(ix->live_blk.ensure(((size_t)mask_blocks(ix->n) + 1) * sizeof(uint32_t)));
-    BSR_HIP(launch_mask_list_count(ix->dead.as<uint64_t>(), ix->n, ix->live_blk.as<uint32_t>(), ix->stream));
+    // (the bitset itself as the mask: the deleted rows ahead of every block of words)
+    BSR_HIP(launch_mask_list_count(ix->dead.as<uint64_t>(), nullptr, ix->n, ix->live_blk.as<uint32_t>(), ix->stream));
     BSR_HIP(launch_dead_zero_fop(ix->dead.as<uint64_t>(), ix->n, ix->live_blk.as<uint32_t>(), ix->op_row_bytes,
                                  ix->fop.as<uint8_t>(), ix->fop_s.as<uint8_t>(), ix->rows.as<float>(), ix->dim,
                                  ix->ascale_s.as<float>(), ix->stream));
@@ -428,12 +444,8 @@ int bsr_index::delete_rows(const uint64_t* ids, uint64_t n_ids, uint64_t* out_de
     if (!ids) return set_error(BSR_E_INVALID, "null ids");
     if (n_ids >> 32) return set_error(BSR_E_INVALID, "n_ids=%llu: at most 2^32 - 1 ids per call", (unsigned long long)n_ids);
     BSR_HIP(hipSetDevice(device));
-    const uint64_t* dids = ids;
-    if (!is_device_ptr(ids)) {
-        BSR_TRY(dead_ids.ensure((size_t)n_ids * sizeof(uint64_t)));
-        BSR_HIP(hipMemcpyAsync(dead_ids.p, ids, (size_t)n_ids * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        dids = dead_ids.as<uint64_t>();
-    }
+    const uint64_t* dids = nullptr;
+    BSR_TRY(on_device(ix, dead_ids, ids, (size_t)n_ids * sizeof(uint64_t), is_device_ptr(ids), &dids));
     BSR_TRY(dead_cnt.ensure(2 * sizeof(uint32_t)));
     BSR_HIP(hipMemsetAsync(dead_cnt.p, 0, 2 * sizeof(uint32_t), stream));
     uint32_t* bad = dead_cnt.as<uint32_t>();
@@ -477,20 +489,18 @@ int bsr_index::deleted_mask(uint64_t* out_words, uint64_t words) const {
     return BSR_OK;
 }
 
-// The exact fallback's row list with tombstones present: the live rows, ascending, built from
-// ~dead by the masked search's list kernels (the count is known: no host read), cached until the
-// next delete, append or load.
+// The exact fallback's row list with tombstones present: the live rows, ascending, built by the
+// mask list kernels with no allow mask -- every row the bitset does not remove (the count is
+// known: no host read) -- cached until the next delete, append or load.
 int bsr_index::ensure_live_list() {
     if (live_list_ok) return BSR_OK;
     const uint64_t live = live_rows();
     if (!live) return BSR_OK;
     const uint32_t n_blk = mask_blocks(n);
-    BSR_TRY(live_mask.ensure((size_t)((n + 63) / 64) * sizeof(uint64_t)));
     BSR_TRY(live_blk.ensure(((size_t)n_blk + 1) * sizeof(uint32_t)));
     BSR_TRY(live_list.ensure((size_t)live * sizeof(uint32_t)));
-    BSR_HIP(launch_dead_andnot(nullptr, dead.as<uint64_t>(), n, live_mask.as<uint64_t>(), stream));
-    BSR_HIP(launch_mask_list_count(live_mask.as<uint64_t>(), n, live_blk.as<uint32_t>(), stream));
-    BSR_HIP(launch_mask_list_scatter(live_mask.as<uint64_t>(), n, live_blk.as<uint32_t>(), (uint32_t)live,
+    BSR_HIP(launch_mask_list_count(nullptr, dead_bits(), n, live_blk.as<uint32_t>(), stream));
+    BSR_HIP(launch_mask_list_scatter(nullptr, dead_bits(), n, live_blk.as<uint32_t>(), (uint32_t)live,
                                      live_list.as<uint32_t>(), stream));
     live_list_ok = true;
     return BSR_OK;
@@ -526,23 +536,14 @@ int bsr_index::update_rows(const uint64_t* ids, const void* new_rows, uint64_t n
     const bool ids_dev = is_device_ptr(ids), rows_dev = is_device_ptr(new_rows);
     // (device inputs may be in flight on any stream of the caller: the load / append rule)
     if (ids_dev || rows_dev) BSR_HIP(hipDeviceSynchronize());
-    const uint64_t* dids = ids;
-    if (!ids_dev) {
-        BSR_TRY(upd_ids.ensure((size_t)n_ids * sizeof(uint64_t)));
-        BSR_HIP(hipMemcpyAsync(upd_ids.p, ids, (size_t)n_ids * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        dids = upd_ids.as<uint64_t>();
-    }
-    const void* src = new_rows;
-    if (!rows_dev) {
-        const size_t bytes = (size_t)n_ids * dim * (bf16 ? 2 : 4);
-        BSR_TRY(tmp.ensure(bytes));
-        BSR_HIP(hipMemcpyAsync(tmp.p, new_rows, bytes, hipMemcpyHostToDevice, stream));
-        src = tmp.p;
-    }
+    const uint64_t* dids = nullptr;
+    const void* src = nullptr;
+    BSR_TRY(on_device(ix, upd_ids, ids, (size_t)n_ids * sizeof(uint64_t), ids_dev, &dids));
+    BSR_TRY(on_device(ix, tmp, new_rows, (size_t)n_ids * dim * (bf16 ? 2 : 4), rows_dev, &src));
     // every buffer is sized before the check, so that nothing can fail between the first stored
     // byte and the last
     const uint64_t nb = (n + kQuantBlock - 1) / kQuantBlock;                                  // 32-row blocks
-    const uint64_t ng = ((n + kSampleStride - 1) / kSampleStride + kSampleScaleRows - 1) / kSampleScaleRows;  // sample groups
+    const uint64_t ng = sample_rows_pad(n) / kSampleScaleRows;                                // sample groups
     const uint64_t w_rows = n_pad / 64, w_blk = (nb + 63) / 64, w_grp = (ng + 63) / 64;
     const uint32_t cap_b = (uint32_t)std::min<uint64_t>(n_ids, nb), cap_g = (uint32_t)std::min<uint64_t>(n_ids, ng);
     const uint32_t mb_b = mask_blocks(nb), mb_g = mask_blocks(ng);
@@ -579,26 +580,20 @@ int bsr_index::update_rows(const uint64_t* ids, const void* new_rows, uint64_t n
     uint32_t* fl = flags.as<uint32_t>();
     BSR_HIP(launch_upd_scatter(dids, n_ids, global_offset, src, dim, ld, bf16, slab, stream));
     BSR_HIP(launch_upd_row_norms(slab, dids, n_ids, global_offset, dim, ld, na.as<float>(), fl, stream));
-    BSR_HIP(launch_mask_list_count(blocks, nb, blk_b, stream));
-    BSR_HIP(launch_mask_list_scatter(blocks, nb, blk_b, cap_b, list_b, stream));
+    BSR_HIP(launch_mask_list_count(blocks, nullptr, nb, blk_b, stream));
+    BSR_HIP(launch_mask_list_scatter(blocks, nullptr, nb, blk_b, cap_b, list_b, stream));
     BSR_HIP(launch_upd_rows_to_i8(slab, n, dim, ld, fop.as<int8_t>(), ascale.as<float>(), fl + 1, list_b, blk_b + mb_b,
                                   cap_b, stream));
     if (h[kUpdSampleRows]) {  // (no row the fop_s sample reads: nothing of it changes)
-        BSR_HIP(launch_mask_list_count(groups, ng, blk_g, stream));
-        BSR_HIP(launch_mask_list_scatter(groups, ng, blk_g, cap_g, list_g, stream));
+        BSR_HIP(launch_mask_list_count(groups, nullptr, ng, blk_g, stream));
+        BSR_HIP(launch_mask_list_scatter(groups, nullptr, ng, blk_g, cap_g, list_g, stream));
         BSR_HIP(launch_upd_rows_to_i8_sample(slab, n, dim, ld, fop_s.as<int8_t>(), ascale_s.as<float>(), list_g,
                                              blk_g + mb_g, cap_g, stream));
     }
     // tombstones stay as they are: the deleted rows' operand is zeroed again (as after an append)
     if (n_dead) BSR_TRY(dead_zero_operand(ix));
     // the flags are sticky (only a load clears them) and ea_max only grows (atomicMax)
-    uint32_t f[2] = {0, 0};
-    BSR_HIP(hipMemcpyAsync(f, flags.p, sizeof f, hipMemcpyDeviceToHost, stream));
-    BSR_HIP(hipStreamSynchronize(stream));
-    row_flags = f[0];
-    memcpy(&row_ebound, &f[1], sizeof(float));
-    approx_ok = !(f[0] & (kRowNormOvf | kRowNormRange)) && !(cfg.flags & BSR_FLAG_EXACT_ONLY);
-    return BSR_OK;
+    return read_row_state(ix);
 }
 
 int bsr_index_update_impl(bsr_index* ix, const uint64_t* ids, const void* rows, uint64_t n_ids) {
@@ -612,13 +607,7 @@ int bsr_index_update_impl(bsr_index* ix, const uint64_t* ids, const void* rows, 
 // The rows one chunk of the in-place move stages: BSR_COMPACT_STAGE_BYTES (read per call), 256 MB
 // by default, at least kRowPad rows.
 static uint64_t compact_stage_rows(const bsr_index* ix) {
-    uint64_t bytes = 256ull << 20;
-    const char* v = getenv("BSR_COMPACT_STAGE_BYTES");
-    if (v && v[0]) {
-        char* end = nullptr;
-        const unsigned long long x = strtoull(v, &end, 10);
-        if (end != v) bytes = x;
-    }
+    const uint64_t bytes = env_bytes("BSR_COMPACT_STAGE_BYTES", 256ull << 20);
     return std::max<uint64_t>(bytes / ((size_t)ix->ld * sizeof(float)), kRowPad);
 }
 static double host_ms() {
@@ -742,7 +731,7 @@ int bsr_index::compact_rows(uint64_t new_global_offset, uint32_t fl, uint64_t* o
         ++dead_gen;  // (the row count, the offset, the bitset: every captured graph is stale)
         if (fl & BSR_COMPACT_SHRINK) {
             // what index_finish_load sizes again, released where it is larger than that
-            const uint64_t n_s_pad = round_up(std::max<uint64_t>((n + kSampleStride - 1) / kSampleStride, 1), kSampleScaleRows);
+            const uint64_t n_s_pad = sample_rows_pad(n);
             auto drop = [](DevBuf& b, size_t need) { if (b.bytes > std::max<size_t>(need, 16)) b.release(); };
             drop(na, n_pad * sizeof(float));
             drop(fop, (size_t)n_pad * op_row_bytes);
@@ -751,7 +740,6 @@ int bsr_index::compact_rows(uint64_t new_global_offset, uint32_t fl, uint64_t* o
             drop(ascale_s, (size_t)(n_s_pad / kSampleScaleRows) * sizeof(float));
             cmp_stage.release();
             live_list.release();
-            live_mask.release();
         }
         return index_finish_load(ix);
     };
@@ -1210,13 +1198,7 @@ static QueryPrepArgs query_prep_args(const bsr_index* ix, const float* qsrc, uin
 // The queries on the device: device queries where they are, host queries copied into q_in (sized
 // here unless it already is: gtau_prepare sizes it ahead of phase A, which allocates nothing).
 static int stage_queries(bsr_index* ix, const float* queries, uint32_t nq, const float** qsrc) {
-    *qsrc = queries;
-    if (is_device_ptr(queries)) return BSR_OK;
-    const size_t bytes = (size_t)nq * ix->dim * sizeof(float);
-    BSR_TRY(ix->q_in.ensure(bytes));
-    BSR_HIP(hipMemcpyAsync(ix->q_in.p, queries, bytes, hipMemcpyHostToDevice, ix->stream));
-    *qsrc = ix->q_in.as<float>();
-    return BSR_OK;
+    return on_device(ix, ix->q_in, queries, (size_t)nq * ix->dim * sizeof(float), is_device_ptr(queries), qsrc);
 }
 
 // ---- after the status readback -----------------------------------------------------------
@@ -1231,19 +1213,24 @@ static int check_queries(bsr_index* ix, uint32_t nq) {
     return set_error(BSR_E_NONFINITE, "query %u contains NaN/Inf (the reference panics)", bad);
 }
 // The nfail queries of fail2 -- uncertified, or not served by the filter (zero/tiny/huge |b|) --
-// as the exact scans' input: their ids in ascending order, counted into stats (direct: the filter
-// cannot serve the query; fallback: it was left uncertified), in qids (device) in groups of kScanQF,
-// the last group padded with its first id.  rerun (optional): set, with nothing counted or
-// uploaded, when a query the filter serves is among them.
-static int failed_queries(bsr_index* ix, uint32_t nq, uint32_t nfail, bool* rerun = nullptr) {
-    std::vector<uint32_t>& h_fail = ix->h_fail;
-    h_fail.resize(nfail);
+// and every query's flags, read into h_fail and h_qflags.
+static int read_failed(bsr_index* ix, uint32_t nq, uint32_t nfail) {
+    ix->h_fail.resize(nfail);
     ix->h_qflags.resize(nq);
-    BSR_HIP(hipMemcpyAsync(h_fail.data(), ix->fail2.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    BSR_HIP(hipMemcpyAsync(ix->h_fail.data(), ix->fail2.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            ix->stream));
     BSR_HIP(hipMemcpyAsync(ix->h_qflags.data(), ix->qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            ix->stream));
     BSR_HIP(hipStreamSynchronize(ix->stream));
+    return BSR_OK;
+}
+// ... as the exact scans' input: their ids in ascending order, counted into stats (direct: the filter
+// cannot serve the query; fallback: it was left uncertified), in qids (device) in groups of kScanQF,
+// the last group padded with its first id.  rerun (optional): set, with nothing counted or
+// uploaded, when a query the filter serves is among them.
+static int failed_queries(bsr_index* ix, uint32_t nq, uint32_t nfail, bool* rerun = nullptr) {
+    BSR_TRY(read_failed(ix, nq, nfail));
+    std::vector<uint32_t>& h_fail = ix->h_fail;
     if (rerun) {
         for (uint32_t q : h_fail) *rerun |= !(ix->h_qflags[q] & kQueryNoApprox);
         if (*rerun) return BSR_OK;
@@ -1277,19 +1264,32 @@ static int finalize_and_read(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t n_
     return BSR_OK;
 }
 
+// ---- the opening of a batch, shared by every search entry point ---------------------------------
+// The checks every search makes first ...
+static int check_batch(const bsr_index* ix, uint32_t k) {
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (k == 0 || k > ix->cfg.max_k) return set_error(BSR_E_INVALID, "k=%u outside [1, max_k=%u]", k, ix->cfg.max_k);
+    return BSR_OK;
+}
+// ... and, after the caller's own argument checks: the device, the batch's statistics (path: the
+// search_path bits known from the start) and its result buffer.
+static int begin_batch(bsr_index* ix, uint32_t nq, uint32_t k, uint32_t path = 0) {
+    BSR_HIP(hipSetDevice(ix->device));
+    ix->stats = bsr_search_stats{};
+    ix->stats.n_queries = nq;
+    ix->stats.filter_op = 0;  // int8
+    ix->stats.row_ebound = ix->row_ebound;
+    ix->stats.search_path = path;
+    return ix->prepare_result(nq, k);
+}
+
 // force_threshold: the thresholded path whatever top_slots says, launched directly (the rerun of a
 // batch the self-thresholded path left uncertified, below).
 int bsr_index::search_device(const float* queries, uint32_t nq, uint32_t k, int (*after_launch)(void*), void* ctx,
                              bool force_threshold) {
     bsr_index* ix = this;
-    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
-    if (k == 0 || k > ix->cfg.max_k) return set_error(BSR_E_INVALID, "k=%u outside [1, max_k=%u]", k, ix->cfg.max_k);
-    BSR_HIP(hipSetDevice(ix->device));
-    stats = bsr_search_stats{};
-    stats.n_queries = nq;
-    stats.filter_op = 0;  // int8
-    stats.row_ebound = row_ebound;
-    BSR_TRY(prepare_result(nq, k));
+    BSR_TRY(check_batch(ix, k));
+    BSR_TRY(begin_batch(ix, nq, k));
     if (nq == 0) return BSR_OK;
     if (!queries) return set_error(BSR_E_INVALID, "null queries");
 
@@ -1496,23 +1496,45 @@ static bool masked_filter_path(const bsr_index* ix, uint32_t mode, uint64_t A, u
     return !(mode == BSR_MASK_AUTO && auto_prefers_list(ix->n, A, nq, k));
 }
 
+// The masked filter stage behind the cut, shared by the two masked searches: every remaining row of
+// every query rescored exactly and certified against tau0 (mode B; raw_cnt / items: the cut's
+// outputs, n_rows: what the fused finalize counts against), then read_bytes of the result read back
+// (the status words lead it), the host polling the stream.  *nfail = the queries left to the list scan.
+static int masked_filter_stage(bsr_index* ix, uint32_t nq, uint32_t k, const uint32_t* raw_cnt, const uint32_t* items,
+                               uint32_t cap_m, uint64_t n_rows, size_t read_bytes, uint32_t* nfail) {
+    ev_begin(ix, ix->ev_rescore);
+    RescoreArgs rb = rescore_args(ix, nq, k);
+    rb.n_items_dev = items;
+    rb.qlist = reinterpret_cast<const uint32_t*>(ix->qids_id.as<int32_t>());  // (identity for q < nq)
+    rescore_emitted(rb, ix, cap_m);
+    rb.fail_cnt = ix->d_status + kStFail2;
+    rb.fail_list = ix->fail2.as<uint32_t>();
+    rb.n_rows = n_rows;
+    rescore_bookkeeping(rb, ix, nq, raw_cnt);
+    BSR_HIP(launch_rescore(rb, ix->stream));
+    ev_end(ix, ix->ev_rescore);
+    ix->next_status_clean = true;
+    ev_end(ix, ix->ev_total);
+    BSR_HIP(hipMemcpyAsync(ix->h_res, ix->res[ix->cur].p, read_bytes, hipMemcpyDeviceToHost, ix->stream));
+    BSR_HIP(stream_wait(ix->stream));
+    BSR_TRY(check_queries(ix, nq));
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(ix->h_res);
+    ix->stats.n_emitted = st[kStEmitted];
+    *nfail = st[kStFail2];
+    return BSR_OK;
+}
+
 int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
                                     uint64_t allow_words, uint32_t mode) {
     bsr_index* ix = this;
-    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
-    if (k == 0 || k > ix->cfg.max_k) return set_error(BSR_E_INVALID, "k=%u outside [1, max_k=%u]", k, ix->cfg.max_k);
+    BSR_TRY(check_batch(ix, k));
     if (!allow) return set_error(BSR_E_INVALID, "null allow mask (bsr_local_top_k searches without one)");
     if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
         return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
     if (allow_words != (n + 63) / 64)
         return set_error(BSR_E_INVALID, "allow_words=%llu, the index holds %llu rows (%llu words)",
                          (unsigned long long)allow_words, (unsigned long long)n, (unsigned long long)((n + 63) / 64));
-    BSR_HIP(hipSetDevice(ix->device));
-    stats = bsr_search_stats{};
-    stats.n_queries = nq;
-    stats.filter_op = 0;
-    stats.row_ebound = row_ebound;
-    BSR_TRY(prepare_result(nq, k));
+    BSR_TRY(begin_batch(ix, nq, k));
     if (nq == 0) return BSR_OK;
     if (!queries) return set_error(BSR_E_INVALID, "null queries");
 
@@ -1525,24 +1547,15 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
     BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
     // The mask on the device, and the number of allowed rows A: the host needs it for the path,
     // the list's size and the result count min(k, A).
+    // (tombstones: what drives A, the list, the cut and the counts is allow & ~dead, formed by every
+    // mask kernel as it reads)
     const uint64_t* dmask = allow;
     uint32_t A = 0;
     if (n > 0) {
-        if (!is_device_ptr(allow)) {
-            BSR_TRY(mask_dev.ensure((size_t)allow_words * sizeof(uint64_t)));
-            BSR_HIP(hipMemcpyAsync(mask_dev.p, allow, (size_t)allow_words * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                   stream));
-            dmask = mask_dev.as<uint64_t>();
-        }
-        if (n_dead) {
-            // tombstones: the mask that drives A, the list, the cut and the counts is allow & ~dead
-            BSR_TRY(mask_eff.ensure((size_t)allow_words * sizeof(uint64_t)));
-            BSR_HIP(launch_dead_andnot(dmask, dead.as<uint64_t>(), n, mask_eff.as<uint64_t>(), stream));
-            dmask = mask_eff.as<uint64_t>();
-        }
+        BSR_TRY(on_device(ix, mask_dev, allow, (size_t)allow_words * sizeof(uint64_t), is_device_ptr(allow), &dmask));
         const uint32_t n_blk = mask_blocks(n);
         BSR_TRY(mask_blk.ensure(((size_t)n_blk + 1) * sizeof(uint32_t)));
-        BSR_HIP(launch_mask_list_count(dmask, n, mask_blk.as<uint32_t>(), stream));
+        BSR_HIP(launch_mask_list_count(dmask, dead_bits(), n, mask_blk.as<uint32_t>(), stream));
         BSR_HIP(hipMemcpyAsync(&A, mask_blk.as<uint32_t>() + n_blk, sizeof A, hipMemcpyDeviceToHost, stream));
         BSR_HIP(hipStreamSynchronize(stream));
     }
@@ -1557,7 +1570,8 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
     auto build_list = [&]() -> int {
         if (have_list || !A) return BSR_OK;
         BSR_TRY(mask_list.ensure((size_t)A * sizeof(uint32_t)));
-        BSR_HIP(launch_mask_list_scatter(dmask, n, mask_blk.as<uint32_t>(), A, mask_list.as<uint32_t>(), stream));
+        BSR_HIP(launch_mask_list_scatter(dmask, dead_bits(), n, mask_blk.as<uint32_t>(), A, mask_list.as<uint32_t>(),
+                                         stream));
         have_list = true;
         return BSR_OK;
     };
@@ -1580,26 +1594,10 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
     BSR_TRY(emit_pass(ix, nq, qpad, k, cap_m));
     uint32_t* raw_cnt = mask_aux.as<uint32_t>();
     uint32_t* items = raw_cnt + qpad;
-    BSR_HIP(launch_mask_cut(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dmask, n, raw_cnt, items, stream));
-    ev_begin(ix, ev_rescore);
-    RescoreArgs rb = rescore_args(ix, nq, k);
-    rb.n_items_dev = items;
-    rb.qlist = reinterpret_cast<const uint32_t*>(qids_id.as<int32_t>());  // (identity for q < nq)
-    rescore_emitted(rb, ix, cap_m);
-    rb.fail_cnt = d_status + kStFail2;
-    rb.fail_list = fail2.as<uint32_t>();
-    rb.n_rows = A;  // (the fused finalize's count: min(k, A))
-    rescore_bookkeeping(rb, ix, nq, raw_cnt);
-    BSR_HIP(launch_rescore(rb, stream));
-    ev_end(ix, ev_rescore);
-    next_status_clean = true;
-    ev_end(ix, ev_total);
-    BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, res_bytes, hipMemcpyDeviceToHost, stream));
-    BSR_HIP(stream_wait(stream));
-    BSR_TRY(check_queries(ix, nq));
-    const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
-    stats.n_emitted = st[kStEmitted];
-    const uint32_t nfail = st[kStFail2];
+    BSR_HIP(launch_mask_cut(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dmask, allow_words, nullptr, dead_bits(),
+                            n, raw_cnt, items, stream));
+    uint32_t nfail = 0;  // (n_rows = A: the fused finalize's count is min(k, A))
+    BSR_TRY(masked_filter_stage(ix, nq, k, raw_cnt, items, cap_m, A, res_bytes, &nfail));
     if (!nfail) return BSR_OK;
     // Uncertified queries (an overflowed list among them) and queries the filter cannot
     // serve take the list scan: the reference's arithmetic on every allowed row.
@@ -1616,14 +1614,7 @@ int bsr_index::search_device_masked(const float* queries, uint32_t nq, uint32_t 
 // The ids one chunk of row lists may hold: BSR_MASK_LIST_BUDGET bytes (read per search), 256 MB
 // by default.  A dense mask per tenant over a large shard would otherwise want n_masks x n ids.
 static uint64_t mask_list_budget_ids() {
-    uint64_t bytes = 256ull << 20;
-    const char* v = getenv("BSR_MASK_LIST_BUDGET");
-    if (v && v[0]) {
-        char* end = nullptr;
-        const unsigned long long x = strtoull(v, &end, 10);
-        if (end != v) bytes = x;
-    }
-    return std::max<uint64_t>(bytes / sizeof(uint32_t), 1);
+    return std::max<uint64_t>(env_bytes("BSR_MASK_LIST_BUDGET", 256ull << 20) / sizeof(uint32_t), 1);
 }
 
 // The exact list scan of the queries with on_list[q] set, every one over the list of its own mask
@@ -1744,8 +1735,7 @@ int bsr_index::search_device_masked_groups(const float* queries, uint32_t nq, ui
                                            uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
                                            uint32_t mode) {
     bsr_index* ix = this;
-    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
-    if (k == 0 || k > ix->cfg.max_k) return set_error(BSR_E_INVALID, "k=%u outside [1, max_k=%u]", k, ix->cfg.max_k);
+    BSR_TRY(check_batch(ix, k));
     if (n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 (bsr_local_top_k searches without a mask)");
     if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
         return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
@@ -1754,13 +1744,7 @@ int bsr_index::search_device_masked_groups(const float* queries, uint32_t nq, ui
                          (unsigned long long)allow_words, (unsigned long long)n, (unsigned long long)((n + 63) / 64));
     if (nq && !allow) return set_error(BSR_E_INVALID, "null allow masks");
     if (nq && !query_mask) return set_error(BSR_E_INVALID, "null query_mask");
-    BSR_HIP(hipSetDevice(ix->device));
-    stats = bsr_search_stats{};
-    stats.n_queries = nq;
-    stats.filter_op = 0;
-    stats.row_ebound = row_ebound;
-    stats.search_path = BSR_PATH_MASK_GROUPS;
-    BSR_TRY(prepare_result(nq, k));
+    BSR_TRY(begin_batch(ix, nq, k, BSR_PATH_MASK_GROUPS));
     if (nq == 0) return BSR_OK;
     if (!queries) return set_error(BSR_E_INVALID, "null queries");
 
@@ -1773,12 +1757,9 @@ int bsr_index::search_device_masked_groups(const float* queries, uint32_t nq, ui
     BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
     // The masks and the mask ids on the device; the ids on the host too (it forms the query groups).
     const uint64_t* dallow = allow;
-    if (allow_words && !is_device_ptr(allow)) {
-        const size_t bytes = (size_t)n_masks * allow_words * sizeof(uint64_t);
-        BSR_TRY(mask_dev.ensure(bytes));
-        BSR_HIP(hipMemcpyAsync(mask_dev.p, allow, bytes, hipMemcpyHostToDevice, stream));
-        dallow = mask_dev.as<uint64_t>();
-    }
+    if (allow_words)
+        BSR_TRY(on_device(ix, mask_dev, allow, (size_t)n_masks * allow_words * sizeof(uint64_t), is_device_ptr(allow),
+                          &dallow));
     const uint32_t* dqmask = query_mask;
     h_grp_qmask.resize(nq);
     if (is_device_ptr(query_mask)) {
@@ -1849,38 +1830,18 @@ int bsr_index::search_device_masked_groups(const float* queries, uint32_t nq, ui
         BSR_TRY(emit_pass(ix, nq, qpad, k, cap_m));
         uint32_t* raw_cnt = mask_aux.as<uint32_t>();
         uint32_t* items = raw_cnt + qpad;
-        BSR_HIP(launch_mask_cut_groups(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dallow, allow_words, dqmask,
-                                       dead_bits(), n, raw_cnt, items, stream));
-        ev_begin(ix, ev_rescore);
-        RescoreArgs rb = rescore_args(ix, nq, k);
-        rb.n_items_dev = items;
-        rb.qlist = reinterpret_cast<const uint32_t*>(qids_id.as<int32_t>());  // (identity for q < nq)
-        rescore_emitted(rb, ix, cap_m);
-        rb.fail_cnt = d_status + kStFail2;
-        rb.fail_list = fail2.as<uint32_t>();
-        rb.n_rows = min_a;  // (>= k: the count of every filter-group query is k)
-        rescore_bookkeeping(rb, ix, nq, raw_cnt);
-        BSR_HIP(launch_rescore(rb, stream));
-        ev_end(ix, ev_rescore);
-        next_status_clean = true;
-        ev_end(ix, ev_total);
-        // (with list-group queries the rows are read after their scan: the status words alone here)
-        BSR_HIP(hipMemcpyAsync(h_res, res[cur].p, n_list_q ? kStWords * sizeof(uint32_t) : res_bytes, hipMemcpyDeviceToHost,
-                               stream));
-        BSR_HIP(stream_wait(stream));
-        BSR_TRY(check_queries(ix, nq));
-        const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
-        stats.n_emitted = st[kStEmitted];
-        const uint32_t nfail = st[kStFail2];
+        BSR_HIP(launch_mask_cut(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dallow, allow_words, dqmask,
+                                dead_bits(), n, raw_cnt, items, stream));
+        // (n_rows = min_a >= k: the count of every filter-group query is k; with list-group queries
+        // the rows are read after their scan: the status words alone here)
+        uint32_t nfail = 0;
+        BSR_TRY(masked_filter_stage(ix, nq, k, raw_cnt, items, cap_m, min_a,
+                                    n_list_q ? kStWords * sizeof(uint32_t) : res_bytes, &nfail));
         if (!nfail && !n_list_q) return BSR_OK;
         if (nfail) {
             // Uncertified queries and queries the filter cannot serve join the list scan; the
             // list-group queries among them (empty lists: mode B fails them) are there already.
-            h_fail.resize(nfail);
-            h_qflags.resize(nq);
-            BSR_HIP(hipMemcpyAsync(h_fail.data(), fail2.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            BSR_HIP(hipMemcpyAsync(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            BSR_HIP(hipStreamSynchronize(stream));
+            BSR_TRY(read_failed(ix, nq, nfail));
             for (uint32_t q : h_fail) {
                 if (q >= nq || on_list[q]) continue;
                 on_list[q] = 1;
@@ -1914,11 +1875,7 @@ bool bsr_index::gtau_eligible(uint32_t nq, uint32_t k) const {
 int bsr_index::gtau_prepare(const float* queries, uint32_t nq, uint32_t k) {
     if (!gtau_eligible(nq, k)) return set_error(BSR_E_STATE, "global-threshold search not applicable");
     if (!queries) return set_error(BSR_E_INVALID, "null queries");
-    BSR_HIP(hipSetDevice(device));
-    stats = bsr_search_stats{};
-    stats.n_queries = nq;
-    stats.row_ebound = row_ebound;
-    BSR_TRY(prepare_result(nq, k));
+    BSR_TRY(begin_batch(this, nq, k));
     const uint32_t qpad = (uint32_t)round_up(nq, kFilterTile);
     const uint32_t ks = ks_for(k);
     BSR_TRY(query_buffers(this, nq, qpad, k));
@@ -2004,37 +1961,38 @@ static void collect_profile(bsr_index* ix) {
     ev_collect(ix->ev_total, p.search_ms, p.searches, 1);
 }
 
-int bsr_local_top_k_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx,
-                         float* out_dist, uint32_t* out_count) {
+// A local top-k entry point around its search: the null checks, the search, the results to the
+// caller's arrays, the profile.
+template <class F>
+static int top_k_call(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist, uint32_t* out_count,
+                      F&& search) {
     if (!ix) return set_error(BSR_E_INVALID, "null index");
     if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
-    BSR_TRY(ix->search_device(queries, nq, k));
+    BSR_TRY(search());
     BSR_TRY(copy_out(ix, nq, k, out_idx, out_dist, out_count));
     collect_profile(ix);
     return BSR_OK;
 }
 
+int bsr_local_top_k_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx,
+                         float* out_dist, uint32_t* out_count) {
+    return top_k_call(ix, nq, k, out_idx, out_dist, out_count, [&] { return ix->search_device(queries, nq, k); });
+}
+
 int bsr_local_top_k_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
                                 uint64_t allow_words, uint32_t mode, uint64_t* out_idx, float* out_dist,
                                 uint32_t* out_count) {
-    if (!ix) return set_error(BSR_E_INVALID, "null index");
-    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
-    BSR_TRY(ix->search_device_masked(queries, nq, k, allow, allow_words, mode));
-    BSR_TRY(copy_out(ix, nq, k, out_idx, out_dist, out_count));
-    collect_profile(ix);
-    return BSR_OK;
+    return top_k_call(ix, nq, k, out_idx, out_dist, out_count,
+                      [&] { return ix->search_device_masked(queries, nq, k, allow, allow_words, mode); });
 }
 
 int bsr_local_top_k_masked_groups_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k,
                                        const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                                        const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
                                        uint32_t* out_count) {
-    if (!ix) return set_error(BSR_E_INVALID, "null index");
-    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
-    BSR_TRY(ix->search_device_masked_groups(queries, nq, k, allow, allow_words, n_masks, query_mask, mode));
-    BSR_TRY(copy_out(ix, nq, k, out_idx, out_dist, out_count));
-    collect_profile(ix);
-    return BSR_OK;
+    return top_k_call(ix, nq, k, out_idx, out_dist, out_count, [&] {
+        return ix->search_device_masked_groups(queries, nq, k, allow, allow_words, n_masks, query_mask, mode);
+    });
 }
 
 int bsr_index_collect_profile_impl(bsr_index* ix) {

@@ -41,6 +41,9 @@ struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
     int ensure(size_t need);
+    // At least `need` bytes with the first `keep` bytes kept and zeros behind them: a new
+    // allocation takes the buffer's place once the copy is done (the stream is then idle).
+    int grow(size_t need, size_t keep, hipStream_t s);
     void release();
     template <class T> T* as() const { return static_cast<T*>(p); }
     ~DevBuf() { release(); }
@@ -55,6 +58,12 @@ hipError_t flag_wait(const uint32_t* flag, hipStream_t s);
 int select_device(int device);
 
 static inline uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
+// Rows of the fop_s sample operand of an n-row shard: every kSampleStride-th row, padded to whole
+// scale groups (at least one).
+static inline uint64_t sample_rows_pad(uint64_t n) {
+    const uint64_t n_s = (n + kSampleStride - 1) / kSampleStride;
+    return round_up(n_s ? n_s : 1, kSampleScaleRows);
+}
 
 struct Events {
     hipEvent_t a = nullptr, b = nullptr;
@@ -189,23 +198,22 @@ struct bsr_index {
 
     // Tombstones (bsr_index_delete): the bitset of deleted rows, allocated by the
     // first delete (ceil(n_pad / 64) words, zero beyond the deleted rows), and what is derived from it.
+    // Every mask kernel takes the bitset next to the allow mask and removes its rows as it reads.
     bsr::DevBuf dead;
     uint64_t n_dead = 0;     // deleted rows
     uint64_t dead_gen = 0;   // bumped by every delete that changes a row, and by a load that clears any
     bsr::DevBuf dead_ids;    // a delete's host ids on the device
     bsr::DevBuf dead_cnt;    // u32 [2]: ids out of range, rows newly deleted
-    bsr::DevBuf live_mask;   // ~dead: the live rows as an allow mask
-    bsr::DevBuf live_blk;    // its block offsets (launch_mask_list_count); during a delete, the bitset's own
+    bsr::DevBuf live_blk;    // the live rows' block offsets (launch_mask_list_count); during a delete, the bitset's own
     bsr::DevBuf live_list;   // u32 [live]: the live rows, ascending -- the exact fallback's row list
     bool live_list_ok = false;  // built since the last delete / append / load
-    bsr::DevBuf mask_eff;    // a masked search's allow & ~dead
     uint64_t live_rows() const { return n - n_dead; }
     const uint64_t* dead_bits() const { return n_dead ? dead.as<uint64_t>() : nullptr; }
     int delete_rows(const uint64_t* ids, uint64_t n_ids, uint64_t* out_deleted);
     int deleted_mask(uint64_t* out_words, uint64_t words) const;
     void clear_tombstones();        // load: every row live again
     int tombstones_after_append();  // the bitset grown to the new rows, the operand zeroed again
-    int ensure_live_list();         // live_list, built from ~dead when it is not there
+    int ensure_live_list();         // live_list, built from the bitset (no allow mask) when it is not there
 
     // In-place update (bsr_index_update): rows replaced by global id, the derived
     // state of their blocks rebuilt from lists.  A captured search graph bakes in nothing an update

@@ -495,17 +495,28 @@ __global__ __launch_bounds__(256) void k_header_publish(const int32_t* __restric
 }
 
 // ------------------------------------------------------------------------------------
-// Masked search: the allow mask as a list of row ids, and the emitted lists cut
-// by the mask.  Bit (i & 63) of word (i >> 6) allows local row i; bits at positions >= n are
-// ignored.  The list is built in three deterministic steps -- per-block popcounts (a block =
-// kMaskBlockWords words), one workgroup's exclusive scan of them, a scatter -- so the ids come
-// out ascending: the list scan then walks the slab front to back.
+// Mask bitsets: an allow mask as a list of row ids, and the emitted lists cut
+// by a mask.  Bit (i & 63) of word (i >> 6) allows local row i; bits at positions >= n are
+// ignored.  One family serves the masked search (one mask), the grouped masked search (n_masks
+// masks of `words` words each, gridDim.y or the query picking one), the live-row list (no allow
+// mask: every row) and the update's block bitsets; the index's tombstones (dead, nullable) are
+// taken out as the words are read -- no copy of a mask is ever made.  A list is built in three
+// deterministic steps -- per-block popcounts (a block = kMaskBlockWords words), one workgroup's
+// exclusive scan of them per mask, a scatter -- so the ids come out ascending: the list scan then
+// walks the slab front to back.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mask_word(const uint64_t* __restrict__ allow, uint64_t w, uint64_t n) {
+// The one reader of a bitset word: the rows of word w that are allowed (allow = nullptr: every
+// row < n) and not deleted (dead = nullptr: none is).
+__device__ __forceinline__ uint64_t mask_bits(const uint64_t* __restrict__ allow, const uint64_t* __restrict__ dead,
+                                              uint64_t w, uint64_t n) {
     const uint64_t lo = w * 64;
     if (lo >= n) return 0;
-    const uint64_t x = allow[w];
-    return n - lo >= 64 ? x : x & ((1ull << (n - lo)) - 1ull);
+    uint64_t x = allow ? allow[w] : ~0ull;
+    if (n - lo < 64) x &= (1ull << (n - lo)) - 1ull;
+    return dead && x ? x & ~dead[w] : x;
+}
+__device__ __forceinline__ const uint64_t* mask_of(const uint64_t* allow, uint64_t g, uint64_t words) {
+    return allow ? allow + g * words : nullptr;
 }
 
 // The workgroup's 256 per-thread counts: this thread's exclusive prefix, *total = their sum.
@@ -531,104 +542,24 @@ __device__ __forceinline__ uint32_t block_exclusive_256(uint32_t v, uint32_t* s_
     return before + inc - v;
 }
 
-__global__ __launch_bounds__(256) void k_mask_count(const uint64_t* __restrict__ allow, uint64_t n,
-                                                    uint32_t* __restrict__ blk) {
-    __shared__ uint32_t s_wave[4];
-    const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
-    uint32_t total;
-    (void)block_exclusive_256((uint32_t)__popcll(mask_word(allow, w, n)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
-}
-
-// blk[0..n_blk) -> their exclusive prefix sums, blk[n_blk] = the number of allowed rows.
-__global__ __launch_bounds__(256) void k_mask_scan(uint32_t* __restrict__ blk, uint32_t n_blk) {
-    __shared__ uint32_t s_wave[4];
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < n_blk; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_blk ? blk[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_256(v, s_wave, &total);
-        if (i < n_blk) blk[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) blk[n_blk] = carry;
-}
-
-__global__ __launch_bounds__(256) void k_mask_scatter(const uint64_t* __restrict__ allow, uint64_t n,
-                                                      const uint32_t* __restrict__ blk, uint32_t n_list,
-                                                      uint32_t* __restrict__ list) {
-    __shared__ uint32_t s_wave[4];
-    const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
-    uint64_t x = mask_word(allow, w, n);
-    uint32_t total;
-    uint32_t pos = blk[blockIdx.x] + block_exclusive_256((uint32_t)__popcll(x), s_wave, &total);
-    while (x) {
-        const uint32_t b = (uint32_t)__builtin_ctzll(x);
-        x &= x - 1;
-        if (pos < n_list) list[pos] = (uint32_t)(w * 64 + b);
-        ++pos;
-    }
-}
-
-// One wave per query: cand[q][0 .. cnt[q]) compacted in place to the keys whose row is allowed,
-// cnt[q] rewritten; raw[q] keeps the emitted count.  A chunk of 64 keys is read before anything
-// is written at or below it, so the compaction needs no second buffer.  An overflowed list
-// (cnt[q] > cap: rows were dropped) is left as it is -- it must stay overflowed.  *items = nq (the
-// device-counted rescore that follows reads its item count there).
-__global__ __launch_bounds__(256) void k_mask_cut(uint64_t* __restrict__ cand, uint32_t* __restrict__ cnt,
-                                                  uint32_t cap, uint32_t nq, const uint64_t* __restrict__ allow,
-                                                  uint64_t n, uint32_t* __restrict__ raw,
-                                                  uint32_t* __restrict__ items) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (blockIdx.x == 0 && threadIdx.x == 0) *items = nq;
-    if (q >= nq) return;
-    const uint32_t c = cnt[q];
-    if (lane == 0) raw[q] = c;
-    if (c > cap) return;
-    uint64_t* keys = cand + (uint64_t)q * cap;
-    uint32_t out = 0;
-    for (uint32_t base = 0; base < c; base += kWave) {
-        const uint32_t i = base + lane;
-        const uint64_t key = i < c ? keys[i] : kKeyNone;
-        const uint32_t row = key_row(key);
-        const bool keep = key != kKeyNone && row < n && ((allow[row >> 6] >> (row & 63)) & 1ull);
-        const uint64_t m = __ballot(keep);
-        if (keep) keys[out + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = key;
-        out += (uint32_t)__popcll(m);
-    }
-    if (lane == 0) cnt[q] = out;
-}
-
-// ------------------------------------------------------------------------------------
-// Grouped masked search: n_masks allow masks of `words` words each and a mask id
-// per query.  The kernels above with blockIdx.y (or the query) picking the mask, and the index's
-// tombstones taken out as the words are read (dead: nullable) -- no copy of the masks is made.
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t group_word(const uint64_t* __restrict__ allow, const uint64_t* __restrict__ dead,
-                                               uint64_t w, uint64_t n) {
-    const uint64_t x = mask_word(allow, w, n);
-    return dead && x ? x & ~dead[w] : x;
-}
-
 // blockIdx.y = the mask: blk[y * stride + blockIdx.x] = the block's allowed live rows.
-__global__ __launch_bounds__(256) void k_mask_groups_count(const uint64_t* __restrict__ allow, uint64_t words,
-                                                           uint64_t n, const uint64_t* __restrict__ dead,
-                                                           uint32_t* __restrict__ blk, uint32_t stride) {
+__global__ __launch_bounds__(256) void k_mask_count(const uint64_t* __restrict__ allow, uint64_t words, uint64_t n,
+                                                    const uint64_t* __restrict__ dead, uint32_t* __restrict__ blk,
+                                                    uint32_t stride) {
     __shared__ uint32_t s_wave[4];
     const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
     uint32_t total;
-    (void)block_exclusive_256((uint32_t)__popcll(group_word(allow + blockIdx.y * words, dead, w, n)), s_wave, &total);
+    (void)block_exclusive_256((uint32_t)__popcll(mask_bits(mask_of(allow, blockIdx.y, words), dead, w, n)), s_wave, &total);
     if (threadIdx.x == 0) blk[(uint64_t)blockIdx.y * stride + blockIdx.x] = total;
 }
 
-// blockIdx.x = the mask g < n_masks: k_mask_scan over its row of blk, out[g] = A_g.  The extra
-// workgroup blockIdx.x = n_masks counts the entries of query_mask that name no mask into
-// out[n_masks] (the host refuses the call before any kernel indexes a mask with one).
-__global__ __launch_bounds__(256) void k_mask_groups_scan(uint32_t* __restrict__ blk_all, uint32_t n_blk,
-                                                          uint32_t n_masks, const uint32_t* __restrict__ query_mask,
-                                                          uint32_t nq, uint32_t* __restrict__ out) {
+// blockIdx.x = the mask g < n_masks: its row of blk, blk[0 .. n_blk) -> their exclusive prefix sums,
+// blk[n_blk] = A_g, the number of its allowed rows, also out[g] (out nullable).  With a query_mask
+// the launch has one more workgroup, blockIdx.x = n_masks: it counts the entries of query_mask that
+// name no mask into out[n_masks] (the host refuses the call before any kernel indexes a mask with one).
+__global__ __launch_bounds__(256) void k_mask_scan(uint32_t* __restrict__ blk_all, uint32_t n_blk, uint32_t n_masks,
+                                                   const uint32_t* __restrict__ query_mask, uint32_t nq,
+                                                   uint32_t* __restrict__ out) {
     __shared__ uint32_t s_wave[4];
     uint32_t carry = 0;
     if (blockIdx.x == n_masks) {
@@ -652,20 +583,21 @@ __global__ __launch_bounds__(256) void k_mask_groups_scan(uint32_t* __restrict__
     }
     if (threadIdx.x == 0) {
         blk[n_blk] = carry;
-        out[blockIdx.x] = carry;
+        if (out) out[blockIdx.x] = carry;
     }
 }
 
-// blockIdx.y = the list: the ids of mask d[y].mask, ascending, at list + d[y].off.
-__global__ __launch_bounds__(256) void k_mask_groups_scatter(const uint64_t* __restrict__ allow, uint64_t words,
-                                                             uint64_t n, const uint64_t* __restrict__ dead,
-                                                             const uint32_t* __restrict__ blk, uint32_t stride,
-                                                             const MaskListDesc* __restrict__ d,
-                                                             uint32_t* __restrict__ list) {
+// blockIdx.y = the list: the first n_list ids of mask me.mask, ascending, at list + me.off, with
+// me = d[y], or -- d = nullptr, a single list -- the descriptor passed by value.
+__global__ __launch_bounds__(256) void k_mask_scatter(const uint64_t* __restrict__ allow, uint64_t words, uint64_t n,
+                                                      const uint64_t* __restrict__ dead,
+                                                      const uint32_t* __restrict__ blk, uint32_t stride,
+                                                      const MaskListDesc* __restrict__ d, MaskListDesc one,
+                                                      uint32_t* __restrict__ list) {
     __shared__ uint32_t s_wave[4];
-    const MaskListDesc me = d[blockIdx.y];
+    const MaskListDesc me = d ? d[blockIdx.y] : one;
     const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
-    uint64_t x = group_word(allow + (uint64_t)me.mask * words, dead, w, n);
+    uint64_t x = mask_bits(mask_of(allow, me.mask, words), dead, w, n);
     uint32_t total;
     uint32_t pos = blk[(uint64_t)me.mask * stride + blockIdx.x] + block_exclusive_256((uint32_t)__popcll(x), s_wave, &total);
     uint32_t* out = list + me.off;
@@ -677,12 +609,17 @@ __global__ __launch_bounds__(256) void k_mask_groups_scatter(const uint64_t* __r
     }
 }
 
-// k_mask_cut with the query's own mask, allow + query_mask[q] * words, less the deleted rows.
-__global__ __launch_bounds__(256) void k_mask_cut_groups(uint64_t* __restrict__ cand, uint32_t* __restrict__ cnt,
-                                                         uint32_t cap, uint32_t nq, const uint64_t* __restrict__ allow,
-                                                         uint64_t words, const uint32_t* __restrict__ query_mask,
-                                                         const uint64_t* __restrict__ dead, uint64_t n,
-                                                         uint32_t* __restrict__ raw, uint32_t* __restrict__ items) {
+// One wave per query: cand[q][0 .. cnt[q]) compacted in place to the keys whose row the query's
+// mask (query_mask[q]; query_mask = nullptr: mask 0 for every query) allows and no tombstone
+// removes, cnt[q] rewritten; raw[q] keeps the emitted count.  A chunk of 64 keys is read before
+// anything is written at or below it, so the compaction needs no second buffer.  An overflowed
+// list (cnt[q] > cap: rows were dropped) is left as it is -- it must stay overflowed.  *items = nq
+// (the device-counted rescore that follows reads its item count there).
+__global__ __launch_bounds__(256) void k_mask_cut(uint64_t* __restrict__ cand, uint32_t* __restrict__ cnt,
+                                                  uint32_t cap, uint32_t nq, const uint64_t* __restrict__ allow,
+                                                  uint64_t words, const uint32_t* __restrict__ query_mask,
+                                                  const uint64_t* __restrict__ dead, uint64_t n,
+                                                  uint32_t* __restrict__ raw, uint32_t* __restrict__ items) {
     const int lane = threadIdx.x & 63;
     const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x == 0 && threadIdx.x == 0) *items = nq;
@@ -690,15 +627,14 @@ __global__ __launch_bounds__(256) void k_mask_cut_groups(uint64_t* __restrict__ 
     const uint32_t c = cnt[q];
     if (lane == 0) raw[q] = c;
     if (c > cap) return;
-    const uint64_t* mine = allow + (uint64_t)query_mask[q] * words;
+    const uint64_t* mine = mask_of(allow, query_mask ? query_mask[q] : 0u, words);
     uint64_t* keys = cand + (uint64_t)q * cap;
     uint32_t out = 0;
     for (uint32_t base = 0; base < c; base += kWave) {
         const uint32_t i = base + lane;
         const uint64_t key = i < c ? keys[i] : kKeyNone;
         const uint32_t row = key_row(key);
-        bool keep = key != kKeyNone && row < n && ((mine[row >> 6] >> (row & 63)) & 1ull);
-        if (keep && dead) keep = !((dead[row >> 6] >> (row & 63)) & 1ull);
+        const bool keep = key != kKeyNone && ((mask_bits(mine, dead, row >> 6, n) >> (row & 63)) & 1ull);
         const uint64_t m = __ballot(keep);
         if (keep) keys[out + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = key;
         out += (uint32_t)__popcll(m);
@@ -763,7 +699,7 @@ __global__ __launch_bounds__(256) void k_dead_zero_fop(const uint64_t* __restric
     const uint32_t units = row_bytes / 16, ld = row_bytes;
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
     for (uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < words; w += (uint64_t)gridDim.x * 4) {
-        const uint64_t x0 = mask_word(dead, w, n);  // (wave-uniform)
+        const uint64_t x0 = mask_bits(dead, nullptr, w, n);  // (wave-uniform)
         if (!x0) continue;
         uint64_t x = x0;
         while (x) {
@@ -812,15 +748,6 @@ __global__ __launch_bounds__(256) void k_dead_zero_fop(const uint64_t* __restric
             }
         }
     }
-}
-
-// out[w] = allow[w] & ~dead[w] (allow = nullptr: ~dead[w], the live rows' mask) over the mask's
-// ceil(n / 64) words; the tail bits of the last word are left to the readers (mask_word).
-__global__ __launch_bounds__(256) void k_dead_andnot(const uint64_t* __restrict__ allow,
-                                                     const uint64_t* __restrict__ dead, uint64_t words,
-                                                     uint64_t* __restrict__ out) {
-    for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < words; w += (uint64_t)gridDim.x * blockDim.x)
-        out[w] = (allow ? allow[w] : ~0ull) & ~dead[w];
 }
 
 // ------------------------------------------------------------------------------------
@@ -1115,37 +1042,25 @@ hipError_t launch_dead_zero_fop(const uint64_t* dead, uint64_t n, const uint32_t
                        row_bytes, fop, fop_s, rows, dim, scales_s);
     return hipGetLastError();
 }
-hipError_t launch_dead_andnot(const uint64_t* allow, const uint64_t* dead, uint64_t n, uint64_t* out, hipStream_t s) {
-    const uint64_t words = (n + 63) / 64;
-    hipLaunchKernelGGL(k_dead_andnot, dim3(grid_for(words, 256, 2048)), dim3(256), 0, s, allow, dead, words, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_mask_list_count(const uint64_t* allow, uint64_t n, uint32_t* blk, hipStream_t s) {
-    const uint32_t n_blk = mask_blocks(n);
-    hipLaunchKernelGGL(k_mask_count, dim3(n_blk), dim3(256), 0, s, allow, n, blk);
-    hipLaunchKernelGGL(k_mask_scan, dim3(1), dim3(256), 0, s, blk, n_blk);
-    return hipGetLastError();
-}
-hipError_t launch_mask_list_scatter(const uint64_t* allow, uint64_t n, const uint32_t* blk, uint32_t n_list,
-                                    uint32_t* list, hipStream_t s) {
-    hipLaunchKernelGGL(k_mask_scatter, dim3(mask_blocks(n)), dim3(256), 0, s, allow, n, blk, n_list, list);
-    return hipGetLastError();
-}
 // (a grid's y extent is at most 65535: more masks or lists than that take a launch per 65535)
 constexpr uint32_t kGridYMax = 65535;
+static hipError_t mask_count(const uint64_t* allow, uint64_t words, uint32_t n_masks, uint64_t n, const uint64_t* dead,
+                             const uint32_t* query_mask, uint32_t nq, uint32_t* blk, uint32_t* out, hipStream_t s) {
+    const uint32_t n_blk = mask_blocks(n), stride = n_blk + 1;
+    for (uint32_t g0 = 0; g0 < n_masks; g0 += kGridYMax) {
+        const uint32_t g = n_masks - g0 < kGridYMax ? n_masks - g0 : kGridYMax;
+        hipLaunchKernelGGL(k_mask_count, dim3(n_blk, g), dim3(256), 0, s, allow ? allow + (uint64_t)g0 * words : nullptr,
+                           words, n, dead, blk + (uint64_t)g0 * stride, stride);
+    }
+    hipLaunchKernelGGL(k_mask_scan, dim3(n_masks + (query_mask ? 1u : 0u)), dim3(256), 0, s, blk, n_blk, n_masks,
+                       query_mask, nq, out);
+    return hipGetLastError();
+}
 hipError_t launch_mask_groups_count(const uint64_t* allow, uint64_t words, uint32_t n_masks, uint64_t n,
                                     const uint64_t* dead, const uint32_t* query_mask, uint32_t nq, uint32_t* blk,
                                     uint32_t* out, hipStream_t s) {
     if (!n_masks || words != (n + 63) / 64) return hipErrorInvalidValue;
-    const uint32_t n_blk = mask_blocks(n), stride = n_blk + 1;
-    for (uint32_t g0 = 0; g0 < n_masks; g0 += kGridYMax) {
-        const uint32_t g = n_masks - g0 < kGridYMax ? n_masks - g0 : kGridYMax;
-        hipLaunchKernelGGL(k_mask_groups_count, dim3(n_blk, g), dim3(256), 0, s, allow + (uint64_t)g0 * words, words, n,
-                           dead, blk + (uint64_t)g0 * stride, stride);
-    }
-    hipLaunchKernelGGL(k_mask_groups_scan, dim3(n_masks + 1), dim3(256), 0, s, blk, n_blk, n_masks, query_mask, nq, out);
-    return hipGetLastError();
+    return mask_count(allow, words, n_masks, n, dead, query_mask, nq, blk, out, s);
 }
 hipError_t launch_mask_groups_scatter(const uint64_t* allow, uint64_t words, uint64_t n, const uint64_t* dead,
                                       const uint32_t* blk, const MaskListDesc* d, uint32_t n_lists, uint32_t* list,
@@ -1153,21 +1068,28 @@ hipError_t launch_mask_groups_scatter(const uint64_t* allow, uint64_t words, uin
     const uint32_t n_blk = mask_blocks(n);
     for (uint32_t l0 = 0; l0 < n_lists; l0 += kGridYMax) {
         const uint32_t l = n_lists - l0 < kGridYMax ? n_lists - l0 : kGridYMax;
-        hipLaunchKernelGGL(k_mask_groups_scatter, dim3(n_blk, l), dim3(256), 0, s, allow, words, n, dead, blk,
-                           n_blk + 1, d + l0, list);
+        hipLaunchKernelGGL(k_mask_scatter, dim3(n_blk, l), dim3(256), 0, s, allow, words, n, dead, blk, n_blk + 1, d + l0,
+                           MaskListDesc{}, list);
     }
     return hipGetLastError();
 }
-hipError_t launch_mask_cut_groups(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
-                                  uint64_t words, const uint32_t* query_mask, const uint64_t* dead, uint64_t n,
-                                  uint32_t* raw, uint32_t* items, hipStream_t s) {
-    hipLaunchKernelGGL(k_mask_cut_groups, dim3((nq + 3) / 4), dim3(256), 0, s, cand, cnt, cap, nq, allow, words,
-                       query_mask, dead, n, raw, items);
+// One mask, one list: the same kernels, the list's descriptor a launch argument (no upload).
+hipError_t launch_mask_list_count(const uint64_t* allow, const uint64_t* dead, uint64_t n, uint32_t* blk,
+                                  hipStream_t s) {
+    return mask_count(allow, 0, 1, n, dead, nullptr, 0, blk, nullptr, s);
+}
+hipError_t launch_mask_list_scatter(const uint64_t* allow, const uint64_t* dead, uint64_t n, const uint32_t* blk,
+                                    uint32_t n_list, uint32_t* list, hipStream_t s) {
+    const uint32_t n_blk = mask_blocks(n);
+    hipLaunchKernelGGL(k_mask_scatter, dim3(n_blk), dim3(256), 0, s, allow, (uint64_t)0, n, dead, blk, n_blk + 1,
+                       static_cast<const MaskListDesc*>(nullptr), MaskListDesc{0, 0, n_list}, list);
     return hipGetLastError();
 }
 hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
-                           uint64_t n, uint32_t* raw, uint32_t* items, hipStream_t s) {
-    hipLaunchKernelGGL(k_mask_cut, dim3((nq + 3) / 4), dim3(256), 0, s, cand, cnt, cap, nq, allow, n, raw, items);
+                           uint64_t words, const uint32_t* query_mask, const uint64_t* dead, uint64_t n, uint32_t* raw,
+                           uint32_t* items, hipStream_t s) {
+    hipLaunchKernelGGL(k_mask_cut, dim3((nq + 3) / 4), dim3(256), 0, s, cand, cnt, cap, nq, allow, words, query_mask,
+                       dead, n, raw, items);
     return hipGetLastError();
 }
 

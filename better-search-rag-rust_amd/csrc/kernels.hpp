@@ -77,44 +77,44 @@ hipError_t launch_header_publish(const int32_t* src, uint32_t words, int32_t* ho
 hipError_t launch_gather_emulate(const void* send, const void* script, void* recv, uint64_t bytes, uint32_t P,
                                  uint32_t rank, hipStream_t s);
 
-// Masked search.  The allow mask: bit (i & 63) of word (i >> 6) allows local row
-// i; bits at positions >= n are ignored.  Its row list is built in two launches around the
-// host's read of the count: blk [mask_blocks(n) + 1] receives the exclusive prefix sums of the
-// per-block popcounts and, in its last word, the number of allowed rows A; the scatter then
-// writes the A ids in ascending order.
+// Mask bitsets, one kernel family.  An allow mask: bit (i & 63) of word (i >> 6)
+// allows local row i; bits at positions >= n are ignored; allow = nullptr allows every row < n.
+// dead (nullable): the index's bitset of deleted rows -- every kernel forms allow[w] & ~dead[w] as
+// it reads, no copy of a mask is made.  A mask's row list is built in two steps around the host's
+// read of the count: blk [mask_blocks(n) + 1] receives the exclusive prefix sums of the per-block
+// popcounts and, in its last word, the number of allowed live rows A (two launches); the scatter
+// then writes the first n_list of the A ids in ascending order.
 constexpr uint32_t kMaskBlockWords = 256;  // mask words per workgroup of the list build
 static inline uint32_t mask_blocks(uint64_t n) {
     const uint64_t words = (n + 63) / 64, b = (words + kMaskBlockWords - 1) / kMaskBlockWords;
     return (uint32_t)(b < 1 ? 1 : b);
 }
-hipError_t launch_mask_list_count(const uint64_t* allow, uint64_t n, uint32_t* blk, hipStream_t s);
-hipError_t launch_mask_list_scatter(const uint64_t* allow, uint64_t n, const uint32_t* blk, uint32_t n_list,
-                                    uint32_t* list, hipStream_t s);
-// The emitted lists cut by the mask: cand[q][0 .. cnt[q]) compacted in place to the keys of
-// allowed rows and cnt[q] rewritten (an overflowed list, cnt[q] > cap, is left overflowed);
-// raw[q] = the emitted count; *items = nq.
-hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
-                           uint64_t n, uint32_t* raw, uint32_t* items, hipStream_t s);
+hipError_t launch_mask_list_count(const uint64_t* allow, const uint64_t* dead, uint64_t n, uint32_t* blk,
+                                  hipStream_t s);
+hipError_t launch_mask_list_scatter(const uint64_t* allow, const uint64_t* dead, uint64_t n, const uint32_t* blk,
+                                    uint32_t n_list, uint32_t* list, hipStream_t s);
 
-// Grouped masked search: n_masks allow masks of `words` = ceil(n / 64) words each,
-// allow[g * words ..], and query_mask[q] < n_masks naming query q's.  dead (nullable): the index's
-// bitset of deleted rows -- every kernel forms allow_g[w] & ~dead[w] as it reads.
+// The same for n_masks allow masks of `words` = ceil(n / 64) words each, allow[g * words ..] (the
+// grouped masked search), and query_mask[q] < n_masks naming query q's.
 // The counts, two launches: blk[g * (mask_blocks(n) + 1) ..] receives mask g's exclusive block
-// prefixes; out[g] = A_g, the rows mask g allows, and out[n_masks] = the entries of
-// query_mask[0 .. nq) that name no mask (>= n_masks; no kernel indexes a mask with one).
+// prefixes; out[g] = A_g, the rows mask g allows, and -- query_mask given -- out[n_masks] = the
+// entries of query_mask[0 .. nq) that name no mask (>= n_masks; no kernel indexes a mask with one).
 hipError_t launch_mask_groups_count(const uint64_t* allow, uint64_t words, uint32_t n_masks, uint64_t n,
                                     const uint64_t* dead, const uint32_t* query_mask, uint32_t nq, uint32_t* blk,
                                     uint32_t* out, hipStream_t s);
-// One list per entry of d[0 .. n_lists): the ids of mask d[y].mask, ascending, at list + d[y].off
-// (d[y].n_list = A of that mask).
+// One list per entry of d[0 .. n_lists) (device): the first d[y].n_list ids of mask d[y].mask,
+// ascending, at list + d[y].off.
 struct MaskListDesc { uint64_t off; uint32_t mask, n_list; };
 hipError_t launch_mask_groups_scatter(const uint64_t* allow, uint64_t words, uint64_t n, const uint64_t* dead,
                                       const uint32_t* blk, const MaskListDesc* d, uint32_t n_lists, uint32_t* list,
                                       hipStream_t s);
-// launch_mask_cut with query q's own mask.
-hipError_t launch_mask_cut_groups(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
-                                  uint64_t words, const uint32_t* query_mask, const uint64_t* dead, uint64_t n,
-                                  uint32_t* raw, uint32_t* items, hipStream_t s);
+// The emitted lists cut by query q's mask, allow + query_mask[q] * words (query_mask = nullptr: mask
+// 0 for every query), less the deleted rows: cand[q][0 .. cnt[q]) compacted in place to the keys of
+// allowed live rows and cnt[q] rewritten (an overflowed list, cnt[q] > cap, is left overflowed);
+// raw[q] = the emitted count; *items = nq.
+hipError_t launch_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, const uint64_t* allow,
+                           uint64_t words, const uint32_t* query_mask, const uint64_t* dead, uint64_t n, uint32_t* raw,
+                           uint32_t* items, hipStream_t s);
 // A query group of the grouped list scan (launch_scan_list_groups): its list and its own queries.
 struct ScanGroupDesc { uint64_t off; uint32_t n_list, nq; };
 
@@ -131,12 +131,10 @@ hipError_t launch_dead_apply(const uint64_t* ids, uint64_t n_ids, uint64_t lo, u
 // live row whose rank among the live rows is a multiple of kSampleStride, or zeros when it has
 // none: the sample is the live rows thinned 1 in kSampleStride (rows: the f32 slab
 // [n_pad][row_bytes]; scales_s: the sample operand's scales, kept; dead_blk
-// [mask_blocks(n) + 1]: launch_mask_list_count over dead).  row_bytes = ld, a multiple of 64.
+// [mask_blocks(n) + 1]: launch_mask_list_count of dead as the mask).  row_bytes = ld, a multiple of 64.
 hipError_t launch_dead_zero_fop(const uint64_t* dead, uint64_t n, const uint32_t* dead_blk, uint32_t row_bytes,
                                 uint8_t* fop, uint8_t* fop_s, const float* rows, uint32_t dim, const float* scales_s,
                                 hipStream_t s);
-// out = allow & ~dead over the mask's ceil(n / 64) words (allow = nullptr: ~dead, the live rows).
-hipError_t launch_dead_andnot(const uint64_t* allow, const uint64_t* dead, uint64_t n, uint64_t* out, hipStream_t s);
 
 // In-place update (bsr_index_update): n_ids incoming rows src [n_ids][dim] (f32, or
 // bf16 bits) replace the slab rows ids[j] - lo.  Every kernel is driven by the ids or by a list

@@ -569,3 +569,147 @@ def synth_queries(rng, nq, qpad, row_bytes):
     sc = np.zeros(qpad, np.float32)
     sc[:nq] = np.exp(rng.uniform(np.log(1e-4), np.log(1e-1), nq)).astype(np.float32)
     return B, sc
+
+
+# ----------------------------------------------------------------------------------------
+# The mask bitsets (csrc/k_prep.hip: one kernel family for lists, counts and the cut)
+# ----------------------------------------------------------------------------------------
+MASK_BLOCK_WORDS = 256  # kMaskBlockWords (the GPU tests check it against the library's)
+LIST_DESC = np.dtype([("off", "<u8"), ("mask", "<u4"), ("n_list", "<u4")])  # MaskListDesc
+
+
+def mask_words(n):
+    return (n + 63) // 64
+
+
+def mask_blocks(n):
+    return max(1, (mask_words(n) + MASK_BLOCK_WORDS - 1) // MASK_BLOCK_WORDS)
+
+
+def pack_bits(bits):
+    """bool [n] -> u64 words, bit (i & 63) of word (i >> 6) = bits[i]; the tail bits zero."""
+    n = len(bits)
+    b = np.zeros(mask_words(n) * 64, np.uint8)
+    b[:n] = bits
+    return np.packbits(b, bitorder="little").view(np.uint64).copy()
+
+
+def mask_rows(allow, dead, n):
+    """The model of the one bitset reader: bool [n], row i allowed (allow None: every row) and not
+    deleted (dead None: none).  Bits at positions >= n are ignored."""
+    def unpack(w):
+        return np.unpackbits(np.ascontiguousarray(w).view(np.uint8), bitorder="little")[:n].astype(bool)
+    rows = np.ones(n, bool) if allow is None else unpack(allow)
+    return rows if dead is None else rows & ~unpack(dead)
+
+
+def mask_list_model(allow, dead, n):
+    """(blk [mask_blocks(n) + 1]: the exclusive prefix sums of the per-block counts, then A; the A ids
+    ascending)."""
+    ids = np.flatnonzero(mask_rows(allow, dead, n)).astype(np.uint32)
+    per = np.bincount(ids // (64 * MASK_BLOCK_WORDS), minlength=mask_blocks(n))
+    return np.concatenate(([0], np.cumsum(per))).astype(np.uint32), ids
+
+
+def mask_cut_model(keys, allow, dead, n):
+    """The keys of one list that survive the cut, in their order: not KEY_NONE, row < n, allowed, live."""
+    keys = np.asarray(keys, np.uint64)
+    rows = key_row(keys).astype(np.int64)
+    ok = mask_rows(allow, dead, n)
+    keep = (keys != KEY_NONE) & (rows < n)
+    keep[keep] = ok[rows[keep]]
+    return keys[keep]
+
+
+def _mask_lib():
+    L = lib()
+    L.kc_mask_block_words.restype = ctypes.c_uint32
+    L.kc_mask_blocks.restype = ctypes.c_uint32
+    L.kc_mask_blocks.argtypes = [ctypes.c_uint64]
+    return L
+
+
+def mask_count(allow, dead, n, n_masks=1, query_mask=None, grouped=False):
+    """launch_mask_list_count (grouped False) / launch_mask_groups_count.  Returns (blk
+    [n_masks][mask_blocks(n) + 1], out [n_masks + 1] or None); both start 0xFF-filled."""
+    L = _mask_lib()
+    words = mask_words(n)
+    assert allow is None or allow.size == n_masks * words
+    assert dead is None or dead.size == words
+    blk = np.full((n_masks, mask_blocks(n) + 1), 0xFFFFFFFF, np.uint32)
+    out = np.full(n_masks + 1, 0xFFFFFFFF, np.uint32) if grouped else None
+    nq = 0 if query_mask is None else len(query_mask)
+    _check(L.kc_mask_count(_p(_own(allow, np.uint64)), ctypes.c_uint64(words), ctypes.c_uint32(n_masks),
+                           ctypes.c_uint64(n), _p(_own(dead, np.uint64)), _p(_own(query_mask, np.uint32)),
+                           ctypes.c_uint32(nq), _p(blk), _p(out), ctypes.c_int(1 if grouped else 0)), "mask_count")
+    return blk, out
+
+
+def mask_scatter(allow, dead, n, blk, list_buf, n_list=0, descs=None):
+    """launch_mask_list_scatter (descs None: the first n_list ids at list_buf[0 ..]) /
+    launch_mask_groups_scatter over descs (LIST_DESC).  list_buf is written in place."""
+    L = _mask_lib()
+    n_masks = blk.shape[0]
+    n_lists = 0 if descs is None else len(descs)
+    if descs is not None:
+        assert descs.dtype == LIST_DESC and all(int(d["off"]) + int(d["n_list"]) <= len(list_buf) for d in descs)
+    else:
+        assert n_list <= len(list_buf)
+    _check(L.kc_mask_scatter(_p(_own(allow, np.uint64)), ctypes.c_uint64(mask_words(n)), ctypes.c_uint32(n_masks),
+                             ctypes.c_uint64(n), _p(_own(dead, np.uint64)), _p(_own(blk, np.uint32)), _p(descs),
+                             ctypes.c_uint32(n_lists), ctypes.c_uint32(n_list), _p(_own(list_buf, np.uint32)),
+                             ctypes.c_uint64(len(list_buf)), ctypes.c_int(0 if descs is None else 1)), "mask_scatter")
+
+
+def mask_cut(cand, cnt, nq, allow, n, n_masks=1, query_mask=None, dead=None):
+    """launch_mask_cut: cand [nq_buf][cap] and cnt [nq_buf] are written in place.  Returns (raw
+    [nq_buf], items), both 0xFF-filled before the launch."""
+    L = _mask_lib()
+    nq_buf, cap = cand.shape
+    assert len(cnt) == nq_buf and nq <= nq_buf and allow.size == n_masks * mask_words(n)
+    assert query_mask is None or (len(query_mask) == nq and int(query_mask.max()) < n_masks)
+    raw = np.full(nq_buf, 0xFFFFFFFF, np.uint32)
+    items = np.full(1, 0xFFFFFFFF, np.uint32)
+    _check(L.kc_mask_cut(_p(_own(cand, np.uint64)), _p(_own(cnt, np.uint32)), ctypes.c_uint32(cap), ctypes.c_uint32(nq),
+                         ctypes.c_uint32(nq_buf), _p(_own(allow, np.uint64)), ctypes.c_uint64(mask_words(n)),
+                         ctypes.c_uint32(n_masks), _p(_own(query_mask, np.uint32)), _p(_own(dead, np.uint64)),
+                         ctypes.c_uint64(n), _p(raw), _p(items)), "mask_cut")
+    return raw, int(items[0])
+
+
+# The cases of tests/test_gpu_kernels_mask.py (the CPU test of the models walks the small ones).
+MASK_NS = (1, 63, 64, 65, 16384, 16385, 2 * 16384 + 100, 257 * 16384 + 5)
+MASK_KINDS = ("empty", "full", "half", "last", "garbage", "none")
+DEAD_KINDS = ("none", "random", "superset")
+
+
+def mask_case(n, kind, seed=0):
+    """An allow mask of `kind` over n rows (u64 words, or None for kind "none").  "garbage": a random
+    mask whose last word is filled at the positions >= n, which every reader must ignore."""
+    rng = np.random.default_rng(1000 + 7 * seed + n % 9973)
+    if kind == "none":
+        return None
+    if kind == "empty":
+        return pack_bits(np.zeros(n, bool))
+    if kind == "full":
+        return pack_bits(np.ones(n, bool))
+    if kind == "last":
+        bits = np.zeros(n, bool)
+        bits[n - 1] = True
+        return pack_bits(bits)
+    w = pack_bits(rng.random(n) < 0.5)
+    if kind == "garbage" and n % 64:
+        w[-1] |= np.uint64(0xFFFFFFFFFFFFFFFF) << np.uint64(n % 64)
+    return w
+
+
+def dead_case(n, kind, allow, seed=0):
+    """A bitset of deleted rows (None: no tombstones).  "superset": every allowed row and a random
+    half of the others (allow None: every row), so that no row is left.  No bit at a position >= n."""
+    rng = np.random.default_rng(2000 + 7 * seed + n % 9973)
+    if kind == "none":
+        return None
+    bits = rng.random(n) < 0.5
+    if kind == "superset":
+        bits |= mask_rows(allow, None, n)
+    return pack_bits(bits)

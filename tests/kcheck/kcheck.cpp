@@ -228,4 +228,65 @@ int kc_select_cand(const uint64_t* cand, const uint32_t* cnt, uint32_t cap, uint
     return b.finish(r);
 }
 
+// ---- the mask bitsets (one kernel family: lists, counts, the cut) --------------------------------
+uint32_t kc_mask_block_words() { return bsr::kMaskBlockWords; }
+uint32_t kc_mask_blocks(uint64_t n) { return bsr::mask_blocks(n); }
+
+// allow [n_masks][words] (nullptr: every row), dead [words] (nullptr: none), words = ceil(n / 64);
+// blk [n_masks][mask_blocks(n) + 1].  grouped = 0: launch_mask_list_count (n_masks = 1; query_mask
+// and out are not used); else launch_mask_groups_count with query_mask [nq] (nullable) and
+// out [n_masks + 1].
+int kc_mask_count(const uint64_t* allow, uint64_t words, uint32_t n_masks, uint64_t n, const uint64_t* dead,
+                  const uint32_t* query_mask, uint32_t nq, uint32_t* blk, uint32_t* out, int grouped) {
+    Bufs b;
+    const uint64_t* d_allow = b.in(allow, (size_t)n_masks * words * sizeof(uint64_t));
+    const uint64_t* d_dead = b.in(dead, words * sizeof(uint64_t));
+    const uint32_t* d_qm = b.in(query_mask, nq * sizeof(uint32_t));
+    uint32_t* d_blk = b.io(blk, (size_t)n_masks * (bsr::mask_blocks(n) + 1) * sizeof(uint32_t));
+    uint32_t* d_out = b.io(out, ((size_t)n_masks + 1) * sizeof(uint32_t));
+    hipError_t r = hipSuccess;
+    if (b.err == hipSuccess)
+        r = grouped ? bsr::launch_mask_groups_count(d_allow, words, n_masks, n, d_dead, d_qm, nq, d_blk, d_out, nullptr)
+                    : bsr::launch_mask_list_count(d_allow, d_dead, n, d_blk, nullptr);
+    return b.finish(r);
+}
+
+// blk as kc_mask_count left it; list [list_words].  grouped = 0: launch_mask_list_scatter writes the
+// first n_list ids at list[0 ..]; else launch_mask_groups_scatter with the n_lists descriptors d
+// (MaskListDesc: u64 off, u32 mask, u32 n_list), uploaded here.
+int kc_mask_scatter(const uint64_t* allow, uint64_t words, uint32_t n_masks, uint64_t n, const uint64_t* dead,
+                    const uint32_t* blk, const void* d, uint32_t n_lists, uint32_t n_list, uint32_t* list,
+                    uint64_t list_words, int grouped) {
+    Bufs b;
+    const uint64_t* d_allow = b.in(allow, (size_t)n_masks * words * sizeof(uint64_t));
+    const uint64_t* d_dead = b.in(dead, words * sizeof(uint64_t));
+    const uint32_t* d_blk = b.in(blk, (size_t)n_masks * (bsr::mask_blocks(n) + 1) * sizeof(uint32_t));
+    const bsr::MaskListDesc* d_d = static_cast<const bsr::MaskListDesc*>(b.in(d, n_lists * sizeof(bsr::MaskListDesc)));
+    uint32_t* d_list = b.io(list, list_words * sizeof(uint32_t));
+    hipError_t r = hipSuccess;
+    if (b.err == hipSuccess)
+        r = grouped ? bsr::launch_mask_groups_scatter(d_allow, words, n, d_dead, d_blk, d_d, n_lists, d_list, nullptr)
+                    : bsr::launch_mask_list_scatter(d_allow, d_dead, n, d_blk, n_list, d_list, nullptr);
+    return b.finish(r);
+}
+
+// cand [nq_buf][cap], cnt / raw [nq_buf] (nq_buf >= nq), items one word; allow [n_masks][words];
+// query_mask [nq] (nullptr: mask 0 for every query); dead [words] (nullable).
+int kc_mask_cut(uint64_t* cand, uint32_t* cnt, uint32_t cap, uint32_t nq, uint32_t nq_buf, const uint64_t* allow,
+                uint64_t words, uint32_t n_masks, const uint32_t* query_mask, const uint64_t* dead, uint64_t n,
+                uint32_t* raw, uint32_t* items) {
+    Bufs b;
+    uint64_t* d_cand = b.io(cand, (size_t)nq_buf * cap * sizeof(uint64_t));
+    uint32_t* d_cnt = b.io(cnt, nq_buf * sizeof(uint32_t));
+    const uint64_t* d_allow = b.in(allow, (size_t)n_masks * words * sizeof(uint64_t));
+    const uint32_t* d_qm = b.in(query_mask, nq * sizeof(uint32_t));
+    const uint64_t* d_dead = b.in(dead, words * sizeof(uint64_t));
+    uint32_t* d_raw = b.io(raw, nq_buf * sizeof(uint32_t));
+    uint32_t* d_items = b.io(items, sizeof(uint32_t));
+    hipError_t r = hipSuccess;
+    if (b.err == hipSuccess)
+        r = bsr::launch_mask_cut(d_cand, d_cnt, cap, nq, d_allow, words, d_qm, d_dead, n, d_raw, d_items, nullptr);
+    return b.finish(r);
+}
+
 }  // extern "C"

@@ -206,3 +206,58 @@ def test_planted_row_is_the_worst_row():
             for plant in kc.plant_positions(n):
                 _, _, e = kc.quantize(kc.prep_rows(n, dim, plant), 32)
                 assert int(np.argmax(e)) == plant, (dim, n, plant)
+
+
+# ---- the mask bitsets ----------------------------------------------------------------------
+def _bit(words, i):
+    return (int(words[i >> 6]) >> (i & 63)) & 1
+
+
+def _rows_by_loop(allow, dead, n):
+    return [i for i in range(n)
+            if (allow is None or _bit(allow, i)) and not (dead is not None and _bit(dead, i))]
+
+
+@pytest.mark.parametrize("n", [n for n in kc.MASK_NS if n <= 2 * 16384 + 100])
+def test_mask_list_model_against_a_loop(n):
+    """mask_rows / mask_list_model (np.unpackbits) against a bit-by-bit loop: every mask kind and
+    dead kind of the GPU test, the block prefixes included."""
+    rows_per_block = 64 * kc.MASK_BLOCK_WORDS
+    for kind in kc.MASK_KINDS:
+        allow = kc.mask_case(n, kind)
+        if kind == "garbage" and n % 64:
+            assert int(allow[-1]) >> (n % 64) == (1 << (64 - n % 64)) - 1  # test data: the tail is set
+        for dkind in kc.DEAD_KINDS:
+            dead = kc.dead_case(n, dkind, allow)
+            want = _rows_by_loop(allow, dead, n)
+            blk, ids = kc.mask_list_model(allow, dead, n)
+            assert ids.dtype == np.uint32 and ids.tolist() == want, (kind, dkind)
+            assert len(blk) == kc.mask_blocks(n) + 1 and blk[-1] == len(want)
+            for b in range(kc.mask_blocks(n)):
+                assert blk[b] == sum(1 for i in want if i < b * rows_per_block), (kind, dkind, b)
+            if dkind == "superset":
+                assert not want
+            if kind == "last" and dkind == "none":
+                assert want == [n - 1]
+            if kind in ("full", "none") and dkind == "none":
+                assert want == list(range(n))
+
+
+def test_mask_blocks_and_pack_bits_by_hand():
+    assert [kc.mask_blocks(n) for n in (0, 1, 16384, 16385, 257 * 16384 + 5)] == [1, 1, 1, 2, 258]
+    w = kc.pack_bits(np.array([1, 0, 1] + [0] * 61 + [1], bool))
+    assert w.tolist() == [5, 1]
+
+
+def test_mask_cut_model_against_a_loop():
+    n = 100
+    allow = kc.mask_case(n, "garbage", seed=4)
+    dead = kc.dead_case(n, "random", None, seed=5)
+    rows = [0, 99, 100, 127, 128, 5000, 0xFFFFFFFE, 17, 17, 64, 63]
+    keys = np.array([((i + 1) << 32) | r for i, r in enumerate(rows)] + [int(kc.KEY_NONE)], np.uint64)
+    for d in (None, dead):
+        want = [int(k) for k in keys
+                if int(k) != int(kc.KEY_NONE) and (int(k) & 0xFFFFFFFF) < n
+                and _bit(allow, int(k) & 0xFFFFFFFF) and not (d is not None and _bit(d, int(k) & 0xFFFFFFFF))]
+        assert kc.mask_cut_model(keys, allow, d, n).tolist() == want
+    assert kc.mask_cut_model(keys[:0], allow, None, n).tolist() == []
