@@ -58,6 +58,9 @@ BSR_PATH_TOP_RERUN = 64
 BSR_PATH_MASK_LIST = 128    # masked search: exact top-k over the allowed-row list
 BSR_PATH_MASK_FILTER = 256  # masked search: int8 filter, emitted lists cut by the mask
 BSR_PATH_MASK_GROUPS = 512  # bsr_local_top_k_masked_groups ran (with the MASK_LIST / MASK_FILTER bits)
+BSR_PATH_RANGE = 1024       # bsr_local_range_search ran
+BSR_PATH_RANGE_SCAN = 2048  # ... and a query of the batch was answered by the exact range scan
+BSR_RANGE_MAX_RESULTS = 4096  # result slots per query of a range search (include/bsr.h)
 BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
 BSR_MASK_LIST = 1
 BSR_MASK_FILTER = 2
@@ -141,6 +144,7 @@ def lib() -> ctypes.CDLL:
         "bsr_local_top_k":(ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, _P, _P]),
         "bsr_local_top_k_masked_groups": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
+        "bsr_local_range_search": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
         "bsr_comm_init": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(_P)]),
@@ -163,7 +167,7 @@ def lib() -> ctypes.CDLL:
     }
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
-                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact"}
+                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -550,6 +554,40 @@ class Index:
         nw = int(allow_words.numel()) if hasattr(allow_words, "numel") else int(allow_words.size)
         _check(lib().bsr_local_top_k_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), nw,
                                             _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_count)))
+
+    def range_search(self, queries, radius, max_results: int = 256):
+        """Every live row within a distance of each query (bsr_local_range_search) -> (idx [Q,cap]
+        u64, dist [Q,cap] f32, count [Q] u32) with cap = max_results.  radius: a scalar for the
+        whole batch or one value per query.  count[q] is always the exact number of rows with
+        distance <= radius[q]; when it exceeds max_results, row q holds only padding (~0, +inf) --
+        call again with more slots or a smaller radius."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
+        nq = q.shape[0]
+        r = np.asarray(radius, np.float32)
+        if r.ndim == 0:
+            r = np.full(nq, r, np.float32)
+        r = np.ascontiguousarray(r.reshape(-1))
+        if r.size != nq:
+            raise BsrError(-1, f"radius has {r.size} entries for {nq} queries")
+        cap = int(max_results)
+        if cap < 1 or cap > BSR_RANGE_MAX_RESULTS:
+            raise BsrError(-1, f"max_results={cap} outside [1, {BSR_RANGE_MAX_RESULTS}]")
+        oi = np.empty((nq, cap), np.uint64)
+        od = np.empty((nq, cap), np.float32)
+        oc = np.empty(nq, np.uint32)
+        _check(lib().bsr_local_range_search(self._h, _ptr(q), nq, _ptr(r), cap, _ptr(oi), _ptr(od), _ptr(oc)))
+        return oi, od, oc
+
+    def range_search_device(self, queries, nq: int, radius, max_results: int, out_idx, out_dist, out_count):
+        """Zero-copy variant of range_search on caller buffers (torch tensors, numpy arrays or raw
+        pointers, each host or device): queries [nq][dim] f32, radius [nq] f32, out_idx / out_dist
+        [nq][max_results], out_count [nq]."""
+        _check(lib().bsr_local_range_search(self._h, _ptr(queries), nq, _ptr(radius), max_results, _ptr(out_idx),
+                                            _ptr(out_dist), _ptr(out_count)))
 
     def _allow_group_words(self, allow_masks):
         """(buffer, masks, words per mask) of a grouped search's allow masks: a bool array [G][n]

@@ -1995,6 +1995,152 @@ int bsr_local_top_k_masked_groups_impl(bsr_index* ix, const float* queries, uint
     });
 }
 
+// ---------------------------------------------------------------------------------------
+// Range search (bsr_local_range_search)
+// ---------------------------------------------------------------------------------------
+// The exact range scan of n_ids queries (device id list in groups of kScanQF, the last group padded
+// with valid ids, as run_exact_scan's): every row of the shard, the deleted ones skipped by their bit.
+static int run_range_scan(bsr_index* ix, RangeArgs ra, const int32_t* ids, uint32_t n_ids) {
+    const uint32_t grid = scan_grid_for(ix->n);
+    ev_begin(ix, ix->ev_scan, 1);
+    for (uint32_t g = 0; g * kScanQF < n_ids; ++g) {
+        ra.qids = ids + (size_t)g * kScanQF;
+        ra.nqf = std::min(kScanQF, n_ids - g * kScanQF);
+        BSR_HIP(launch_range_scan(ra, grid, ix->stream));
+    }
+    ev_end(ix, ix->ev_scan);
+    return BSR_OK;
+}
+
+int bsr_index::range_search_device(const float* queries, uint32_t nq, const float* radius, uint32_t capacity,
+                                   uint64_t* out_idx, float* out_dist, uint32_t* out_count) {
+    bsr_index* ix = this;
+    BSR_TRY(check_batch(ix, 1));
+    // (host radii: a NaN is refused before any device work; device radii are checked by the
+    // threshold kernel, and nothing is written to the caller's arrays before the status is read)
+    const bool radius_dev = is_device_ptr(radius);
+    if (!radius_dev)
+        for (uint32_t q = 0; q < nq; ++q)
+            if (radius[q] != radius[q]) return set_error(BSR_E_INVALID, "radius[%u] is NaN", q);
+    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_RANGE));
+    if (nq == 0) return BSR_OK;
+
+    const uint32_t cap = range_cap(capacity);
+    const uint32_t qpad = qpad_for(nq);
+    BSR_TRY(query_buffers(ix, nq, qpad, 1));
+    BSR_TRY(filter_buffers(ix, nq, qpad, 1, cap));
+    stats.n_candidates = 0;
+    BSR_TRY(rng_keys.ensure((size_t)nq * cap * sizeof(uint64_t)));
+    BSR_TRY(rng_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_TRY(rng_idx.ensure((size_t)nq * capacity * sizeof(uint64_t)));
+    BSR_TRY(rng_dist.ensure((size_t)nq * capacity * sizeof(float)));
+    BSR_TRY(rng_out_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
+    const float* rsrc = nullptr;
+    BSR_TRY(on_device(ix, rng_radius, radius, (size_t)nq * sizeof(float), radius_dev, &rsrc));
+    // An index that cannot filter scans every query: no int8 operand worth a threshold
+    // (BSR_FLAG_EXACT_ONLY, sticky norm flags), or no more rows than one emitted list holds.
+    const uint64_t live = live_rows();
+    const bool use_filter = live > 0 && approx_ok && n > cap;
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, use_filter), stream));
+    // (the thresholds; in every mode: the zeroed counts and the device check of the radii)
+    BSR_HIP(launch_range_tau(rsrc, ebound.as<float>(), nb.as<float>(), qflags.as<uint32_t>(), nq, qpad,
+                             tau.as<float>(), cnt.as<uint32_t>(), rng_cnt.as<uint32_t>(), fail.as<uint32_t>(), d_status,
+                             stream));
+    RangeArgs ra{};
+    ra.rows = rows.as<float>();
+    ra.ld = ld;
+    ra.dim = dim;
+    ra.n = n;
+    ra.na = na.as<float>();
+    ra.qf32 = qf32.as<float>();
+    ra.nb = nb.as<float>();
+    ra.radius = rsrc;
+    ra.dead = dead_bits();
+    ra.keys = rng_keys.as<uint64_t>();
+    ra.rcnt = rng_cnt.as<uint32_t>();
+    ra.cap = cap;
+    ra.nq = nq;
+    ra.cand = cand.as<uint64_t>();
+    ra.cnt = cnt.as<uint32_t>();
+    ra.scan_list = fail.as<uint32_t>();
+    ra.status = d_status;
+    if (use_filter) {
+        // the emit pass over every tile (no sample pass ran: no sample tiles to skip, no fix-up),
+        // then the exact rescore of every emitted row against the radius
+        smp_tiles = 0;
+        BSR_TRY(emit_pass(ix, nq, qpad, 1, cap));
+        ev_begin(ix, ev_rescore);
+        BSR_HIP(launch_range_rescore(ra, stream));
+        ev_end(ix, ev_rescore);
+    } else if (live > 0) {
+        stats.n_exact_direct = nq;
+        stats.search_path |= BSR_PATH_RANGE_SCAN;
+        BSR_TRY(run_range_scan(ix, ra, qids_id.as<int32_t>(), nq));
+    }
+    // The one status readback: the query flags (a non-finite query, a NaN radius) and the number
+    // of queries left to the scan.
+    BSR_HIP(hipMemcpyAsync(h_res, d_status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BSR_HIP(stream_wait(stream));
+    BSR_TRY(check_queries(ix, nq));
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+    if (st[kStQueryFlags] & kRangeNanRadius) return set_error(BSR_E_INVALID, "a radius of the batch is NaN");
+    if (use_filter) {
+        stats.n_emitted = st[kStEmitted];
+        const uint32_t nscan = st[kStFail], ndirect = st[kStFail2];
+        stats.n_exact_direct = ndirect;
+        stats.n_fallback = nscan - ndirect;
+        if (nscan) {
+            // queries the filter cannot serve, and queries whose emitted list overflowed
+            stats.search_path |= BSR_PATH_RANGE_SCAN;
+            h_fail.resize(nscan);
+            BSR_HIP(hipMemcpy(h_fail.data(), fail.p, (size_t)nscan * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            std::sort(h_fail.begin(), h_fail.end());
+            std::vector<int32_t> padded(round_up(nscan, kScanQF));
+            for (size_t i = 0; i < padded.size(); ++i)
+                padded[i] = (int32_t)(i < nscan ? h_fail[i] : h_fail[i / kScanQF * kScanQF]);
+            BSR_TRY(qids.ensure(padded.size() * sizeof(int32_t)));
+            BSR_HIP(hipMemcpyAsync(qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   stream));
+            BSR_HIP(hipStreamSynchronize(stream));  // (padded is read by the copy)
+            BSR_TRY(run_range_scan(ix, ra, qids.as<int32_t>(), nscan));
+        }
+    }
+    // The lists sorted into result rows: straight into the caller's arrays when all three are on
+    // the device, else into the index's own and copied out.
+    const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count);
+    uint64_t* di = out_dev ? out_idx : rng_idx.as<uint64_t>();
+    float* dd = out_dev ? out_dist : rng_dist.as<float>();
+    uint32_t* dc = out_dev ? out_count : rng_out_cnt.as<uint32_t>();
+    BSR_HIP(launch_range_finish(rng_keys.as<uint64_t>(), rng_cnt.as<uint32_t>(), cap, nq, capacity, global_offset, di,
+                                dd, dc, stream));
+    ev_end(ix, ev_total);
+    if (!out_dev) {
+        const size_t nk = (size_t)nq * capacity;
+        BSR_HIP(hipMemcpyAsync(out_idx, di, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, dd, nk * sizeof(float), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, dc, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_range_search_impl(bsr_index* ix, const float* queries, uint32_t nq, const float* radius,
+                                uint32_t capacity, uint64_t* out_idx, float* out_dist, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (capacity == 0 || capacity > BSR_RANGE_MAX_RESULTS)
+        return set_error(BSR_E_INVALID, "capacity=%u outside [1, %u]", capacity, BSR_RANGE_MAX_RESULTS);
+    if (nq && !radius) return set_error(BSR_E_INVALID, "null radius");
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    BSR_TRY(ix->range_search_device(queries, nq, radius, capacity, out_idx, out_dist, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
 int bsr_index_collect_profile_impl(bsr_index* ix) {
     collect_profile(ix);
     return BSR_OK;

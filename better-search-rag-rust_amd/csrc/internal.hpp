@@ -234,6 +234,17 @@ struct bsr_index {
     bsr::DevBuf cmp_stage;  // f32 [chunk rows][ld]: BSR_COMPACT_STAGE_BYTES (read per call), kept
     bsr::DevBuf cmp_first;  // u32: the first row that moves
 
+    // Range search (bsr_local_range_search): every live row within radius[q] of
+    // query q, `capacity` result slots per query.  Launched directly, never captured; its result
+    // rows go to buffers of its own (the packed result of begin_batch carries only its status
+    // words), and from there to the caller's arrays, host or device.
+    int range_search_device(const float* queries, uint32_t nq, const float* radius, uint32_t capacity,
+                            uint64_t* out_idx, float* out_dist, uint32_t* out_count);
+    bsr::DevBuf rng_radius;  // f32 [nq]: a host radius array's device copy
+    bsr::DevBuf rng_keys;    // u64 [nq][range_cap(capacity)]: the in-range distance keys, any order
+    bsr::DevBuf rng_cnt;     // u32 [nq]: their exact counts
+    bsr::DevBuf rng_idx, rng_dist, rng_out_cnt;  // the result rows [nq][capacity], the counts [nq]
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

@@ -1589,6 +1589,305 @@ __global__ void k_cosine_pair(const float* __restrict__ a, uint32_t la, const fl
 }
 
 // ------------------------------------------------------------------------------------
+// Range search (bsr_local_range_search): every live row within a distance of the
+// query.  The emission threshold is solved from the radius through exclusion_bound() before the
+// filter runs, so the emitted rows are a superset of the answer; the emitted rows are rescored
+// with the reference's arithmetic, a query whose list overflowed (or that cannot filter) is
+// scanned exactly, and one kernel sorts a query's list into its result rows.
+// ------------------------------------------------------------------------------------
+// The largest f32 threshold t (to within the few ulps the settle loops walk) with
+// exclusion_bound(t, E_q, |b|) > r: a row the filter does not emit at t has a reference distance
+// of at least that bound.  In double, as exclusion_bound computes: the bound rounded down to f32
+// exceeds r iff ((1 - t) - E_q) - 2.5e-7 >= the f32 after r, and its identical-row clause wants
+// t < ((1 - E_q) - 1e-4) - 6e-9 / |b|.  The candidate from those two is then settled against
+// exclusion_bound itself (it is what certifies), up first, then down.  +inf: no positive
+// threshold does it -- a threshold at or below zero would admit about half of a centred corpus
+// and every deleted row (their zeroed operand scores exactly 0) -- and the query is scanned.
+__device__ __forceinline__ float range_threshold(float r, float ebound_q, float mag_b) {
+    const double eb = (double)ebound_q;
+    const float rn = nextafterf(r, INFINITY);
+    const double td = ((1.0 - (double)rn) - eb) - 2.5e-7;
+    const double lim = ((1.0 - eb) - 1e-4) - 6e-9 / (double)mag_b;
+    float t = (float)td;
+    if ((double)t > td) t = nextafterf(t, -INFINITY);
+    float tl = (float)lim;
+    if (!((double)tl < lim)) tl = nextafterf(tl, -INFINITY);
+    t = fminf(t, tl);
+    if (!(t > 0.0f)) return INFINITY;
+    for (int i = 0; i < 4; ++i) {
+        const float up = nextafterf(t, INFINITY);
+        if (!(exclusion_bound(up, ebound_q, mag_b) > r)) break;
+        t = up;
+    }
+    for (int i = 0; i < 8; ++i) {
+        if (!(t > 0.0f)) return INFINITY;
+        if (exclusion_bound(t, ebound_q, mag_b) > r) return t;
+        t = nextafterf(t, -INFINITY);
+    }
+    return INFINITY;
+}
+
+// One workgroup for the batch (a few double operations per query): the zeroing k_select_tau does
+// for the emit pass, the thresholds, and the list of the queries the scan answers by design.  The
+// list is counted in LDS, so the status words are each written once, by thread 0.
+__global__ __launch_bounds__(1024) void k_range_tau(const float* __restrict__ radius,
+                                                    const float* __restrict__ ebound,
+                                                    const float* __restrict__ nb,
+                                                    const uint32_t* __restrict__ qflags, uint32_t nq,
+                                                    uint32_t qpad, float* __restrict__ tau,
+                                                    uint32_t* __restrict__ cnt, uint32_t* __restrict__ rcnt,
+                                                    uint32_t* __restrict__ scan_list,
+                                                    uint32_t* __restrict__ status) {
+    __shared__ uint32_t s_scan, s_nan;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) { s_scan = 0; s_nan = 0; }
+    // (the per-query counters, the emit filter's tail counters and gang words)
+    for (uint32_t i = t; i < qpad + 8 * kTailCounters + kGangWords; i += blockDim.x) cnt[i] = 0;
+    for (uint32_t i = t; i < nq; i += blockDim.x) rcnt[i] = 0;
+    __syncthreads();
+    for (uint32_t q = t; q < qpad; q += blockDim.x) {
+        float tq = INFINITY;  // padding, radius < 0, NaN: emits nothing, no scan
+        if (q < nq) {
+            const float r = radius[q];
+            if (r != r) {
+                s_nan = 1u;
+            } else if (r >= 0.0f) {
+                const float eb = ebound[q];
+                if (!(qflags[q] & kQueryNoApprox) && eb < 1.0f) tq = range_threshold(r, eb, nb[q]);
+                if (!(tq < INFINITY)) scan_list[atomicAdd(&s_scan, 1u)] = q;
+            }
+        }
+        tau[q] = tq;
+    }
+    __syncthreads();
+    if (t == 0) {
+        status[kStFail] = s_scan;
+        status[kStEmitted] = 0;
+        status[kStFail2] = s_scan;
+        if (s_nan) atomicOr(status + kStQueryFlags, kRangeNanRadius);
+    }
+}
+
+// One workgroup of four waves per query; wave w takes the emitted keys w*64 + lane, + 256, ...:
+// its 64 rows go chunk by chunk through its own LDS stage (load_cand_chunk, two chunks in flight)
+// and each lane walks its row in index order (seq_chunk, finish_distance) against the query's LDS
+// copy -- the arithmetic of k_rescore.  The in-range live rows claim the slots of the query's list
+// from a counter in LDS, a wave at a time.
+__global__ __launch_bounds__(256) void k_range_rescore(RangeArgs a) {
+    constexpr int W = 4, STAGE = 64 * 68, QMAX = 1024;
+    __shared__ __attribute__((aligned(16))) float lds_all[W * STAGE + QMAX];
+    __shared__ uint32_t s_n;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float* const lds = lds_all + w * STAGE;
+    float* const ldq = lds_all + W * STAGE;
+    const uint32_t q = blockIdx.x;
+    if (q == 0 && w == 0) {  // the batch's emitted keys (a statistic; one wave, no atomics)
+        uint32_t sum = 0;
+        for (uint32_t i = lane; i < a.nq; i += kWave) sum += a.cnt[i];
+        sum = wave_reduce_u32(sum, [](uint32_t x, uint32_t y) { return x + y; });
+        if (lane == 0) a.status[kStEmitted] = sum;
+    }
+    const uint32_t c = a.cnt[q];
+    if (c > a.cap) {  // keys were dropped: the exact scan answers the query
+        if (threadIdx.x == 0) a.scan_list[atomicAdd(a.status + kStFail, 1u)] = q;
+        return;
+    }
+    if (threadIdx.x == 0) s_n = 0;
+    const uint32_t ld = a.ld, dim = a.dim, nch = ld / 64;
+    const float* const qrow = a.qf32 + (uint64_t)q * ld;
+    const bool qlds = ld <= (uint32_t)QMAX;  // (longer rows read the query from global memory)
+    if (qlds)
+        for (uint32_t cc = threadIdx.x; cc < ld; cc += 64 * W) ldq[cc] = qrow[cc];
+    __syncthreads();
+    const float rad = a.radius[q], mag_b = a.nb[q];
+    const float* rows = a.rows;
+    const uint64_t* src = a.cand + (uint64_t)q * a.cap;
+    uint64_t* dst = a.keys + (uint64_t)q * a.cap;
+    for (uint32_t base = 64u * w; base < c; base += 64 * W) {
+        const uint32_t ci = base + lane;
+        const uint64_t ck = ci < c ? src[ci] : kKeyNone;
+        const bool valid = ck != kKeyNone;
+        const uint32_t myrow = valid ? key_row(ck) : 0u;
+        float acc[1] = {-0.0f}, mx[1] = {0.0f};
+        uint32_t lrow[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) lrow[i] = (uint32_t)__shfl((int)myrow, (i * 64 + lane) >> 4, kWave);
+        auto step = [&](f32x4_t (&pre)[16], uint32_t ch) {
+            wave_sync();
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int L16 = i * 64 + lane;
+                *reinterpret_cast<f32x4_t*>(lds + (L16 >> 4) * 68 + (L16 & 15) * 4) = pre[i];
+            }
+            wave_sync();
+            if (ch + 2 < nch) load_cand_chunk(pre, rows, ld, lrow, ch + 2, lane);
+            const float* const bb[1] = {(qlds ? ldq : qrow) + ch * 64};
+            const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+            seq_chunk<1>(lds + lane * 68, bb, nvalid, acc, mx);
+        };
+        f32x4_t preA[16], preB[16];
+        load_cand_chunk(preA, rows, ld, lrow, 0, lane);
+        if (nch > 1) load_cand_chunk(preB, rows, ld, lrow, 1, lane);
+        for (uint32_t ch = 0; ch < nch; ch += 2) {
+            step(preA, ch);
+            if (ch + 1 < nch) step(preB, ch + 1);
+        }
+        const float mag_a = a.na[myrow];
+        const uint32_t dw = a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[myrow >> 5] : 0u;
+        const float d = finish_distance(acc[0], mx[0], mag_a, mag_b);
+        const bool hit = valid && !((dw >> (myrow & 31)) & 1u) && d <= rad;
+        const uint64_t m = __ballot(hit);
+        if (m) {
+            const int leader = __builtin_ctzll(m);
+            uint32_t b0 = 0;
+            if (lane == leader) b0 = atomicAdd(&s_n, (uint32_t)__popcll(m));
+            b0 = (uint32_t)__shfl((int)b0, leader, kWave);
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (hit) dst[b0 + rank] = dist_key(d, myrow);  // (b0 + rank < c <= cap)
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.rcnt[q] = s_n;
+}
+
+// k_scan_exact's tile loop (the same staging, seq_chunk and finish_distance) with a radius per
+// query instead of a top-k list: the in-range live rows of a wave claim slots of the query's list
+// with one atomic add on its count and store their keys below cap.  Only the launch's first nqf
+// queries count (the ids past them pad the template width).
+template <int QF>
+__global__ __launch_bounds__(256, 2) void k_range_scan(RangeArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    float* ldq = lds + 256 * 68;
+    const int t = threadIdx.x, lane = t & 63;
+    const float* __restrict__ rows = a.rows;
+    const uint32_t ld = a.ld, dim = a.dim;
+    const uint64_t n = a.n, n_tiles = (n + 255) / 256;
+    const uint32_t nch = ld / 64;
+
+    const float* qp[QF];
+    float mag_b[QF], rad[QF];
+    uint32_t id[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        id[j] = (uint32_t)a.qids[j];
+        qp[j] = a.qf32 + (uint64_t)id[j] * ld;
+        mag_b[j] = a.nb[id[j]];
+        rad[j] = a.radius[id[j]];
+    }
+    const uint32_t lrow0 = (uint32_t)t >> 4;
+    const uint32_t lcol = ((uint32_t)t & 15) * 4;
+    uint64_t tile = blockIdx.x;
+    uint32_t ch = 0;
+    f32x4_t pre[16];
+    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
+    auto issue = [&](uint64_t tl, uint32_t c) {
+        const float* base = rows + (tl * 256 + lrow0) * ld + c * 64 + lcol;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const f32x4_t*>(base + (uint64_t)i * 16 * ld);
+        if constexpr (QF > 1) {
+            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + c * 64);
+        }
+    };
+    if (tile < n_tiles) issue(tile, 0);
+    float acc[QF], mx[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+
+    while (tile < n_tiles) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
+        if constexpr (QF > 1) {
+            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
+        }
+        __syncthreads();
+        uint64_t ntile = tile;
+        uint32_t nch_ = ch + 1;
+        if (nch_ == nch) { nch_ = 0; ntile = tile + gridDim.x; }
+        if (ntile >= n_tiles) { ntile = tile; nch_ = ch; }
+        issue(ntile, nch_);
+
+        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+        const float* bq[QF];
+#pragma unroll
+        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
+        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
+
+        if (ch == nch - 1) {
+            const uint64_t row = tile * 256 + t;
+            const bool valid = row < n;
+            const float mag_a = valid ? a.na[row] : 0.0f;
+            const uint32_t dw = valid && a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[row >> 5] : 0u;
+            const bool live = valid && !((dw >> (row & 31)) & 1u);
+#pragma unroll
+            for (int j = 0; j < QF; ++j) {
+                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+                const bool hit = live && (uint32_t)j < a.nqf && d <= rad[j];
+                const uint64_t m = __ballot(hit);
+                if (m) {
+                    const int leader = __builtin_ctzll(m);
+                    uint32_t b0 = 0;
+                    if (lane == leader) b0 = atomicAdd(a.rcnt + id[j], (uint32_t)__popcll(m));
+                    b0 = (uint32_t)__shfl((int)b0, leader, kWave);
+                    const uint32_t slot = b0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (hit && slot < a.cap) a.keys[(uint64_t)id[j] * a.cap + slot] = dist_key(d, (uint32_t)row);
+                }
+                acc[j] = -0.0f;
+                mx[j] = 0.0f;
+            }
+            ch = 0;
+            tile += gridDim.x;
+        } else {
+            ++ch;
+        }
+    }
+}
+
+// One workgroup per query: its list (any order) through a bitonic network in LDS over the next
+// power of two (at least 64) padded with kKeyNone -- u64 order is (distance, row) order -- then the
+// result rows.  A list longer than the capacity leaves only padding; the count is written either way.
+__global__ __launch_bounds__(256) void k_range_finish(const uint64_t* __restrict__ keys,
+                                                      const uint32_t* __restrict__ rcnt, uint32_t cap,
+                                                      uint32_t capacity, uint64_t offset,
+                                                      uint64_t* __restrict__ out_idx,
+                                                      float* __restrict__ out_dist,
+                                                      uint32_t* __restrict__ out_count) {
+    __shared__ uint64_t sk[kRangeMaxResults];
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    const uint32_t c = rcnt[q];
+    const bool fits = c <= capacity;
+    if (t == 0) out_count[q] = c;
+    if (fits && c > 0) {  // (uniform over the workgroup)
+        uint32_t P = 64;
+        while (P < c) P <<= 1;
+        const uint64_t* src = keys + (uint64_t)q * cap;
+        for (uint32_t i = t; i < P; i += blockDim.x) sk[i] = i < c ? src[i] : kKeyNone;
+        __syncthreads();
+        for (uint32_t k = 2; k <= P; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                for (uint32_t i = t; i < P; i += blockDim.x) {
+                    const uint32_t p = i ^ j;
+                    if (p > i) {
+                        const uint64_t x = sk[i], y = sk[p];
+                        const bool up = (i & k) == 0;
+                        if ((x > y) == up) { sk[i] = y; sk[p] = x; }
+                    }
+                }
+                __syncthreads();
+            }
+    }
+    for (uint32_t i = t; i < capacity; i += blockDim.x) {
+        const bool has = fits && i < c;
+        const uint64_t key = has ? sk[i] : kKeyNone;
+        out_idx[(uint64_t)q * capacity + i] = has ? offset + key_row(key) : ~0ull;
+        out_dist[(uint64_t)q * capacity + i] = has ? key_dist(key) : INFINITY;
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Launchers
 // ------------------------------------------------------------------------------------
 #ifdef BSR_RESCORE_STAMPS
@@ -1879,6 +2178,40 @@ hipError_t launch_merge(const MergeArgs& a_in, hipStream_t s) {
 hipError_t launch_cosine_pair(const float* a, uint32_t la, const float* b, uint32_t lb, float* out,
                               hipStream_t s) {
     hipLaunchKernelGGL(k_cosine_pair, dim3(1), dim3(64), 0, s, a, la, b, lb, out);
+    return hipGetLastError();
+}
+
+// ---- range search ------------------------------------------------------------------------
+hipError_t launch_range_tau(const float* radius, const float* ebound, const float* nb, const uint32_t* qflags,
+                            uint32_t nq, uint32_t qpad, float* tau, uint32_t* cnt, uint32_t* rcnt,
+                            uint32_t* scan_list, uint32_t* status, hipStream_t s) {
+    if (!nq || qpad < nq) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_range_tau, dim3(1), dim3(1024), 0, s, radius, ebound, nb, qflags, nq, qpad, tau, cnt, rcnt,
+                       scan_list, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_rescore(const RangeArgs& a, hipStream_t s) {
+    if (!a.nq || !a.cap || a.ld == 0 || a.ld % 64 != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_range_rescore, dim3(a.nq), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_scan(const RangeArgs& a, uint32_t grid, hipStream_t s) {
+    if (!a.nqf || a.nqf > kScanQF || !grid || !a.cap || a.ld == 0 || a.ld % 64 != 0) return hipErrorInvalidValue;
+    if (a.nqf <= 1) hipLaunchKernelGGL(k_range_scan<1>, dim3(grid), dim3(256), 0, s, a);
+    else if (a.nqf <= 2) hipLaunchKernelGGL(k_range_scan<2>, dim3(grid), dim3(256), 0, s, a);
+    else if (a.nqf <= 4) hipLaunchKernelGGL(k_range_scan<4>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_range_scan<8>, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint32_t cap, uint32_t nq,
+                               uint32_t capacity, uint64_t offset, uint64_t* out_idx, float* out_dist,
+                               uint32_t* out_count, hipStream_t s) {
+    if (!nq || !capacity || capacity > kRangeMaxResults || cap < capacity) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_range_finish, dim3(nq), dim3(256), 0, s, keys, rcnt, cap, capacity, offset, out_idx,
+                       out_dist, out_count);
     return hipGetLastError();
 }
 

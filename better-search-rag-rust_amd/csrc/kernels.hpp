@@ -473,6 +473,70 @@ hipError_t launch_merge_parts_groups(const uint64_t* part, uint32_t grid, const 
 hipError_t launch_cosine_pair(const float* a, uint32_t la, const float* b, uint32_t lb,
                               float* out, hipStream_t s);
 
+// ---- range search (bsr_local_range_search; k_exact.hip) -----------------------
+// The emitted lists of a range search of `capacity` result slots per query: twice the capacity,
+// at least 1024 and at most 8192 keys, a multiple of 64.  (8192 keys are 64 KB: a list fits the
+// 160 KB LDS of a gfx950 CU next to the finish kernel's own 32 KB; the sort itself only ever holds
+// capacity <= 4096 keys.)
+constexpr uint32_t kRangeMaxResults = 4096;
+static inline uint32_t range_cap(uint32_t capacity) {
+    const uint32_t c = 2u * capacity < 1024u ? 1024u : 2u * capacity > 8192u ? 8192u : 2u * capacity;
+    return (c + 63u) / 64u * 64u;
+}
+// OR-ed into the kStQueryFlags status word by launch_range_tau: a radius of the batch is NaN.
+constexpr uint32_t kRangeNanRadius = 0x100u;
+// The emission threshold from the radius, before the filter runs (it takes k_select_tau's place):
+// tau[q] = the largest f32 t (to within a few ulps) with exclusion_bound(t, ebound[q], nb[q]) >
+// radius[q], so every row the filter does not emit lies outside the radius.  A query that cannot
+// filter -- kQueryNoApprox, ebound >= 1, or a threshold <= 0 -- gets tau = +inf and is appended to
+// scan_list (status[kStFail] counts the list, status[kStFail2] these queries); radius < 0 and
+// padding queries get +inf and no scan; a NaN radius gets +inf, no scan and kRangeNanRadius.
+// Also zeroes what k_select_tau zeroes for the emit pass -- cnt[0 .. qpad), the tail counters and
+// gang words behind them, the status words kStFail / kStEmitted / kStFail2 (before it counts into
+// them) -- and the range counts rcnt[0 .. nq).  One workgroup.
+hipError_t launch_range_tau(const float* radius, const float* ebound, const float* nb, const uint32_t* qflags,
+                            uint32_t nq, uint32_t qpad, float* tau, uint32_t* cnt, uint32_t* rcnt,
+                            uint32_t* scan_list, uint32_t* status, hipStream_t s);
+// What the range kernels share: the exact operands, the radii, the per-query lists keys [nq][cap]
+// of distance keys (in arbitrary order) and their counts rcnt [nq].
+struct RangeArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t n;                 // rows of the shard (the scan)
+    const float* na;            // row magnitudes (read, never recomputed)
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const float* radius;        // [nq]
+    const uint64_t* dead;       // the bitset of deleted rows (nullable)
+    uint64_t* keys;             // [nq][cap]
+    uint32_t* rcnt;             // [nq]
+    uint32_t cap;
+    uint32_t nq;
+    // the rescore: the emitted score keys cand [qpad][cap] and their counts cnt; a query with
+    // cnt[q] > cap appends itself to scan_list / status[kStFail] and writes nothing
+    const uint64_t* cand;
+    const uint32_t* cnt;
+    uint32_t* scan_list;
+    uint32_t* status;           // also: status[kStEmitted] = the sum of cnt[0 .. nq)
+    // the scan: the ids of the launch's nqf <= kScanQF queries (device; entries up to the template
+    // width -- 1, 2, 4 or 8 -- must be valid ids, those past nqf count nothing)
+    const int32_t* qids;
+    uint32_t nqf;
+};
+// One workgroup per query over its emitted rows: the reference distance of every listed row; the
+// live rows with d <= radius[q] become the query's list, their number rcnt[q].
+hipError_t launch_range_rescore(const RangeArgs& a, hipStream_t s);
+// The exact fallback, k_scan_exact's tile loop: every valid live row with d <= radius claims a slot
+// of its query's list by an atomic add on rcnt[id] (zero before the launch) and stores its key when
+// the slot is below cap; the count stays exact beyond that.
+hipError_t launch_range_scan(const RangeArgs& a, uint32_t grid, hipStream_t s);
+// One workgroup per query: a list of rcnt[q] <= capacity keys sorted ascending (distance, then
+// row) into out_idx / out_dist [nq][capacity] as (offset + row, distance), (~0, +inf) behind them;
+// a longer list: (~0, +inf) in every slot.  out_count[q] = rcnt[q] either way.
+hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint32_t cap, uint32_t nq,
+                               uint32_t capacity, uint64_t offset, uint64_t* out_idx, float* out_dist,
+                               uint32_t* out_count, hipStream_t s);
+
 uint32_t scan_grid_for(uint64_t n);
 
 }  // namespace bsr

@@ -120,6 +120,8 @@ typedef struct {
 #define BSR_PATH_MASK_LIST   128u /* masked search: exact top-k over the allowed-row list */
 #define BSR_PATH_MASK_FILTER 256u /* masked search: int8 filter, emitted lists cut by the mask */
 #define BSR_PATH_MASK_GROUPS 512u /* bsr_local_top_k_masked_groups ran (with MASK_LIST / MASK_FILTER bits) */
+#define BSR_PATH_RANGE      1024u /* bsr_local_range_search ran */
+#define BSR_PATH_RANGE_SCAN 2048u /* ... and a query of the batch was answered by the exact range scan */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -306,6 +308,43 @@ int bsr_local_top_k_masked_groups(bsr_index* ix, const float* queries, uint32_t 
                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                                   const uint32_t* query_mask, uint32_t mode,
                                   uint64_t* out_idx, float* out_dist, uint32_t* out_count);
+
+/* ---- range search: every live row of the shard within a distance of each query, exact.
+ * out_count[q] = the number of live rows whose reference distance to query q is <= radius[q]:
+ * the exact f32 of src/metrics.rs:143-165 (identical-vector shortcut and zero-magnitude rule
+ * included), compared as plain f32.  The count is always exact, even above `capacity`.
+ *   out_count[q] <= capacity: row q of out_idx / out_dist ([n_queries][capacity]) holds exactly
+ *     those rows as (global index, distance) in (distance asc, global index asc) order, and
+ *     (~0, +inf) after them;
+ *   out_count[q] >  capacity: every slot of row q is (~0, +inf) -- call again with more capacity
+ *     or a smaller radius, as with snprintf.  Never a partial or unordered subset.
+ * radius[q] < 0: count 0.  radius[q] >= 2 or +inf: every live row is in range.  A NaN radius:
+ * BSR_E_INVALID for the call, the outputs untouched (device radii are checked on the device,
+ * before any result is written).
+ * BSR_E_INVALID before any device is touched: a null index; with n_queries > 0 a null radius,
+ * queries or output; capacity 0 or above BSR_RANGE_MAX_RESULTS.  Not loaded: BSR_E_STATE.  A
+ * non-finite query: BSR_E_NONFINITE, as bsr_local_top_k.  n_queries = 0: BSR_OK.  An empty shard:
+ * every count 0.  Every other status as bsr_local_top_k.
+ * queries, radius and the outputs are, independently, host or device pointers, detected per call.
+ * Deleted rows (bsr_index_delete) are never counted or returned.
+ * How: the int8 filter's certified bound gives the emission threshold from the
+ * radius, so the emitted rows are a superset of the answer and are rescored exactly; a query
+ * whose emitted list overflows, or that the filter cannot serve, takes an exact scan of the shard.
+ * An index that cannot filter (BSR_FLAG_EXACT_ONLY, out-of-range row norms, or no more rows than
+ * an emitted list holds) scans every query.  Never graph-replayed; the plain search's graphs are
+ * left alone.  bsr_search_stats: search_path carries BSR_PATH_RANGE, and BSR_PATH_RANGE_SCAN
+ * when any query was answered by the scan; n_emitted = the emitted keys of the batch;
+ * n_exact_direct = the queries sent to the scan by design; n_fallback = the queries whose emitted
+ * list overflowed.
+ * Out of scope: an allow mask combined with a radius; a multi-rank range search (every rank calls
+ * this on its shard and the caller concatenates: ranges need no merge); a CSR (compressed sparse
+ * row) output. */
+#define BSR_RANGE_MAX_RESULTS 4096u
+int bsr_local_range_search(bsr_index* ix, const float* queries, uint32_t n_queries,
+                           const float* radius,            /* [n_queries], host or device */
+                           uint32_t capacity,              /* result slots per query, 1..BSR_RANGE_MAX_RESULTS */
+                           uint64_t* out_idx, float* out_dist,   /* [n_queries][capacity] */
+                           uint32_t* out_count);                 /* [n_queries] */
 
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]
