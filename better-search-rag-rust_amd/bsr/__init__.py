@@ -145,6 +145,7 @@ def lib() -> ctypes.CDLL:
         "bsr_local_top_k_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, _P, _P]),
         "bsr_local_top_k_masked_groups": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_local_range_search": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P, _P]),
+        "bsr_local_range_search_masked": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
         "bsr_comm_init": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(_P)]),
@@ -167,7 +168,8 @@ def lib() -> ctypes.CDLL:
     }
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
-                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search"}
+                "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
+                "bsr_local_range_search_masked"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -555,12 +557,22 @@ class Index:
         _check(lib().bsr_local_top_k_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), nw,
                                             _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_count)))
 
-    def range_search(self, queries, radius, max_results: int = 256):
+    def range_search(self, queries, radius, max_results: int = 256, allow_mask=None, allow_ids=None,
+                     allow_masks=None, query_mask=None, mask_mode="auto"):
         """Every live row within a distance of each query (bsr_local_range_search) -> (idx [Q,cap]
         u64, dist [Q,cap] f32, count [Q] u32) with cap = max_results.  radius: a scalar for the
         whole batch or one value per query.  count[q] is always the exact number of rows with
         distance <= radius[q]; when it exceeds max_results, row q holds only padding (~0, +inf) --
-        call again with more slots or a smaller radius."""
+        call again with more slots or a smaller radius.
+        Restricted to allowed rows (bsr_local_range_search_masked): allow_mask / allow_ids give one
+        mask for the batch, as local_top_k's; allow_masks [G][n] with query_mask [Q] one mask per
+        query group, as local_top_k_grouped's.  The counts are then over the allowed live rows.
+        mask_mode: "auto", "list", "filter" or a BSR_MASK_* value, per mask group."""
+        one = allow_mask is not None or allow_ids is not None
+        if one and (allow_masks is not None or query_mask is not None):
+            raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
+        if (allow_masks is None) != (query_mask is None):
+            raise BsrError(-1, "allow_masks and query_mask go together")
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -579,15 +591,41 @@ class Index:
         oi = np.empty((nq, cap), np.uint64)
         od = np.empty((nq, cap), np.float32)
         oc = np.empty(nq, np.uint32)
-        _check(lib().bsr_local_range_search(self._h, _ptr(q), nq, _ptr(r), cap, _ptr(oi), _ptr(od), _ptr(oc)))
+        if not one and allow_masks is None:
+            _check(lib().bsr_local_range_search(self._h, _ptr(q), nq, _ptr(r), cap, _ptr(oi), _ptr(od), _ptr(oc)))
+            return oi, od, oc
+        if one:
+            w, nw = self._allow_words(allow_mask, allow_ids)
+            n_masks, qm = 1, None
+        else:
+            w, n_masks, nw = self._allow_group_words(allow_masks)
+            qm = self._query_mask_ids(query_mask, nq)
+        # (an empty shard's masks have no words: a valid, non-null pointer all the same)
+        wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
+        _check(lib().bsr_local_range_search_masked(self._h, _ptr(q), nq, _ptr(r), cap, wp, nw, n_masks, _ptr(qm),
+                                                   _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(oc)))
         return oi, od, oc
 
-    def range_search_device(self, queries, nq: int, radius, max_results: int, out_idx, out_dist, out_count):
+    def range_search_device(self, queries, nq: int, radius, max_results: int, out_idx, out_dist, out_count,
+                            allow_words=None, query_mask=None, mask_mode="auto"):
         """Zero-copy variant of range_search on caller buffers (torch tensors, numpy arrays or raw
         pointers, each host or device): queries [nq][dim] f32, radius [nq] f32, out_idx / out_dist
-        [nq][max_results], out_count [nq]."""
-        _check(lib().bsr_local_range_search(self._h, _ptr(queries), nq, _ptr(radius), max_results, _ptr(out_idx),
-                                            _ptr(out_dist), _ptr(out_count)))
+        [nq][max_results], out_count [nq].  allow_words: the packed allow masks, [G][ceil(n / 64)]
+        uint64 with query_mask [nq] 32-bit mask ids, or [ceil(n / 64)] -- one mask, no query_mask."""
+        if allow_words is None:
+            if query_mask is not None:
+                raise BsrError(-1, "a query_mask needs allow_words")
+            _check(lib().bsr_local_range_search(self._h, _ptr(queries), nq, _ptr(radius), max_results, _ptr(out_idx),
+                                                _ptr(out_dist), _ptr(out_count)))
+            return
+        shape = tuple(allow_words.shape)
+        if len(shape) not in (1, 2):
+            raise BsrError(-1, "packed allow masks have shape [G][words] or [words]")
+        n_masks = int(shape[0]) if len(shape) == 2 else 1
+        _check(lib().bsr_local_range_search_masked(self._h, _ptr(queries), nq, _ptr(radius), max_results,
+                                                   _ptr(allow_words), int(shape[-1]), n_masks, _ptr(query_mask),
+                                                   _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist),
+                                                   _ptr(out_count)))
 
     def _allow_group_words(self, allow_masks):
         """(buffer, masks, words per mask) of a grouped search's allow masks: a bool array [G][n]
@@ -605,6 +643,24 @@ class Index:
         w = np.ascontiguousarray(w)
         return w, int(w.shape[0]), int(w.shape[1])
 
+    @staticmethod
+    def _query_mask_ids(query_mask, nq: int):
+        """A grouped search's query_mask [nq] as a buffer of 32-bit mask ids: integers (checked and
+        converted here) or a 32-bit torch tensor (passed through)."""
+        if hasattr(query_mask, "data_ptr"):
+            if query_mask.element_size() != 4 or not query_mask.is_contiguous():
+                raise BsrError(-1, "a tensor query_mask holds 32-bit mask ids, contiguous")
+            qm, n_qm = query_mask, int(query_mask.numel())
+        else:
+            qm = np.asarray(query_mask)
+            if qm.size and (not np.issubdtype(qm.dtype, np.integer) or int(qm.min()) < 0 or int(qm.max()) > 0xFFFFFFFF):
+                raise BsrError(-1, "query_mask holds mask ids: integers in [0, G)")
+            qm = np.ascontiguousarray(qm.reshape(-1), np.uint32)
+            n_qm = int(qm.size)
+        if n_qm != nq:
+            raise BsrError(-1, f"query_mask has {n_qm} entries for {nq} queries")
+        return qm
+
     def local_top_k_grouped(self, queries, k: int, allow_masks, query_mask, mask_mode="auto"):
         """Batched search with one allow mask per group of queries (bsr_local_top_k_masked_groups)
         -> (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32).  allow_masks: a bool array [G][n], packed
@@ -618,18 +674,7 @@ class Index:
             raise BsrError(-6, f"query length {q.shape[1]} != dim {self.dim}")
         nq = q.shape[0]
         w, n_masks, nw = self._allow_group_words(allow_masks)
-        if hasattr(query_mask, "data_ptr"):
-            if query_mask.element_size() != 4 or not query_mask.is_contiguous():
-                raise BsrError(-1, "a tensor query_mask holds 32-bit mask ids, contiguous")
-            qm, n_qm = query_mask, int(query_mask.numel())
-        else:
-            qm = np.asarray(query_mask)
-            if qm.size and (not np.issubdtype(qm.dtype, np.integer) or int(qm.min()) < 0 or int(qm.max()) > 0xFFFFFFFF):
-                raise BsrError(-1, "query_mask holds mask ids: integers in [0, G)")
-            qm = np.ascontiguousarray(qm.reshape(-1), np.uint32)
-            n_qm = int(qm.size)
-        if n_qm != nq:
-            raise BsrError(-1, f"query_mask has {n_qm} entries for {nq} queries")
+        qm = self._query_mask_ids(query_mask, nq)
         oi = np.empty((nq, k), np.uint64)
         od = np.empty((nq, k), np.float32)
         oc = np.empty(nq, np.uint32)

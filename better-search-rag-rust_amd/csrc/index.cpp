@@ -2141,6 +2141,335 @@ int bsr_local_range_search_impl(bsr_index* ix, const float* queries, uint32_t nq
     return BSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Masked range search (bsr_local_range_search_masked)
+// ---------------------------------------------------------------------------------------
+// The exact range over row lists for the queries `listed` (ascending ids), every one over the list
+// of its own mask (h_grp_qmask, A_g in h_grp_out): run_list_scan_groups' plan with the lists in
+// segments, so that a chunk never holds more than the budget's ids and a list longer than that is
+// split over chunks -- the counts accumulate through the atomic on rcnt, no merge is needed.  A
+// chunk is one scatter launch and, per width qf in {8, 4, 2, 1}, one grouped range scan per 65535
+// query groups.  Queries whose mask allows no row are not scanned: their count stays 0.
+// BSR_MASK_AUTO for a range, where both paths are possible: a pure function of (n, A_g, nq_g,
+// capacity).  Two terms (the measured table, profiles/range_masked_bench.json):
+// - the masked top-k's cost rule, auto_prefers_list, unchanged -- a list-scan row against a filter
+//   pass; the measured range points on its side of the second term agree with it;
+// - the overflow term, the range's own: the filter emits from the whole shard, about 1 / rho rows
+//   per allowed row in range, into lists of range_cap(capacity) keys.  A caller whose results about
+//   fill their capacity overflows those lists once rho < capacity / range_cap(capacity), and an
+//   overflowed query pays the filter pass AND the list scan.  Measured (1M x 768, capacity 256,
+//   100 rows in range within the mask): at rho = 1/4 12% of 1000 queries overflow and the filter
+//   still wins 4.4 to 28 ms; at 1/16 all do and it loses 7.7 to 6.9 ms, at 1/100 2.3 to 1.3 ms.
+//   Hence: the list when rho < capacity / (2 range_cap(capacity)) -- 1/8 up to 512 slots.
+// What the rule cannot see is the radius: a small radius under a sparse mask would filter well.
+static bool range_auto_prefers_list(uint64_t n, uint64_t A, uint32_t nq, uint32_t capacity) {
+    return auto_prefers_list(n, A, nq, 1) || 2 * A * range_cap(capacity) < n * (uint64_t)capacity;
+}
+
+static int run_range_list_scan(bsr_index* ix, RangeListArgs la, const uint64_t* allow, uint64_t words,
+                               uint32_t n_masks, const std::vector<uint32_t>& listed) {
+    const std::vector<uint32_t>& qmask = ix->h_grp_qmask;
+    const std::vector<uint32_t>& A = ix->h_grp_out;
+    // the listed queries by mask, ascending within a mask (a counting sort)
+    std::vector<uint32_t> start(n_masks + 1, 0), order;
+    for (uint32_t q : listed)
+        if (A[qmask[q]]) ++start[qmask[q] + 1];
+    for (uint32_t g = 0; g < n_masks; ++g) start[g + 1] += start[g];
+    order.resize(start[n_masks]);
+    {
+        std::vector<uint32_t> at(start.begin(), start.end() - 1);
+        for (uint32_t q : listed)
+            if (A[qmask[q]]) order[at[qmask[q]]++] = q;
+    }
+    if (order.empty()) return BSR_OK;
+
+    struct Launch { uint32_t qf, groups, grid; size_t scan0, ids0; };
+    struct Chunk { size_t seg0; uint32_t n_segs; std::vector<Launch> launches; };
+    std::vector<Chunk> chunks;
+    std::vector<MaskSegDesc>& segs = ix->h_rng_segs;
+    std::vector<ScanGroupDesc>& scans = ix->h_grp_scan;
+    std::vector<int32_t>& ids = ix->h_grp_ids;
+    segs.clear();
+    scans.clear();
+    ids.clear();
+    const uint64_t budget = mask_list_budget_ids();
+    uint64_t used = 0, list_ids = 0;
+    Chunk cur{0, 0, {}};
+    auto close = [&]() {
+        if (!cur.n_segs) return;
+        // the chunk's query groups, one width after the other: every segment meets every group of its mask
+        for (uint32_t qf = kScanQF; qf >= 1; qf /= 2) {
+            std::vector<ScanGroupDesc> sg;
+            std::vector<int32_t> gid;
+            uint32_t longest = 0;
+            for (size_t l = cur.seg0; l < cur.seg0 + cur.n_segs; ++l) {
+                const MaskSegDesc& d = segs[l];
+                const uint32_t q0 = start[d.mask], nqg = start[d.mask + 1] - q0, rest = nqg % kScanQF;
+                auto group = [&](uint32_t first, uint32_t cnt) {
+                    sg.push_back(ScanGroupDesc{d.off, d.n_list, cnt});
+                    for (uint32_t j = 0; j < qf; ++j) gid.push_back((int32_t)order[first + (j < cnt ? j : 0)]);
+                    longest = std::max(longest, d.n_list);
+                };
+                if (qf == kScanQF)
+                    for (uint32_t f = 0; f + kScanQF <= nqg; f += kScanQF) group(q0 + f, kScanQF);
+                if (rest && rest <= qf && rest > qf / 2) group(q0 + nqg - rest, rest);
+            }
+            if (sg.empty()) continue;
+            const uint32_t grid = scan_grid_for(longest);
+            for (size_t g0 = 0; g0 < sg.size(); g0 += 65535) {
+                const uint32_t n_g = (uint32_t)std::min<size_t>(65535, sg.size() - g0);
+                cur.launches.push_back(Launch{qf, n_g, grid, scans.size() + g0, ids.size() + g0 * qf});
+            }
+            scans.insert(scans.end(), sg.begin(), sg.end());
+            ids.insert(ids.end(), gid.begin(), gid.end());
+        }
+        list_ids = std::max(list_ids, used);
+        chunks.push_back(std::move(cur));
+        cur = Chunk{segs.size(), 0, {}};
+        used = 0;
+    };
+    for (uint32_t g = 0; g < n_masks; ++g) {
+        if (start[g] == start[g + 1]) continue;
+        for (uint32_t pos = 0; pos < A[g];) {
+            if (used == budget) close();
+            const uint32_t take = (uint32_t)std::min<uint64_t>(A[g] - pos, budget - used);
+            segs.push_back(MaskSegDesc{used, g, pos, take, 0});
+            ++cur.n_segs;
+            used += take;
+            pos += take;
+        }
+    }
+    close();
+
+    BSR_TRY(ix->mask_list.ensure((size_t)list_ids * sizeof(uint32_t)));
+    BSR_TRY(ix->rng_segs.ensure(segs.size() * sizeof(MaskSegDesc)));
+    BSR_TRY(ix->grp_scan.ensure(scans.size() * sizeof(ScanGroupDesc)));
+    BSR_TRY(ix->qids.ensure(ids.size() * sizeof(int32_t)));
+    BSR_HIP(hipMemcpyAsync(ix->rng_segs.p, segs.data(), segs.size() * sizeof(MaskSegDesc), hipMemcpyHostToDevice,
+                           ix->stream));
+    BSR_HIP(hipMemcpyAsync(ix->grp_scan.p, scans.data(), scans.size() * sizeof(ScanGroupDesc), hipMemcpyHostToDevice,
+                           ix->stream));
+    BSR_HIP(hipMemcpyAsync(ix->qids.p, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
+    la.list = ix->mask_list.as<uint32_t>();
+    ev_begin(ix, ix->ev_scan, 1);
+    for (const Chunk& c : chunks) {
+        // (the stream orders a chunk's scatter behind the scans of the chunk before it)
+        BSR_HIP(launch_mask_groups_scatter_seg(allow, words, ix->n, ix->dead_bits(), ix->grp_blk.as<uint32_t>(),
+                                               ix->rng_segs.as<MaskSegDesc>() + c.seg0, c.n_segs,
+                                               ix->mask_list.as<uint32_t>(), ix->stream));
+        for (const Launch& l : c.launches) {
+            la.grp = ix->grp_scan.as<ScanGroupDesc>() + l.scan0;
+            la.qids = ix->qids.as<int32_t>() + l.ids0;
+            la.groups = l.groups;
+            la.qf = l.qf;
+            BSR_HIP(launch_range_scan_list_groups(la, l.grid, ix->stream));
+        }
+    }
+    ev_end(ix, ix->ev_scan);
+    return BSR_OK;
+}
+
+int bsr_index::range_search_device_masked(const float* queries, uint32_t nq, const float* radius, uint32_t capacity,
+                                          const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                          const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx,
+                                          float* out_dist, uint32_t* out_count) {
+    bsr_index* ix = this;
+    BSR_TRY(check_batch(ix, 1));
+    if (allow_words != (n + 63) / 64)
+        return set_error(BSR_E_INVALID, "allow_words=%llu, the index holds %llu rows (%llu words)",
+                         (unsigned long long)allow_words, (unsigned long long)n, (unsigned long long)((n + 63) / 64));
+    // (host radii: a NaN is refused before any device work, as bsr_local_range_search does)
+    const bool radius_dev = is_device_ptr(radius);
+    if (!radius_dev)
+        for (uint32_t q = 0; q < nq; ++q)
+            if (radius[q] != radius[q]) return set_error(BSR_E_INVALID, "radius[%u] is NaN", q);
+    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_RANGE | (query_mask ? BSR_PATH_MASK_GROUPS : 0u)));
+    if (nq == 0) return BSR_OK;
+
+    const uint32_t cap = range_cap(capacity);
+    const uint32_t qpad = qpad_for(nq);
+    BSR_TRY(query_buffers(ix, nq, qpad, 1));
+    BSR_TRY(filter_buffers(ix, nq, qpad, 1, cap));
+    stats.n_candidates = 0;
+    BSR_TRY(mask_aux.ensure(((size_t)qpad + 1) * sizeof(uint32_t)));
+    BSR_TRY(rng_keys.ensure((size_t)nq * cap * sizeof(uint64_t)));
+    BSR_TRY(rng_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_TRY(rng_idx.ensure((size_t)nq * capacity * sizeof(uint64_t)));
+    BSR_TRY(rng_dist.ensure((size_t)nq * capacity * sizeof(float)));
+    BSR_TRY(rng_out_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_TRY(rng_route.ensure((size_t)nq * sizeof(uint32_t)));
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
+    const float* rsrc = nullptr;
+    BSR_TRY(on_device(ix, rng_radius, radius, (size_t)nq * sizeof(float), radius_dev, &rsrc));
+    // The masks and the mask ids on the device; the ids on the host too (it forms the query groups).
+    const uint64_t* dallow = allow;
+    if (allow_words)
+        BSR_TRY(on_device(ix, mask_dev, allow, (size_t)n_masks * allow_words * sizeof(uint64_t), is_device_ptr(allow),
+                          &dallow));
+    const uint32_t* dqmask = query_mask;  // (nullptr: mask 0 for every query, n_masks == 1)
+    h_grp_qmask.assign(nq, 0);
+    if (query_mask && is_device_ptr(query_mask)) {
+        BSR_HIP(hipMemcpyAsync(h_grp_qmask.data(), query_mask, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               stream));
+    } else if (query_mask) {
+        memcpy(h_grp_qmask.data(), query_mask, (size_t)nq * sizeof(uint32_t));
+        BSR_TRY(grp_qmask.ensure((size_t)nq * sizeof(uint32_t)));
+        BSR_HIP(hipMemcpyAsync(grp_qmask.p, h_grp_qmask.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               stream));
+        dqmask = grp_qmask.as<uint32_t>();
+    }
+    // 1. Every A_g (over allow_g & ~dead) and the check of query_mask: one readback.
+    const uint32_t n_blk = mask_blocks(n);
+    BSR_TRY(grp_blk.ensure((size_t)n_masks * (n_blk + 1) * sizeof(uint32_t)));
+    BSR_TRY(grp_out.ensure(((size_t)n_masks + 1) * sizeof(uint32_t)));
+    h_grp_out.assign((size_t)n_masks + 1, 0);
+    BSR_HIP(launch_mask_groups_count(dallow, allow_words, n_masks, n, dead_bits(), dqmask, nq, grp_blk.as<uint32_t>(),
+                                     grp_out.as<uint32_t>(), stream));
+    BSR_HIP(hipMemcpyAsync(h_grp_out.data(), grp_out.p, ((size_t)n_masks + (dqmask ? 1 : 0)) * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (dqmask && h_grp_out[n_masks])
+        return set_error(BSR_E_INVALID, "%u entries of query_mask name no mask (n_masks = %u)", h_grp_out[n_masks],
+                         n_masks);
+
+    // 2. The route of every mask group.  The filter is possible where the unmasked range search
+    // filters: the threshold comes from the radius alone, so the emitted rows are a superset of the
+    // answer under any mask and no A_g is too small for it.  BSR_MASK_AUTO: the masked top-k's rule
+    // (k does not enter it) and the range's overflow term, range_auto_prefers_list above.
+    const uint64_t live = live_rows();
+    const bool can_filter = live > 0 && approx_ok && n > cap;
+    std::vector<uint32_t> nq_g(n_masks, 0);
+    std::vector<uint8_t> list_g(n_masks, 1);
+    for (uint32_t q = 0; q < nq; ++q) ++nq_g[h_grp_qmask[q]];
+    bool any_filter = false, any_list = false;
+    for (uint32_t g = 0; g < n_masks; ++g) {
+        if (!nq_g[g]) continue;
+        list_g[g] = !can_filter || mode == BSR_MASK_LIST ||
+                    (mode == BSR_MASK_AUTO && range_auto_prefers_list(n, h_grp_out[g], nq_g[g], capacity));
+        any_filter |= !list_g[g];
+        any_list |= list_g[g] != 0;
+    }
+    h_rng_route.resize(nq);
+    for (uint32_t q = 0; q < nq; ++q) h_rng_route[q] = list_g[h_grp_qmask[q]];
+    if (any_list)
+        BSR_HIP(hipMemcpyAsync(rng_route.p, h_rng_route.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               stream));
+
+    // 3. The queries and the thresholds (in every mode: the zeroed counts, the device check of the
+    // radii); 4. the list-by-design queries: tau = +inf, on the scan list once.
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, any_filter), stream));
+    BSR_HIP(launch_range_tau(rsrc, ebound.as<float>(), nb.as<float>(), qflags.as<uint32_t>(), nq, qpad,
+                             tau.as<float>(), cnt.as<uint32_t>(), rng_cnt.as<uint32_t>(), fail.as<uint32_t>(), d_status,
+                             stream));
+    if (any_list)
+        BSR_HIP(launch_range_route(rng_route.as<uint32_t>(), rsrc, nq, tau.as<float>(), fail.as<uint32_t>(), d_status,
+                                   stream));
+    if (any_filter) {
+        // 5. the emit pass over every tile, the emitted lists cut by each query's mask (less the
+        // tombstones; an overflowed list stays overflowed), the survivors rescored against the radius
+        stats.search_path |= BSR_PATH_MASK_FILTER;
+        smp_tiles = 0;
+        BSR_TRY(emit_pass(ix, nq, qpad, 1, cap));
+        uint32_t* raw_cnt = mask_aux.as<uint32_t>();
+        BSR_HIP(launch_mask_cut(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap, nq, dallow, allow_words, dqmask,
+                                dead_bits(), n, raw_cnt, raw_cnt + qpad, stream));
+        RangeArgs ra{};
+        ra.rows = rows.as<float>();
+        ra.ld = ld;
+        ra.dim = dim;
+        ra.n = n;
+        ra.na = na.as<float>();
+        ra.qf32 = qf32.as<float>();
+        ra.nb = nb.as<float>();
+        ra.radius = rsrc;
+        ra.dead = dead_bits();
+        ra.keys = rng_keys.as<uint64_t>();
+        ra.rcnt = rng_cnt.as<uint32_t>();
+        ra.cap = cap;
+        ra.nq = nq;
+        ra.cand = cand.as<uint64_t>();
+        ra.cnt = cnt.as<uint32_t>();
+        ra.scan_list = fail.as<uint32_t>();
+        ra.status = d_status;
+        ra.emit_cnt = raw_cnt;
+        ev_begin(ix, ev_rescore);
+        BSR_HIP(launch_range_rescore(ra, stream));
+        ev_end(ix, ev_rescore);
+    }
+    // 6. The one status readback: the query flags (a non-finite query, a NaN radius) and the
+    // number of queries on the scan list.
+    BSR_HIP(hipMemcpyAsync(h_res, d_status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BSR_HIP(stream_wait(stream));
+    BSR_TRY(check_queries(ix, nq));
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+    if (st[kStQueryFlags] & kRangeNanRadius) return set_error(BSR_E_INVALID, "a radius of the batch is NaN");
+    const uint32_t nscan = st[kStFail], ndirect = st[kStFail2];
+    stats.n_emitted = any_filter ? st[kStEmitted] : 0;
+    stats.n_exact_direct = ndirect;
+    stats.n_fallback = nscan - ndirect;
+    if (nscan) {
+        // 7. / 8. the row lists of the masks of the queries on the scan list, and the range over them
+        stats.search_path |= BSR_PATH_MASK_LIST;
+        h_fail.resize(nscan);
+        BSR_HIP(hipMemcpy(h_fail.data(), fail.p, (size_t)nscan * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::sort(h_fail.begin(), h_fail.end());
+        RangeListArgs la{};
+        la.rows = rows.as<float>();
+        la.ld = ld;
+        la.dim = dim;
+        la.na = na.as<float>();
+        la.qf32 = qf32.as<float>();
+        la.nb = nb.as<float>();
+        la.radius = rsrc;
+        la.keys = rng_keys.as<uint64_t>();
+        la.rcnt = rng_cnt.as<uint32_t>();
+        la.cap = cap;
+        BSR_TRY(run_range_list_scan(ix, la, dallow, allow_words, n_masks, h_fail));
+    }
+    // The lists sorted into result rows: straight into the caller's arrays when all three are on
+    // the device, else into the index's own and copied out.
+    const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count);
+    uint64_t* di = out_dev ? out_idx : rng_idx.as<uint64_t>();
+    float* dd = out_dev ? out_dist : rng_dist.as<float>();
+    uint32_t* dc = out_dev ? out_count : rng_out_cnt.as<uint32_t>();
+    BSR_HIP(launch_range_finish(rng_keys.as<uint64_t>(), rng_cnt.as<uint32_t>(), cap, nq, capacity, global_offset, di,
+                                dd, dc, stream));
+    ev_end(ix, ev_total);
+    if (!out_dev) {
+        const size_t nk = (size_t)nq * capacity;
+        BSR_HIP(hipMemcpyAsync(out_idx, di, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, dd, nk * sizeof(float), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, dc, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_range_search_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, const float* radius,
+                                       uint32_t capacity, const uint64_t* allow, uint64_t allow_words,
+                                       uint32_t n_masks, const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx,
+                                       float* out_dist, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (capacity == 0 || capacity > BSR_RANGE_MAX_RESULTS)
+        return set_error(BSR_E_INVALID, "capacity=%u outside [1, %u]", capacity, BSR_RANGE_MAX_RESULTS);
+    if (n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 (bsr_local_range_search searches without a mask)");
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !radius) return set_error(BSR_E_INVALID, "null radius");
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (nq && !allow) return set_error(BSR_E_INVALID, "null allow masks");
+    if (!query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    BSR_TRY(ix->range_search_device_masked(queries, nq, radius, capacity, allow, allow_words, n_masks, query_mask, mode,
+                                           out_idx, out_dist, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
 int bsr_index_collect_profile_impl(bsr_index* ix) {
     collect_profile(ix);
     return BSR_OK;

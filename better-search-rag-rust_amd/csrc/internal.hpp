@@ -245,6 +245,18 @@ struct bsr_index {
     bsr::DevBuf rng_cnt;     // u32 [nq]: their exact counts
     bsr::DevBuf rng_idx, rng_dist, rng_out_cnt;  // the result rows [nq][capacity], the counts [nq]
 
+    // Masked range search (bsr_local_range_search_masked): the range search with an
+    // allow mask per query group -- the grouped masked search's mask buffers (grp_*), the range
+    // search's result buffers (rng_*), and the row lists in segments.
+    int range_search_device_masked(const float* queries, uint32_t nq, const float* radius, uint32_t capacity,
+                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                   const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                   uint32_t* out_count);
+    bsr::DevBuf rng_route;  // u32 [nq]: 1 = the query's group takes the list scan by design
+    bsr::DevBuf rng_segs;   // MaskSegDesc: the list segments of every chunk
+    std::vector<uint32_t> h_rng_route;
+    std::vector<bsr::MaskSegDesc> h_rng_segs;
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

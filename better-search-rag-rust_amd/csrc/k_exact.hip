@@ -1683,7 +1683,8 @@ __global__ __launch_bounds__(256) void k_range_rescore(RangeArgs a) {
     const uint32_t q = blockIdx.x;
     if (q == 0 && w == 0) {  // the batch's emitted keys (a statistic; one wave, no atomics)
         uint32_t sum = 0;
-        for (uint32_t i = lane; i < a.nq; i += kWave) sum += a.cnt[i];
+        const uint32_t* const ec = a.emit_cnt ? a.emit_cnt : a.cnt;  // (behind a mask cut: the counts before it)
+        for (uint32_t i = lane; i < a.nq; i += kWave) sum += ec[i];
         sum = wave_reduce_u32(sum, [](uint32_t x, uint32_t y) { return x + y; });
         if (lane == 0) a.status[kStEmitted] = sum;
     }
@@ -1840,6 +1841,149 @@ __global__ __launch_bounds__(256, 2) void k_range_scan(RangeArgs a) {
             }
             ch = 0;
             tile += gridDim.x;
+        } else {
+            ++ch;
+        }
+    }
+}
+
+// The masked range search's routing, one workgroup behind k_range_tau: a query
+// with to_list[q] != 0 is answered by the list scan by design -- its threshold becomes +inf (the
+// filter emits nothing for it) and it joins scan_list unless k_range_tau put it there already
+// (tau = +inf with a radius >= 0) or its radius keeps it off (radius < 0, NaN).  status[kStFail] /
+// [kStFail2] grow by the queries appended, each written once, by thread 0.
+__global__ __launch_bounds__(1024) void k_range_route(const uint32_t* __restrict__ to_list,
+                                                      const float* __restrict__ radius, uint32_t nq,
+                                                      float* __restrict__ tau, uint32_t* __restrict__ scan_list,
+                                                      uint32_t* __restrict__ status) {
+    __shared__ uint32_t s_add;
+    const uint32_t t = threadIdx.x;
+    const uint32_t base = status[kStFail];  // (k_range_tau's count; not written before the barrier below)
+    if (t == 0) s_add = 0;
+    __syncthreads();
+    for (uint32_t q = t; q < nq; q += blockDim.x) {
+        if (!to_list[q]) continue;
+        const float r = radius[q];
+        if (r >= 0.0f && tau[q] < INFINITY) scan_list[base + atomicAdd(&s_add, 1u)] = q;  // (NaN: r >= 0 is false)
+        tau[q] = INFINITY;
+    }
+    __syncthreads();
+    if (t == 0 && s_add) {
+        status[kStFail] = base + s_add;
+        status[kStFail2] += s_add;
+    }
+}
+
+// The range over row lists (bsr_local_range_search_masked): k_scan_list<QF, ., GRP>'s
+// gather loop -- group blockIdx.y walks the grp[y].n_list ids at list + grp[y].off, 256 per tile,
+// entry t of the next tile fetched a tile ahead and handed to the loading threads through s_ids --
+// with k_range_scan's epilogue: the in-range rows of a wave claim slots of their query's list with
+// one atomic add on its count and store their keys below cap.  Only the group's first grp[y].nq
+// queries count (the ids past them pad the template width).  No mask and no tombstone is read: the
+// list holds the allowed live rows.  A workgroup without a tile in its group's list does nothing.
+template <int QF>
+__global__ __launch_bounds__(256, 2) void k_range_scan_list(RangeListArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    __shared__ uint32_t s_ids[256];  // the rows of the tile being loaded
+    const ScanGroupDesc me = a.grp[blockIdx.y];
+    const uint32_t* __restrict__ list = a.list + me.off;
+    const uint32_t n_list = me.n_list;
+    float* ldq = lds + 256 * 68;
+    const int t = threadIdx.x, lane = t & 63;
+    const float* __restrict__ rows = a.rows;
+    const uint32_t ld = a.ld, dim = a.dim;
+    const uint32_t n_tiles = (n_list + 255) / 256;
+    const uint32_t nch = ld / 64;
+    const int32_t* qids = a.qids + (uint64_t)blockIdx.y * QF;
+    uint32_t tile = blockIdx.x;
+    if (tile >= n_tiles) return;  // (uniform over the workgroup: before any barrier)
+
+    const float* qp[QF];
+    float mag_b[QF], rad[QF];
+    uint32_t id[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        id[j] = (uint32_t)qids[j];
+        qp[j] = a.qf32 + (uint64_t)id[j] * ld;
+        mag_b[j] = a.nb[id[j]];
+        rad[j] = a.radius[id[j]];
+    }
+    const uint32_t lrow0 = (uint32_t)t >> 4;   // + 16*i
+    const uint32_t lcol = ((uint32_t)t & 15) * 4;
+    uint32_t ch = 0;
+    // entry t of a tile (past the list: row 0, loaded and never counted)
+    auto id_at = [&](uint64_t tl) -> uint32_t {
+        const uint64_t p = tl * 256 + t;
+        return p < n_list ? list[p] : 0u;
+    };
+    f32x4_t pre[16];
+    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
+    auto issue = [&](uint32_t c) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            pre[i] = *reinterpret_cast<const f32x4_t*>(rows + (uint64_t)s_ids[lrow0 + 16 * i] * ld + c * 64 + lcol);
+        if constexpr (QF > 1) {
+            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + c * 64);
+        }
+    };
+    // this lane's own row of the tile being walked and its magnitude; its entry of the next tile
+    uint32_t myrow = id_at(tile), idn = id_at((uint64_t)tile + gridDim.x);
+    s_ids[t] = myrow;
+    __syncthreads();
+    issue(0);
+    float mag_a = a.na[myrow];
+    float acc[QF], mx[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+
+    while (tile < n_tiles) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
+        if constexpr (QF > 1) {
+            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
+        }
+        // (the last chunk's loads are out: the next loads are the next tile's.  Without a next
+        // tile idn is row 0 everywhere and the reload below fetches it in vain.)
+        if (ch == nch - 1) s_ids[t] = idn;
+        __syncthreads();
+        // next (tile, chunk); past the end: reload the current chunk (branch-free prefetch)
+        uint32_t nch_ = ch + 1;
+        if (nch_ == nch) nch_ = (uint64_t)tile + gridDim.x < n_tiles ? 0u : ch;
+        issue(nch_);
+
+        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+        const float* bq[QF];
+#pragma unroll
+        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
+        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
+
+        if (ch == nch - 1) {
+            const bool valid = (uint64_t)tile * 256 + t < n_list;
+#pragma unroll
+            for (int j = 0; j < QF; ++j) {
+                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+                const bool hit = valid && (uint32_t)j < me.nq && d <= rad[j];
+                const uint64_t m = __ballot(hit);
+                if (m) {
+                    const int leader = __builtin_ctzll(m);
+                    uint32_t b0 = 0;
+                    if (lane == leader) b0 = atomicAdd(a.rcnt + id[j], (uint32_t)__popcll(m));
+                    b0 = (uint32_t)__shfl((int)b0, leader, kWave);
+                    const uint32_t slot = b0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (hit && slot < a.cap) a.keys[(uint64_t)id[j] * a.cap + slot] = dist_key(d, myrow);
+                }
+                acc[j] = -0.0f;
+                mx[j] = 0.0f;
+            }
+            ch = 0;
+            tile += gridDim.x;
+            myrow = idn;
+            idn = id_at((uint64_t)tile + gridDim.x);
+            mag_a = a.na[myrow];
         } else {
             ++ch;
         }
@@ -2203,6 +2347,26 @@ hipError_t launch_range_scan(const RangeArgs& a, uint32_t grid, hipStream_t s) {
     else if (a.nqf <= 2) hipLaunchKernelGGL(k_range_scan<2>, dim3(grid), dim3(256), 0, s, a);
     else if (a.nqf <= 4) hipLaunchKernelGGL(k_range_scan<4>, dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_range_scan<8>, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_route(const uint32_t* to_list, const float* radius, uint32_t nq, float* tau,
+                              uint32_t* scan_list, uint32_t* status, hipStream_t s) {
+    if (!nq) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_range_route, dim3(1), dim3(1024), 0, s, to_list, radius, nq, tau, scan_list, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_scan_list_groups(const RangeListArgs& a, uint32_t grid, hipStream_t s) {
+    if (!a.groups || a.groups > 65535 || !grid || !a.cap || a.ld == 0 || a.ld % 64 != 0) return hipErrorInvalidValue;
+    const dim3 g(grid, a.groups);
+    switch (a.qf) {
+        case 1: hipLaunchKernelGGL(k_range_scan_list<1>, g, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_range_scan_list<2>, g, dim3(256), 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_range_scan_list<4>, g, dim3(256), 0, s, a); break;
+        case 8: hipLaunchKernelGGL(k_range_scan_list<8>, g, dim3(256), 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -609,6 +609,29 @@ __global__ __launch_bounds__(256) void k_mask_scatter(const uint64_t* __restrict
     }
 }
 
+// blockIdx.y = the segment (the masked range search): the ids of rank me.first ..
+// me.first + me.n_list - 1 of mask me.mask, ascending, at list + me.off -- k_mask_scatter with a
+// lower bound, so that a list longer than the chunk budget is built piece by piece.
+__global__ __launch_bounds__(256) void k_mask_scatter_seg(const uint64_t* __restrict__ allow, uint64_t words,
+                                                          uint64_t n, const uint64_t* __restrict__ dead,
+                                                          const uint32_t* __restrict__ blk, uint32_t stride,
+                                                          const MaskSegDesc* __restrict__ d,
+                                                          uint32_t* __restrict__ list) {
+    __shared__ uint32_t s_wave[4];
+    const MaskSegDesc me = d[blockIdx.y];
+    const uint64_t w = (uint64_t)blockIdx.x * kMaskBlockWords + threadIdx.x;
+    uint64_t x = mask_bits(mask_of(allow, me.mask, words), dead, w, n);
+    uint32_t total;
+    uint32_t pos = blk[(uint64_t)me.mask * stride + blockIdx.x] + block_exclusive_256((uint32_t)__popcll(x), s_wave, &total);
+    uint32_t* out = list + me.off;
+    while (x) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(x);
+        x &= x - 1;
+        if (pos >= me.first && pos - me.first < me.n_list) out[pos - me.first] = (uint32_t)(w * 64 + b);
+        ++pos;
+    }
+}
+
 // One wave per query: cand[q][0 .. cnt[q]) compacted in place to the keys whose row the query's
 // mask (query_mask[q]; query_mask = nullptr: mask 0 for every query) allows and no tombstone
 // removes, cnt[q] rewritten; raw[q] keeps the emitted count.  A chunk of 64 keys is read before
@@ -1070,6 +1093,17 @@ hipError_t launch_mask_groups_scatter(const uint64_t* allow, uint64_t words, uin
         const uint32_t l = n_lists - l0 < kGridYMax ? n_lists - l0 : kGridYMax;
         hipLaunchKernelGGL(k_mask_scatter, dim3(n_blk, l), dim3(256), 0, s, allow, words, n, dead, blk, n_blk + 1, d + l0,
                            MaskListDesc{}, list);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_mask_groups_scatter_seg(const uint64_t* allow, uint64_t words, uint64_t n, const uint64_t* dead,
+                                          const uint32_t* blk, const MaskSegDesc* d, uint32_t n_segs, uint32_t* list,
+                                          hipStream_t s) {
+    const uint32_t n_blk = mask_blocks(n);
+    for (uint32_t l0 = 0; l0 < n_segs; l0 += kGridYMax) {
+        const uint32_t l = n_segs - l0 < kGridYMax ? n_segs - l0 : kGridYMax;
+        hipLaunchKernelGGL(k_mask_scatter_seg, dim3(n_blk, l), dim3(256), 0, s, allow, words, n, dead, blk, n_blk + 1,
+                           d + l0, list);
     }
     return hipGetLastError();
 }

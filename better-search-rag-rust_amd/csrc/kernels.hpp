@@ -522,6 +522,9 @@ struct RangeArgs {
     // width -- 1, 2, 4 or 8 -- must be valid ids, those past nqf count nothing)
     const int32_t* qids;
     uint32_t nqf;
+    // the rescore behind a mask cut (optional): the emitted counts before the cut, summed into
+    // status[kStEmitted] in cnt's place
+    const uint32_t* emit_cnt;
 };
 // One workgroup per query over its emitted rows: the reference distance of every listed row; the
 // live rows with d <= radius[q] become the query's list, their number rcnt[q].
@@ -536,6 +539,45 @@ hipError_t launch_range_scan(const RangeArgs& a, uint32_t grid, hipStream_t s);
 hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint32_t cap, uint32_t nq,
                                uint32_t capacity, uint64_t offset, uint64_t* out_idx, float* out_dist,
                                uint32_t* out_count, hipStream_t s);
+
+// ---- masked range search (bsr_local_range_search_masked) ------------------------
+// The routing behind launch_range_tau: a query with to_list[q] != 0 (device, [nq]) is answered by
+// the list scan by design -- tau[q] = +inf, and q appended to scan_list (status[kStFail] and
+// status[kStFail2] counting it) unless launch_range_tau listed it already or its radius is < 0 or
+// NaN.  Afterwards every query is on scan_list at most once.  One workgroup.
+hipError_t launch_range_route(const uint32_t* to_list, const float* radius, uint32_t nq, float* tau,
+                              uint32_t* scan_list, uint32_t* status, hipStream_t s);
+// The range over row lists: launch_scan_list_groups' gather with launch_range_scan's epilogue.
+// Group y (blockIdx.y) walks the grp[y].n_list ids at list + grp[y].off (local row ids, each < n;
+// the list holds allowed live rows only -- no mask and no tombstone is read) for the qf queries
+// qids[y * qf ..] (qf one of 1, 2, 4, 8; the first grp[y].nq count, the rest are padding ids of the
+// same mask): every listed row with d <= radius[id] claims a slot of keys[id] by an atomic add on
+// rcnt[id] and stores its key when the slot is below cap; the count stays exact beyond that.  rcnt
+// of every scanned query is zero before its first launch; a list split over several launches
+// accumulates.  grid: scan_grid_for(the launch's longest list).
+struct RangeListArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    const float* na;            // row magnitudes (read, never recomputed)
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const float* radius;        // [nq]
+    const uint32_t* list;       // the launch's row lists
+    const ScanGroupDesc* grp;   // [groups]
+    uint32_t groups, qf;
+    const int32_t* qids;        // [groups][qf]
+    uint64_t* keys;             // [nq][cap]
+    uint32_t* rcnt;             // [nq]
+    uint32_t cap;
+};
+hipError_t launch_range_scan_list_groups(const RangeListArgs& a, uint32_t grid, hipStream_t s);
+// A segment of a mask's row list (a list split over chunks): the ids of rank first .. first + n_list
+// - 1 among the allowed live rows of mask `mask`, ascending, at list + off.  blk: the block prefixes
+// of launch_mask_groups_count.
+struct MaskSegDesc { uint64_t off; uint32_t mask, first, n_list, pad_; };
+hipError_t launch_mask_groups_scatter_seg(const uint64_t* allow, uint64_t words, uint64_t n, const uint64_t* dead,
+                                          const uint32_t* blk, const MaskSegDesc* d, uint32_t n_segs, uint32_t* list,
+                                          hipStream_t s);
 
 uint32_t scan_grid_for(uint64_t n);
 

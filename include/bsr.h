@@ -336,15 +336,72 @@ int bsr_local_top_k_masked_groups(bsr_index* ix, const float* queries, uint32_t 
  * when any query was answered by the scan; n_emitted = the emitted keys of the batch;
  * n_exact_direct = the queries sent to the scan by design; n_fallback = the queries whose emitted
  * list overflowed.
- * Out of scope: an allow mask combined with a radius; a multi-rank range search (every rank calls
- * this on its shard and the caller concatenates: ranges need no merge); a CSR (compressed sparse
- * row) output. */
+ * Out of scope: a multi-rank range search (every rank calls this on its shard and the caller
+ * concatenates: ranges need no merge); a CSR (compressed sparse row) output.  An allow mask
+ * combined with a radius: bsr_local_range_search_masked, below. */
 #define BSR_RANGE_MAX_RESULTS 4096u
 int bsr_local_range_search(bsr_index* ix, const float* queries, uint32_t n_queries,
                            const float* radius,            /* [n_queries], host or device */
                            uint32_t capacity,              /* result slots per query, 1..BSR_RANGE_MAX_RESULTS */
                            uint64_t* out_idx, float* out_dist,   /* [n_queries][capacity] */
                            uint32_t* out_count);                 /* [n_queries] */
+
+/* ---- masked range search: a radius and an allow mask in one call ("every chunk of tenant T
+ * within distance r").  bsr_local_range_search's contract over bsr_local_top_k_masked_groups'
+ * masks, word for word where they overlap:
+ * allow is [n_masks][allow_words] bitsets (allow_words must equal ceil(n / 64), bits at positions
+ * >= n are ignored); query_mask[q] < n_masks names query q's mask; query_mask == NULL is legal only
+ * when n_masks == 1, and every query then uses mask 0.  A mask that no query names is legal.
+ * out_count[q] = the number of rows that are in q's mask, not deleted, and whose reference
+ * distance is <= radius[q] -- always exact, also above `capacity`.
+ *   out_count[q] <= capacity: exactly those rows, (distance asc, global index asc), the
+ *     reference's f32 bits, then (~0, +inf);
+ *   out_count[q] >  capacity: every slot of row q is (~0, +inf).
+ * radius[q] < 0: count 0.  radius[q] >= 2 or +inf: count = A_g, the live rows mask g allows.
+ * A_g = 0 is not an error.
+ * queries, radius, allow, query_mask and the three outputs are, independently, host or device
+ * pointers, detected per call.  Never graph-replayed; the plain search's graphs are left alone.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; capacity 0 or above
+ *      BSR_RANGE_MAX_RESULTS; n_masks == 0; an unknown mode; with n_queries > 0 a null radius,
+ *      queries, output or allow; a null query_mask with n_masks > 1;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. BSR_E_INVALID: allow_words != ceil(n / 64); a NaN in a host radius array;
+ *   4. n_queries = 0: BSR_OK;
+ *   5. BSR_E_INVALID, checked on the device: a query_mask entry >= n_masks (found before any mask
+ *      is indexed with it);
+ *   6. BSR_E_NONFINITE: a non-finite query; BSR_E_INVALID: a NaN in a device radius array -- both
+ *      read from the batch's status words, before any result is written.
+ * An empty shard: every count 0.
+ * mode applies per mask group, with A_g and the number of queries that name the mask:
+ *   BSR_MASK_FILTER  the group's queries go through the int8 filter with the threshold
+ *                    bsr_local_range_search derives from the radius -- it does not depend on the
+ *                    mask, so there is no lower bound on A_g / n -- their emitted lists are cut by
+ *                    the mask and the survivors rescored exactly.  Possible whenever
+ *                    bsr_local_range_search would filter; otherwise the list scan.  A query the
+ *                    threshold cannot serve (a zero / tiny / huge query, a radius near 1 or above),
+ *                    or whose emitted list overflowed, takes the list scan on its own;
+ *   BSR_MASK_LIST    every query takes the list scan: an exact range over the list of its mask's
+ *                    live rows, cost proportional to A_g;
+ *   BSR_MASK_AUTO    per group: the list where bsr_local_top_k_masked's rule prefers it, or where
+ *                    A_g / n < capacity / (2 L), L = min(8192, max(1024, 2 capacity)) the keys of
+ *                    an emitted list -- 1/8 up to 512 slots: results
+ *                    that about fill their capacity then overflow the emitted lists (the filter
+ *                    emits from the whole shard) and would pay both paths.
+ * The full-shard scan never runs here.  bsr_search_stats: search_path carries BSR_PATH_RANGE,
+ * BSR_PATH_MASK_FILTER when the filter pass ran, BSR_PATH_MASK_LIST when any query was answered
+ * by the list scan, BSR_PATH_MASK_GROUPS when a query_mask was given, never BSR_PATH_RANGE_SCAN;
+ * n_exact_direct = the queries sent to the list scan by design (by mode, by AUTO, or because they
+ * cannot filter), n_fallback = the queries whose emitted list overflowed, n_emitted = the emitted
+ * keys before the cut.  The row lists are built in chunks of at most BSR_MASK_LIST_BUDGET bytes
+ * of ids (a long list is split over chunks).
+ * Out of scope: a multi-rank masked range search (every rank calls this on its shard and the
+ * caller concatenates); a CSR output. */
+int bsr_local_range_search_masked(bsr_index* ix, const float* queries, uint32_t n_queries,
+                                  const float* radius, uint32_t capacity,
+                                  const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                  const uint32_t* query_mask, uint32_t mode,
+                                  uint64_t* out_idx, float* out_dist, uint32_t* out_count);
 
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]
