@@ -60,6 +60,7 @@ BSR_PATH_MASK_FILTER = 256  # masked search: int8 filter, emitted lists cut by t
 BSR_PATH_MASK_GROUPS = 512  # bsr_local_top_k_masked_groups ran (with the MASK_LIST / MASK_FILTER bits)
 BSR_PATH_RANGE = 1024       # bsr_local_range_search ran
 BSR_PATH_RANGE_SCAN = 2048  # ... and a query of the batch was answered by the exact range scan
+BSR_PATH_MMR = 4096         # bsr_local_top_k_mmr ran (with the bits of the candidate search)
 BSR_RANGE_MAX_RESULTS = 4096  # result slots per query of a range search (include/bsr.h)
 BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
 BSR_MASK_LIST = 1
@@ -146,6 +147,8 @@ def lib() -> ctypes.CDLL:
         "bsr_local_top_k_masked_groups": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_local_range_search": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P, _P]),
         "bsr_local_range_search_masked": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
+        "bsr_local_top_k_mmr": (ctypes.c_int, [_P, _P, u32, u32, u32, ctypes.c_float, _P, u64, u32, _P, u32, _P, _P,
+                                               _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
         "bsr_comm_init": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(_P)]),
@@ -169,7 +172,7 @@ def lib() -> ctypes.CDLL:
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
-                "bsr_local_range_search_masked"}
+                "bsr_local_range_search_masked", "bsr_local_top_k_mmr"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -626,6 +629,72 @@ class Index:
                                                    _ptr(allow_words), int(shape[-1]), n_masks, _ptr(query_mask),
                                                    _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist),
                                                    _ptr(out_count)))
+
+    def mmr_search(self, queries, k: int, fetch_k=None, lambda_mult: float = 0.5, allow_mask=None, allow_ids=None,
+                   allow_masks=None, query_mask=None, mask_mode="auto", return_rank: bool = False):
+        """A diversified top-k by maximal marginal relevance (bsr_local_top_k_mmr) -> (idx [Q,k] u64,
+        dist [Q,k] f32, count [Q] u32[, rank [Q,k] u32]).  The exact fetch_k nearest rows of each
+        query are the candidates (fetch_k defaults to min(max_k, max(20, 4 k))); k of them are picked
+        greedily, the nearest first, then the one with the largest (1 - lambda_mult) * (distance to
+        the nearest pick) - lambda_mult * (distance to the query).  Rows are in selection order: idx
+        the global index, dist the distance to the query, rank the position in the candidate list.
+        lambda_mult = 1 is local_top_k(k); 0 is farthest-first after the top-1.
+        allow_mask / allow_ids, or allow_masks with query_mask, and mask_mode: as range_search's."""
+        one = allow_mask is not None or allow_ids is not None
+        if one and (allow_masks is not None or query_mask is not None):
+            raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
+        if (allow_masks is None) != (query_mask is None):
+            raise BsrError(-1, "allow_masks and query_mask go together")
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
+        nq = q.shape[0]
+        k = int(k)
+        fk = min(self.max_k, max(20, 4 * k)) if fetch_k is None else int(fetch_k)
+        if k < 1 or k > fk or fk > self.max_k:
+            raise BsrError(-1, f"k={k}, fetch_k={fk} outside 1 <= k <= fetch_k <= max_k={self.max_k}")
+        lam = float(lambda_mult)
+        if not 0.0 <= lam <= 1.0:  # (a NaN fails both comparisons)
+            raise BsrError(-1, f"lambda_mult={lam} outside [0, 1]")
+        oi = np.empty((nq, k), np.uint64)
+        od = np.empty((nq, k), np.float32)
+        oc = np.empty(nq, np.uint32)
+        orank = np.empty((nq, k), np.uint32) if return_rank else None
+        if not one and allow_masks is None:
+            wp, nw, n_masks, qm = None, 0, 0, None
+        else:
+            if one:
+                w, nw = self._allow_words(allow_mask, allow_ids)
+                n_masks, qm = 1, None
+            else:
+                w, n_masks, nw = self._allow_group_words(allow_masks)
+                qm = self._query_mask_ids(query_mask, nq)
+            # (an empty shard's masks have no words: a valid, non-null pointer all the same)
+            wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
+        _check(lib().bsr_local_top_k_mmr(self._h, _ptr(q), nq, k, fk, lam, wp, nw, n_masks, _ptr(qm),
+                                         _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(orank), _ptr(oc)))
+        return (oi, od, oc, orank) if return_rank else (oi, od, oc)
+
+    def mmr_search_device(self, queries, nq: int, k: int, fetch_k: int, lambda_mult: float, out_idx, out_dist,
+                          out_count, out_rank=None, allow_words=None, query_mask=None, mask_mode="auto"):
+        """Zero-copy variant of mmr_search on caller buffers (torch tensors, numpy arrays or raw
+        pointers, each host or device): queries [nq][dim] f32, out_idx / out_dist / out_rank
+        (optional) [nq][k], out_count [nq].  allow_words: the packed allow masks, [G][ceil(n / 64)]
+        uint64 with query_mask [nq] 32-bit mask ids, or [ceil(n / 64)] -- one mask, no query_mask."""
+        if allow_words is None:
+            if query_mask is not None:
+                raise BsrError(-1, "a query_mask needs allow_words")
+            wp, nw, n_masks = None, 0, 0
+        else:
+            shape = tuple(allow_words.shape)
+            if len(shape) not in (1, 2):
+                raise BsrError(-1, "packed allow masks have shape [G][words] or [words]")
+            wp, nw, n_masks = _ptr(allow_words), int(shape[-1]), int(shape[0]) if len(shape) == 2 else 1
+        _check(lib().bsr_local_top_k_mmr(self._h, _ptr(queries), nq, k, fetch_k, float(lambda_mult), wp, nw, n_masks,
+                                         _ptr(query_mask), _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist),
+                                         _ptr(out_rank), _ptr(out_count)))
 
     def _allow_group_words(self, allow_masks):
         """(buffer, masks, words per mask) of a grouped search's allow masks: a bool array [G][n]

@@ -2470,6 +2470,88 @@ int bsr_local_range_search_masked_impl(bsr_index* ix, const float* queries, uint
     return BSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// MMR search (bsr_local_top_k_mmr)
+// ---------------------------------------------------------------------------------------
+int bsr_index::mmr_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k, float lambda,
+                                 const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                 const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                 uint32_t* out_rank, uint32_t* out_count) {
+    BSR_HIP(hipSetDevice(device));
+    // The stage's own result rows first: an allocation after the candidate search would fall
+    // between the capture of its graph and the replay (the key carries the allocation generation).
+    const size_t nk = (size_t)nq * k;
+    BSR_TRY(mmr_idx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(mmr_dist.ensure(nk * sizeof(float)));
+    BSR_TRY(mmr_rank.ensure(nk * sizeof(uint32_t)));
+    BSR_TRY(mmr_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    // The candidates: the search itself with k = fetch_k, run to completion -- the exact rounds of
+    // its uncertified queries and the thresholded rerun come after its host wait, so its lists are
+    // final in d_idx / d_dist / d_cnt only once it returns.
+    if (!allow) BSR_TRY(search_device(queries, nq, fetch_k));
+    else if (n_masks == 1 && !query_mask) BSR_TRY(search_device_masked(queries, nq, fetch_k, allow, allow_words, mode));
+    else BSR_TRY(search_device_masked_groups(queries, nq, fetch_k, allow, allow_words, n_masks, query_mask, mode));
+    stats.search_path |= BSR_PATH_MMR;
+    // The selection, launched directly (never captured; the packed result's status words are not
+    // its business): straight into the caller's arrays when they are all on the device, else into
+    // the index's own and copied out.
+    const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count) &&
+                         (!out_rank || is_device_ptr(out_rank));
+    MmrArgs ma{};
+    ma.rows = rows.as<float>();
+    ma.ld = ld;
+    ma.dim = dim;
+    ma.n = n;
+    ma.offset = global_offset;
+    ma.na = na.as<float>();
+    ma.cand_idx = d_idx;
+    ma.cand_dist = d_dist;
+    ma.cand_cnt = d_cnt;
+    ma.nq = nq;
+    ma.fetch_k = fetch_k;
+    ma.k = k;
+    ma.lambda = lambda;
+    ma.out_idx = out_dev ? out_idx : mmr_idx.as<uint64_t>();
+    ma.out_dist = out_dev ? out_dist : mmr_dist.as<float>();
+    ma.out_rank = out_dev ? out_rank : mmr_rank.as<uint32_t>();
+    ma.out_count = out_dev ? out_count : mmr_cnt.as<uint32_t>();
+    BSR_HIP(launch_mmr_select(ma, stream));
+    if (!out_dev) {
+        BSR_HIP(hipMemcpyAsync(out_idx, ma.out_idx, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, ma.out_dist, nk * sizeof(float), hipMemcpyDefault, stream));
+        if (out_rank) BSR_HIP(hipMemcpyAsync(out_rank, ma.out_rank, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, ma.out_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_k_mmr_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                             float lambda, const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                             const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                             uint32_t* out_rank, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > fetch_k || fetch_k > ix->cfg.max_k)
+        return set_error(BSR_E_INVALID, "k=%u, fetch_k=%u outside 1 <= k <= fetch_k <= max_k=%u", k, fetch_k,
+                         ix->cfg.max_k);
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return set_error(BSR_E_INVALID, "lambda=%g outside [0, 1]", (double)lambda);
+    if (!allow && (n_masks != 0 || query_mask))
+        return set_error(BSR_E_INVALID, "n_masks = %u or a query_mask without allow masks", n_masks);
+    if (allow && n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 with allow masks");
+    if (allow && !query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (nq == 0) return BSR_OK;
+    BSR_TRY(ix->mmr_search_device(queries, nq, k, fetch_k, lambda, allow, allow_words, n_masks, query_mask, mode,
+                                  out_idx, out_dist, out_rank, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
 int bsr_index_collect_profile_impl(bsr_index* ix) {
     collect_profile(ix);
     return BSR_OK;

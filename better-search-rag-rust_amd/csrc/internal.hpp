@@ -257,6 +257,15 @@ struct bsr_index {
     std::vector<uint32_t> h_rng_route;
     std::vector<bsr::MaskSegDesc> h_rng_segs;
 
+    // MMR search (bsr_local_top_k_mmr): the candidate search with k = fetch_k (plain,
+    // masked or grouped, by the mask arguments) run to completion, then the selection kernel over the
+    // lists it left in d_idx / d_dist / d_cnt -- launched directly, never captured -- into the
+    // caller's arrays, host or device (out_rank nullable).  The candidate search keeps its graphs.
+    int mmr_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k, float lambda,
+                          const uint64_t* allow, uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
+                          uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_rank, uint32_t* out_count);
+    bsr::DevBuf mmr_idx, mmr_dist, mmr_rank, mmr_cnt;  // the picks [nq][k], their counts [nq]
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

@@ -2032,6 +2032,120 @@ __global__ __launch_bounds__(256) void k_range_finish(const uint64_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------
+// MMR selection (bsr_local_top_k_mmr): k of a query's m <= 256 exact candidates,
+// picked greedily -- the candidate with the largest (mu * min distance to a picked row) - (lam *
+// distance to the query), each product and the difference rounded on its own.
+// ------------------------------------------------------------------------------------
+// One workgroup of four waves per query; candidate position w*64 + lane belongs to one lane for the
+// whole kernel, which keeps its row, dq, mind and picked flag in registers.  Per pick after the
+// first: the row picked last goes into the workgroup's LDS vector, every wave that still has an
+// unpicked candidate streams its 64 rows against it -- k_range_rescore's loop (load_cand_chunk, two
+// chunks in flight, seq_chunk, finish_distance with the two stored magnitudes), the picked row in
+// the query's place -- and the smallest (score desc, position asc) key wins: a butterfly per wave,
+// then four entries in LDS.  Column t of the pair distances exists only once pick t-1 is known, so
+// the work is k * m distances per query.  The first pick is the lowest valid position.
+__global__ __launch_bounds__(256) void k_mmr_select(MmrArgs a) {
+    constexpr int W = 4, STAGE = 64 * 68, QMAX = 1024;
+    __shared__ __attribute__((aligned(16))) float lds_all[W * STAGE + QMAX];
+    __shared__ uint64_t s_best[W];
+    __shared__ uint32_t s_brow[W];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float* const lds = lds_all + w * STAGE;
+    float* const ldp = lds_all + W * STAGE;
+    const uint32_t q = blockIdx.x, pos = threadIdx.x;
+    const uint32_t ld = a.ld, dim = a.dim, nch = ld / 64, k = a.k;
+    const uint32_t m = a.cand_cnt[q] < a.fetch_k ? a.cand_cnt[q] : a.fetch_k;
+    const uint64_t gidx = pos < m ? a.cand_idx[(uint64_t)q * a.fetch_k + pos] : ~0ull;
+    // (an id outside the shard is no candidate: no row is read through it)
+    const bool valid = pos < m && gidx >= a.offset && gidx - a.offset < a.n;
+    const uint32_t myrow = valid ? (uint32_t)(gidx - a.offset) : 0u;
+    const float dq = valid ? a.cand_dist[(uint64_t)q * a.fetch_k + pos] : INFINITY;
+    const float lam = a.lambda, mu = 1.0f - lam;
+    const float mag_a = valid ? a.na[myrow] : 0.0f;
+    const bool qlds = ld <= (uint32_t)QMAX;  // (longer rows read the picked row from global memory)
+    const float* const rows = a.rows;
+    uint32_t lrow[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) lrow[i] = (uint32_t)__shfl((int)myrow, (i * 64 + lane) >> 4, kWave);
+    float mind = INFINITY;
+    bool picked = !valid;
+    uint32_t prow = 0, t = 0;
+    uint64_t* const oi = a.out_idx + (uint64_t)q * k;
+    float* const od = a.out_dist + (uint64_t)q * k;
+    uint32_t* const orank = a.out_rank ? a.out_rank + (uint64_t)q * k : nullptr;
+    for (; t < k; ++t) {
+        uint64_t key = kKeyNone;
+        if (t == 0) {
+            if (valid) key = score_key(0.0f, pos);
+        } else {
+            const float* const prow_g = rows + (uint64_t)prow * ld;
+            if (qlds)
+                for (uint32_t cc = threadIdx.x; cc < ld; cc += 64 * W) ldp[cc] = prow_g[cc];
+            __syncthreads();
+            if (__ballot(!picked)) {  // (a wave with nothing left to score skips the walk, not the barriers)
+                float acc[1] = {-0.0f}, mx[1] = {0.0f};
+                auto step = [&](f32x4_t (&pre)[16], uint32_t ch) {
+                    wave_sync();
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int L16 = i * 64 + lane;
+                        *reinterpret_cast<f32x4_t*>(lds + (L16 >> 4) * 68 + (L16 & 15) * 4) = pre[i];
+                    }
+                    wave_sync();
+                    if (ch + 2 < nch) load_cand_chunk(pre, rows, ld, lrow, ch + 2, lane);
+                    const float* const bb[1] = {(qlds ? ldp : prow_g) + ch * 64};
+                    const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+                    seq_chunk<1>(lds + lane * 68, bb, nvalid, acc, mx);
+                };
+                f32x4_t preA[16], preB[16];
+                load_cand_chunk(preA, rows, ld, lrow, 0, lane);
+                if (nch > 1) load_cand_chunk(preB, rows, ld, lrow, 1, lane);
+                for (uint32_t ch = 0; ch < nch; ch += 2) {
+                    step(preA, ch);
+                    if (ch + 1 < nch) step(preB, ch + 1);
+                }
+                if (!picked) {
+                    mind = fminf(mind, finish_distance(acc[0], mx[0], mag_a, a.na[prow]));
+                    const float gain = mu * mind, cost = lam * dq;
+                    key = score_key(gain - cost, pos);
+                }
+            }
+        }
+        uint64_t wb = key;
+#pragma unroll
+        for (int j = 32; j > 0; j >>= 1) {
+            const uint64_t y = shfl_xor64(wb, j);
+            wb = y < wb ? y : wb;
+        }
+        if (key == wb && (key != kKeyNone || lane == 0)) {  // (the keys of a wave differ: one lane)
+            s_best[w] = wb;
+            s_brow[w] = myrow;
+        }
+        __syncthreads();
+        uint64_t best = s_best[0];
+        int bw = 0;
+#pragma unroll
+        for (int i = 1; i < W; ++i)
+            if (s_best[i] < best) { best = s_best[i]; bw = i; }
+        if (best == kKeyNone) break;  // (uniform over the workgroup: no candidate is left)
+        prow = s_brow[bw];
+        if (!picked && key == best) {
+            picked = true;
+            oi[t] = gidx;
+            od[t] = dq;
+            if (orank) orank[t] = pos;
+        }
+    }
+    // (t picks were made: the count, and padding behind them)
+    if (threadIdx.x == 0) a.out_count[q] = t;
+    for (uint32_t i = t + threadIdx.x; i < k; i += 64 * W) {
+        oi[i] = ~0ull;
+        od[i] = INFINITY;
+        if (orank) orank[i] = ~0u;
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Launchers
 // ------------------------------------------------------------------------------------
 #ifdef BSR_RESCORE_STAMPS
@@ -2376,6 +2490,15 @@ hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint3
     if (!nq || !capacity || capacity > kRangeMaxResults || cap < capacity) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_range_finish, dim3(nq), dim3(256), 0, s, keys, rcnt, cap, capacity, offset, out_idx,
                        out_dist, out_count);
+    return hipGetLastError();
+}
+
+// ---- MMR selection -------------------------------------------------------------------------
+hipError_t launch_mmr_select(const MmrArgs& a, hipStream_t s) {
+    if (!a.nq || !a.k || a.k > a.fetch_k || a.fetch_k > kMmrMaxFetch || a.ld == 0 || a.ld % 64 != 0 ||
+        !(a.lambda >= 0.0f && a.lambda <= 1.0f))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mmr_select, dim3(a.nq), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -579,6 +579,36 @@ hipError_t launch_mask_groups_scatter_seg(const uint64_t* allow, uint64_t words,
                                           const uint32_t* blk, const MaskSegDesc* d, uint32_t n_segs, uint32_t* list,
                                           hipStream_t s);
 
+// ---- MMR selection (bsr_local_top_k_mmr; k_exact.hip) ---------------------------
+// One workgroup per query picks k of its candidates greedily.  The candidates are the first
+// m = min(cand_cnt[q], fetch_k) slots of row q of cand_idx / cand_dist [nq][fetch_k] (global ids and
+// query distances dq, as a search leaves them; the kernel takes the slots as they stand -- position
+// = slot -- and an id outside [offset, offset + n) is no candidate).  D(i, j) is the reference's
+// distance of the stored rows of positions i and j with the stored magnitudes na.  The first pick is
+// the lowest candidate position; every later one the unpicked position with the largest
+// (mu * mind_i) - (lambda * dq_i), mu = 1.0f - lambda, mind_i = the smallest D(i, p) over the
+// picks p so far (fminf, from +inf), every operation a rounded f32 one; ties go to the lower
+// position.  Row q of out_idx / out_dist / out_rank (nullable) [nq][k] holds the picks in selection
+// order -- global id, dq, position -- then (~0, +inf, ~0u); out_count[q] = the number of picks,
+// min(k, candidates).  fetch_k <= kMmrMaxFetch, 1 <= k <= fetch_k, lambda in [0, 1].
+constexpr uint32_t kMmrMaxFetch = 256;
+struct MmrArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t n, offset;         // rows of the shard; the global id of row 0
+    const float* na;            // row magnitudes (read, never recomputed)
+    const uint64_t* cand_idx;   // [nq][fetch_k]
+    const float* cand_dist;     // [nq][fetch_k]
+    const uint32_t* cand_cnt;   // [nq]
+    uint32_t nq, fetch_k, k;
+    float lambda;
+    uint64_t* out_idx;          // [nq][k]
+    float* out_dist;            // [nq][k]
+    uint32_t* out_rank;         // [nq][k], nullable
+    uint32_t* out_count;        // [nq]
+};
+hipError_t launch_mmr_select(const MmrArgs& a, hipStream_t s);
+
 uint32_t scan_grid_for(uint64_t n);
 
 }  // namespace bsr

@@ -122,6 +122,7 @@ typedef struct {
 #define BSR_PATH_MASK_GROUPS 512u /* bsr_local_top_k_masked_groups ran (with MASK_LIST / MASK_FILTER bits) */
 #define BSR_PATH_RANGE      1024u /* bsr_local_range_search ran */
 #define BSR_PATH_RANGE_SCAN 2048u /* ... and a query of the batch was answered by the exact range scan */
+#define BSR_PATH_MMR        4096u /* bsr_local_top_k_mmr ran (with the bits of the candidate search) */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -402,6 +403,57 @@ int bsr_local_range_search_masked(bsr_index* ix, const float* queries, uint32_t 
                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                                   const uint32_t* query_mask, uint32_t mode,
                                   uint64_t* out_idx, float* out_dist, uint32_t* out_count);
+
+/* ---- MMR search: a diversified top-k (maximal marginal relevance) over the exact candidates.
+ * For a query whose neighbourhood is a cluster of near-duplicates the exact top-k is k copies of
+ * one passage; MMR fetches fetch_k candidates and picks k of them greedily, trading closeness to
+ * the query against closeness to what is already picked.  The result is one bit pattern
+ * (DESIGN.md §18).  For one query:
+ *   1. the candidates are exactly what bsr_local_top_k returns for k = fetch_k (with allow masks:
+ *      bsr_local_top_k_masked / bsr_local_top_k_masked_groups): m = min(fetch_k, allowed live rows)
+ *      positions 0 .. m-1 in (distance asc, global index asc) order, each with its query distance
+ *      dq_i, the reference's f32 bits;
+ *   2. D(i, j) is the reference's cosine_distance of the stored rows of positions i and j (the
+ *      sequential f32 dot in index order, the max |a - b| identical shortcut, the zero-magnitude
+ *      rule, the stored magnitudes); symmetric bit for bit; on a bf16 index the stored rows are the
+ *      widened f32 values;
+ *   3. lam = lambda as f32, mu = 1.0f - lam (one f32 subtraction);
+ *   4. the first pick is position 0, the nearest row;
+ *   5. every later pick: for each unpicked i, mind_i = fminf(mind_i, D(i, last pick)) (from +inf),
+ *      score_i = (mu * mind_i) - (lam * dq_i) -- two f32 multiplies and one f32 subtraction, each
+ *      rounded on its own, no FMA -- and the largest score wins, ties to the smallest position;
+ *   6. out_count[q] = min(k, m); row q holds the picks in selection order: out_idx the global
+ *      index, out_dist dq of the pick, out_rank (nullable) its position in the candidate list;
+ *      past the count (~0, +inf, ~0u).
+ * lambda = 1 returns bsr_local_top_k(k) bit for bit; pick 0 is always the top-1; with k = fetch_k
+ * the output is a permutation of the candidate list; exact duplicates of a picked row get mind = 0
+ * and drop to the bottom.
+ * allow == NULL: the plain search finds the candidates (n_masks must be 0, query_mask NULL), with
+ * its captured graphs: graph_replay is 1 wherever bsr_local_top_k(n_queries, fetch_k) would replay.
+ * allow != NULL: bsr_local_range_search_masked's contract for allow, allow_words, n_masks,
+ * query_mask and mode (query_mask == NULL is legal only with n_masks == 1).
+ * 1 <= k <= fetch_k <= cfg.max_k; lambda finite and within [0, 1].  queries, the masks and the
+ * four outputs are, independently, host or device pointers, detected per call.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; k or fetch_k out of range; a NaN
+ *      or out-of-range lambda; an inconsistent mask argument set (allow NULL with n_masks != 0 or a
+ *      query_mask; allow with n_masks == 0; a null query_mask with n_masks > 1); an unknown mode;
+ *      with n_queries > 0 a null queries pointer or a null out_idx / out_dist / out_count;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. n_queries = 0: BSR_OK;
+ *   4. everything else as the candidate search reports it: allow_words != ceil(n / 64), a
+ *      query_mask entry >= n_masks, BSR_E_NONFINITE for a non-finite query, BSR_E_DIM.
+ * bsr_search_stats: search_path carries the candidate search's bits plus BSR_PATH_MMR; the other
+ * fields are the candidate search's.
+ * Out of scope: multi-rank MMR (the pair distances need rows of other ranks: run the parallel
+ * search for ids, then MMR on the rank that holds the rows); a per-query lambda; another diversity
+ * measure; returning D. */
+int bsr_local_top_k_mmr(bsr_index* ix, const float* queries, uint32_t n_queries,
+                        uint32_t k, uint32_t fetch_k, float lambda,
+                        const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                        const uint32_t* query_mask, uint32_t mode,
+                        uint64_t* out_idx, float* out_dist, uint32_t* out_rank /* nullable */,
+                        uint32_t* out_count);
 
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]
