@@ -61,6 +61,8 @@ BSR_PATH_MASK_GROUPS = 512  # bsr_local_top_k_masked_groups ran (with the MASK_L
 BSR_PATH_RANGE = 1024       # bsr_local_range_search ran
 BSR_PATH_RANGE_SCAN = 2048  # ... and a query of the batch was answered by the exact range scan
 BSR_PATH_MMR = 4096         # bsr_local_top_k_mmr ran (with the bits of the candidate search)
+BSR_PATH_COLLAPSE = 8192        # bsr_local_top_k_collapsed ran (with the bits of the candidate search)
+BSR_PATH_COLLAPSE_SCAN = 16384  # ... and a query of the batch was answered by the group scan
 BSR_RANGE_MAX_RESULTS = 4096  # result slots per query of a range search (include/bsr.h)
 BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
 BSR_MASK_LIST = 1
@@ -149,6 +151,8 @@ def lib() -> ctypes.CDLL:
         "bsr_local_range_search_masked": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_local_top_k_mmr": (ctypes.c_int, [_P, _P, u32, u32, u32, ctypes.c_float, _P, u64, u32, _P, u32, _P, _P,
                                                _P, _P]),
+        "bsr_local_top_k_collapsed": (ctypes.c_int, [_P, _P, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P, _P,
+                                                     _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
         "bsr_comm_init": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(_P)]),
@@ -172,7 +176,7 @@ def lib() -> ctypes.CDLL:
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
-                "bsr_local_range_search_masked", "bsr_local_top_k_mmr"}
+                "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -695,6 +699,100 @@ class Index:
         _check(lib().bsr_local_top_k_mmr(self._h, _ptr(queries), nq, k, fetch_k, float(lambda_mult), wp, nw, n_masks,
                                          _ptr(query_mask), _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist),
                                          _ptr(out_rank), _ptr(out_count)))
+
+    def collapsed_search(self, queries, k: int, row_group, n_groups=None, fetch_k=None, allow_mask=None,
+                         allow_ids=None, allow_masks=None, query_mask=None, mask_mode="auto",
+                         return_groups: bool = False):
+        """The exact top-k of distinct groups, the best row of each (bsr_local_top_k_collapsed) ->
+        (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32[, group [Q,k] u32]).  row_group [n] holds the
+        group (document) of every local row, each below n_groups (default: max(row_group) + 1); a
+        numpy array or integers, or a 32-bit torch tensor, host or device (then give n_groups).
+        Row q holds the heads of the k groups nearest to query q in (distance asc, index asc) order;
+        count is min(k, distinct groups among the allowed live rows).  fetch_k (default min(max_k,
+        max(4 k, 32))) is the candidate list walked first; the result does not depend on it.
+        allow_mask / allow_ids, or allow_masks with query_mask, and mask_mode: as mmr_search's."""
+        one = allow_mask is not None or allow_ids is not None
+        if one and (allow_masks is not None or query_mask is not None):
+            raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
+        if (allow_masks is None) != (query_mask is None):
+            raise BsrError(-1, "allow_masks and query_mask go together")
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
+        nq = q.shape[0]
+        k = int(k)
+        fk = min(self.max_k, max(4 * k, 32)) if fetch_k is None else int(fetch_k)
+        if k < 1 or k > fk or fk > self.max_k:
+            raise BsrError(-1, f"k={k}, fetch_k={fk} outside 1 <= k <= fetch_k <= max_k={self.max_k}")
+        rg, n_rg, ng = self._row_groups(row_group, n_groups)
+        oi = np.empty((nq, k), np.uint64)
+        od = np.empty((nq, k), np.float32)
+        oc = np.empty(nq, np.uint32)
+        og = np.empty((nq, k), np.uint32) if return_groups else None
+        if not one and allow_masks is None:
+            wp, nw, n_masks, qm = None, 0, 0, None
+        else:
+            if one:
+                w, nw = self._allow_words(allow_mask, allow_ids)
+                n_masks, qm = 1, None
+            else:
+                w, n_masks, nw = self._allow_group_words(allow_masks)
+                qm = self._query_mask_ids(query_mask, nq)
+            # (an empty shard's masks have no words: a valid, non-null pointer all the same)
+            wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
+        _check(lib().bsr_local_top_k_collapsed(self._h, _ptr(q), nq, k, fk, _ptr(rg), n_rg, ng, wp, nw, n_masks,
+                                               _ptr(qm), _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(og),
+                                               _ptr(oc)))
+        return (oi, od, oc, og) if return_groups else (oi, od, oc)
+
+    @staticmethod
+    def _row_groups(row_group, n_groups):
+        """(buffer, entries, n_groups) of a collapsed search's row_group: integers (checked and
+        converted here; n_groups defaults to max + 1) or a 32-bit torch tensor (passed through)."""
+        if hasattr(row_group, "data_ptr"):
+            if row_group.element_size() != 4 or not row_group.is_contiguous():
+                raise BsrError(-1, "a tensor row_group holds 32-bit group ids, contiguous")
+            if n_groups is None:
+                raise BsrError(-1, "a tensor row_group needs n_groups")
+            rg, n_rg = row_group, int(row_group.numel())
+        else:
+            rg = np.asarray(row_group)
+            if rg.size and (not np.issubdtype(rg.dtype, np.integer) or int(rg.min()) < 0 or int(rg.max()) > 0xFFFFFFFE):
+                raise BsrError(-1, "row_group holds group ids: integers in [0, n_groups)")
+            rg = np.ascontiguousarray(rg.reshape(-1), np.uint32)
+            n_rg = int(rg.size)
+            if n_groups is None:
+                n_groups = int(rg.max()) + 1 if n_rg else 1
+        ng = int(n_groups)
+        if ng < 1 or ng > 0xFFFFFFFF:
+            raise BsrError(-1, f"n_groups={ng} outside [1, 2^32)")
+        # (an empty shard's row_group has no entries: a null pointer is legal there)
+        return (rg if n_rg else None), n_rg, ng
+
+    def collapsed_search_device(self, queries, nq: int, k: int, fetch_k: int, row_group, n_groups: int, out_idx,
+                                out_dist, out_count, out_group=None, allow_words=None, query_mask=None,
+                                mask_mode="auto"):
+        """Zero-copy variant of collapsed_search on caller buffers (torch tensors or numpy arrays,
+        each host or device): queries [nq][dim] f32, row_group [n] 32-bit group ids,
+        out_idx / out_dist / out_group (optional) [nq][k], out_count [nq].  allow_words: the packed
+        allow masks, [G][ceil(n / 64)] uint64 with query_mask [nq] 32-bit mask ids, or
+        [ceil(n / 64)] -- one mask, no query_mask."""
+        if allow_words is None:
+            if query_mask is not None:
+                raise BsrError(-1, "a query_mask needs allow_words")
+            wp, nw, n_masks = None, 0, 0
+        else:
+            shape = tuple(allow_words.shape)
+            if len(shape) not in (1, 2):
+                raise BsrError(-1, "packed allow masks have shape [G][words] or [words]")
+            wp, nw, n_masks = _ptr(allow_words), int(shape[-1]), int(shape[0]) if len(shape) == 2 else 1
+        n_rg = int(row_group.numel()) if hasattr(row_group, "numel") else int(np.asarray(row_group).size)
+        _check(lib().bsr_local_top_k_collapsed(self._h, _ptr(queries), nq, k, fetch_k, _ptr(row_group) if n_rg else None,
+                                               n_rg, int(n_groups), wp, nw, n_masks, _ptr(query_mask),
+                                               _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_group),
+                                               _ptr(out_count)))
 
     def _allow_group_words(self, allow_masks):
         """(buffer, masks, words per mask) of a grouped search's allow masks: a bool array [G][n]

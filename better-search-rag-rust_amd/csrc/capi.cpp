@@ -47,6 +47,11 @@ int bsr_local_top_k_mmr_impl(bsr_index* ix, const float* queries, uint32_t nq, u
                              float lambda, const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                              const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
                              uint32_t* out_rank, uint32_t* out_count);
+int bsr_local_top_k_collapsed_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                   const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                   const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                   uint32_t* out_group, uint32_t* out_count);
 int bsr_index_collect_profile_impl(bsr_index* ix);
 int bsr_copy_out_impl(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist,
                       uint32_t* out_count);
@@ -390,6 +395,16 @@ int bsr_local_top_k_mmr(bsr_index* ix, const float* queries, uint32_t n_queries,
                         uint32_t* out_rank, uint32_t* out_count) {
     BSR_GUARD(bsr_local_top_k_mmr_impl(ix, queries, n_queries, k, fetch_k, lambda, allow, allow_words, n_masks,
                                        query_mask, mode, out_idx, out_dist, out_rank, out_count));
+}
+
+int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint32_t fetch_k,
+                              const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                              const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                              const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                              uint32_t* out_group, uint32_t* out_count) {
+    BSR_GUARD(bsr_local_top_k_collapsed_impl(ix, queries, n_queries, k, fetch_k, row_group, row_group_len, n_groups,
+                                             allow, allow_words, n_masks, query_mask, mode, out_idx, out_dist,
+                                             out_group, out_count));
 }
 
 // The device merge's limits (k_merge_lists: one wave per query, the concatenation in LDS).

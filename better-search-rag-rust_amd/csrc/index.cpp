@@ -2552,6 +2552,165 @@ int bsr_local_top_k_mmr_impl(bsr_index* ix, const float* queries, uint32_t nq, u
     return BSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Collapsed search (bsr_local_top_k_collapsed)
+// ---------------------------------------------------------------------------------------
+int bsr_index::collapsed_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                       const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow,
+                                       uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
+                                       uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                       uint32_t* out_count) {
+    bsr_index* ix = this;
+    BSR_HIP(hipSetDevice(device));
+    // Every buffer of the stage but the scan's tables first: an allocation after the candidate
+    // search would fall between the capture of its graph and the replay (the key carries the
+    // allocation generation), as mmr_search_device has it.
+    const size_t nk = (size_t)nq * k;
+    const uint32_t sel_grid = collapse_select_grid(n_groups);
+    BSR_TRY(col_flag.ensure(2 * sizeof(uint32_t)));
+    BSR_TRY(col_fail.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_TRY(col_qids.ensure((size_t)nq * kScanQF * sizeof(int32_t)));
+    BSR_TRY(col_keys.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(col_idx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(col_dist.ensure(nk * sizeof(float)));
+    BSR_TRY(col_group.ensure(nk * sizeof(uint32_t)));
+    BSR_TRY(col_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_TRY(part.ensure((size_t)sel_grid * kScanQF * k * sizeof(uint64_t)));
+    // The groups on the device and their check, before anything indexes a table with one.
+    uint32_t* const flag = col_flag.as<uint32_t>();  // [0]: a group id out of range; [1]: the fail list's count
+    BSR_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(uint32_t), stream));
+    const uint32_t* dgrp = nullptr;
+    if (n) {
+        BSR_TRY(on_device(ix, col_grp, row_group, (size_t)n * sizeof(uint32_t), is_device_ptr(row_group), &dgrp));
+        BSR_HIP(launch_group_check(dgrp, n, n_groups, flag, stream));
+        uint32_t bad = 0;
+        BSR_HIP(hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, stream));
+        BSR_HIP(hipStreamSynchronize(stream));
+        if (bad) return set_error(BSR_E_INVALID, "a row_group entry is >= n_groups = %u", n_groups);
+    }
+    // The candidates: the search itself with k = fetch_k, run to completion (mmr_search_device).
+    if (!allow) BSR_TRY(search_device(queries, nq, fetch_k));
+    else if (n_masks == 1 && !query_mask) BSR_TRY(search_device_masked(queries, nq, fetch_k, allow, allow_words, mode));
+    else BSR_TRY(search_device_masked_groups(queries, nq, fetch_k, allow, allow_words, n_masks, query_mask, mode));
+    stats.search_path |= BSR_PATH_COLLAPSE;
+    // The walk, straight into the caller's arrays when they are all on the device, else into the
+    // index's own, copied out at the end.
+    const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count) &&
+                         (!out_group || is_device_ptr(out_group));
+    CollapseWalkArgs wa{};
+    wa.cand_idx = d_idx;
+    wa.cand_dist = d_dist;
+    wa.cand_cnt = d_cnt;
+    wa.nq = nq;
+    wa.fetch_k = fetch_k;
+    wa.k = k;
+    wa.n = n;
+    wa.offset = global_offset;
+    wa.row_group = dgrp;
+    wa.out_idx = out_dev ? out_idx : col_idx.as<uint64_t>();
+    wa.out_dist = out_dev ? out_dist : col_dist.as<float>();
+    wa.out_group = out_dev ? out_group : col_group.as<uint32_t>();
+    wa.out_count = out_dev ? out_count : col_cnt.as<uint32_t>();
+    wa.fail = col_fail.as<uint32_t>();
+    wa.fail_cnt = flag + 1;
+    BSR_HIP(launch_collapse_walk(wa, stream));
+    uint32_t nfail = 0;
+    BSR_HIP(hipMemcpyAsync(&nfail, flag + 1, sizeof nfail, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (nfail) {
+        // The queries whose full list held fewer than k groups: the group scan, in rounds of as many
+        // queries as the table budget holds.
+        stats.search_path |= BSR_PATH_COLLAPSE_SCAN;
+        h_fail.resize(nfail);
+        BSR_HIP(hipMemcpy(h_fail.data(), col_fail.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::sort(h_fail.begin(), h_fail.end());
+        const uint64_t table = 8ull * n_groups;
+        const uint64_t budget = env_bytes("BSR_COLLAPSE_TABLE_BUDGET", 256ull << 20);
+        const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({kScanQF, budget / table, nfail}));
+        const uint32_t rounds = (nfail + per - 1) / per;
+        std::vector<int32_t> padded((size_t)rounds * kScanQF);
+        for (uint32_t r = 0; r < rounds; ++r) {
+            const uint32_t nr = std::min(per, nfail - r * per);
+            for (uint32_t i = 0; i < kScanQF; ++i)
+                padded[(size_t)r * kScanQF + i] = (int32_t)h_fail[(size_t)r * per + (i < nr ? i : 0)];
+        }
+        // (the one allocation behind the candidate search: the plain search re-captures once)
+        BSR_TRY(col_best.ensure((size_t)per * table));
+        BSR_HIP(hipMemcpyAsync(col_qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                               stream));
+        BSR_HIP(hipStreamSynchronize(stream));  // (padded is read by the copy)
+        CollapseScanArgs sa{};
+        sa.rows = rows.as<float>();
+        sa.ld = ld;
+        sa.dim = dim;
+        sa.n = n;
+        sa.na = na.as<float>();
+        sa.qf32 = qf32.as<float>();
+        sa.nb = nb.as<float>();
+        sa.dead = dead_bits();
+        sa.row_group = dgrp;
+        sa.n_groups = n_groups;
+        // (the masks where the candidate search read them: the caller's device arrays or its copies)
+        sa.allow = !allow ? nullptr : is_device_ptr(allow) ? allow : mask_dev.as<uint64_t>();
+        sa.allow_words = allow_words;
+        sa.query_mask = !allow || !query_mask ? nullptr
+                        : is_device_ptr(query_mask) ? query_mask : grp_qmask.as<uint32_t>();
+        sa.best = col_best.as<uint64_t>();
+        const uint32_t grid = scan_grid_for(n);
+        for (uint32_t r = 0; r < rounds; ++r) {
+            const uint32_t nr = std::min(per, nfail - r * per);
+            const int32_t* qid = col_qids.as<int32_t>() + (size_t)r * kScanQF;
+            sa.qids = qid;
+            sa.nqf = nr;
+            BSR_HIP(hipMemsetAsync(col_best.p, 0xff, (size_t)nr * table, stream));
+            BSR_HIP(launch_collapse_scan(sa, grid, stream));
+            BSR_HIP(launch_collapse_select(sa.best, n_groups, nr, k, sel_grid, part.as<uint64_t>(), stream));
+            BSR_HIP(launch_merge_parts(part.as<uint64_t>(), sel_grid, qid, nr, k, col_keys.as<uint64_t>(), stream));
+            BSR_HIP(launch_collapse_finish(col_keys.as<uint64_t>(), qid, nr, k, global_offset, dgrp, wa.out_idx,
+                                           wa.out_dist, wa.out_group, wa.out_count, stream));
+        }
+    }
+    if (!out_dev) {
+        BSR_HIP(hipMemcpyAsync(out_idx, wa.out_idx, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, wa.out_dist, nk * sizeof(float), hipMemcpyDefault, stream));
+        if (out_group) BSR_HIP(hipMemcpyAsync(out_group, wa.out_group, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, wa.out_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_k_collapsed_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                   const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                   const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                   uint32_t* out_group, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > fetch_k || fetch_k > ix->cfg.max_k)
+        return set_error(BSR_E_INVALID, "k=%u, fetch_k=%u outside 1 <= k <= fetch_k <= max_k=%u", k, fetch_k,
+                         ix->cfg.max_k);
+    if (n_groups == 0) return set_error(BSR_E_INVALID, "n_groups = 0");
+    if (!allow && (n_masks != 0 || query_mask))
+        return set_error(BSR_E_INVALID, "n_masks = %u or a query_mask without allow masks", n_masks);
+    if (allow && n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 with allow masks");
+    if (allow && !query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (row_group_len != ix->n)
+        return set_error(BSR_E_INVALID, "row_group_len=%llu, the index holds %llu rows", (unsigned long long)row_group_len,
+                         (unsigned long long)ix->n);
+    if (ix->n && !row_group) return set_error(BSR_E_INVALID, "null row_group");
+    if (nq == 0) return BSR_OK;
+    BSR_TRY(ix->collapsed_search_device(queries, nq, k, fetch_k, row_group, n_groups, allow, allow_words, n_masks,
+                                        query_mask, mode, out_idx, out_dist, out_group, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
 int bsr_index_collect_profile_impl(bsr_index* ix) {
     collect_profile(ix);
     return BSR_OK;

@@ -266,6 +266,23 @@ struct bsr_index {
                           uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_rank, uint32_t* out_count);
     bsr::DevBuf mmr_idx, mmr_dist, mmr_rank, mmr_cnt;  // the picks [nq][k], their counts [nq]
 
+    // Collapsed search (bsr_local_top_k_collapsed): the group check, the candidate
+    // search with k = fetch_k run to completion, the walk over its lists, and for the queries the
+    // walk could not certify the group scan in rounds -- table memset, scan, selection, merge, finish.
+    // All launched directly, never captured; the candidate search keeps its graphs.  Every buffer
+    // but the table is sized before the candidate search; the table at the first scan, and kept.
+    int collapsed_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow,
+                                uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
+                                uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_count);
+    bsr::DevBuf col_grp;    // u32 [n]: a host row_group's device copy
+    bsr::DevBuf col_flag;   // u32 [2]: the group check's flag; the fail list's count
+    bsr::DevBuf col_fail;   // u32 [nq]: the queries the walk could not certify
+    bsr::DevBuf col_qids;   // i32 [rounds][kScanQF]: their ids by scan round, each round padded
+    bsr::DevBuf col_keys;   // u64 [nq][k]: the merged keys of the scanned queries
+    bsr::DevBuf col_best;   // u64 [queries of a round][n_groups]: the scan's tables
+    bsr::DevBuf col_idx, col_dist, col_group, col_cnt;  // the result rows [nq][k], the counts [nq]
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

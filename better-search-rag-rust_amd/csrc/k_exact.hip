@@ -2146,6 +2146,238 @@ __global__ __launch_bounds__(256) void k_mmr_select(MmrArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
+// Collapsed search (bsr_local_top_k_collapsed): the best row of each of the k best
+// groups.  The walk answers a query from its exact candidate list when the list proves the answer;
+// the others take the group scan -- an atomic min per (query, group) over every row -- and a
+// selection of the k smallest table entries.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_group_check(const uint32_t* __restrict__ row_group, uint64_t n,
+                                                     uint32_t n_groups, uint32_t* __restrict__ flag) {
+    bool bad = false;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        bad |= row_group[i] >= n_groups;
+    if (__ballot(bad) && lane_id() == 0) atomicOr(flag, 1u);
+}
+
+// One wave per query, four queries per workgroup (the waves never meet: no barrier).  Position
+// s*64 + lane of the list belongs to one lane; the groups of the list sit in the wave's LDS row, and
+// a position is a first occurrence when no earlier position holds its group (a uniform loop of
+// broadcast reads).  A ballot / mbcnt prefix per 64 positions compacts the first occurrences in
+// list order.
+__global__ __launch_bounds__(256) void k_collapse_walk(CollapseWalkArgs a) {
+    constexpr int QPW = 4, S = (int)kCollapseMaxFetch / 64;
+    __shared__ uint32_t s_grp[QPW][kCollapseMaxFetch];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t q = blockIdx.x * QPW + w;
+    if (q >= a.nq) return;
+    uint32_t* const grp = s_grp[w];
+    const uint32_t fk = a.fetch_k, k = a.k;
+    const uint32_t cnt = a.cand_cnt[q];
+    const uint32_t m = cnt < fk ? cnt : fk;
+    uint64_t gidx[S];
+    float dq[S];
+    uint32_t g[S];
+    bool valid[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const uint32_t pos = s * 64 + lane;
+        gidx[s] = pos < m ? a.cand_idx[(uint64_t)q * fk + pos] : ~0ull;
+        // (an id outside the shard is no candidate: no group is read through it)
+        valid[s] = pos < m && gidx[s] >= a.offset && gidx[s] - a.offset < a.n;
+        dq[s] = valid[s] ? a.cand_dist[(uint64_t)q * fk + pos] : INFINITY;
+        g[s] = valid[s] ? a.row_group[gidx[s] - a.offset] : ~0u;
+        grp[pos] = g[s];
+    }
+    wave_sync();
+    uint64_t* const oi = a.out_idx + (uint64_t)q * k;
+    float* const od = a.out_dist + (uint64_t)q * k;
+    uint32_t* const og = a.out_group ? a.out_group + (uint64_t)q * k : nullptr;
+    uint32_t found = 0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        if ((uint32_t)s * 64 >= m) break;  // (uniform)
+        const uint32_t pos = s * 64 + lane;
+        const uint32_t jend = m < (uint32_t)s * 64 + 64 ? m : (uint32_t)s * 64 + 64;
+        bool first = valid[s];
+        for (uint32_t j = 0; j < jend; ++j) first = first && !(j < pos && grp[j] == g[s]);
+        const uint64_t mk = __ballot(first);
+        const uint32_t slot =
+            found + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        if (first && slot < k) {
+            oi[slot] = gidx[s];
+            od[slot] = dq[s];
+            if (og) og[slot] = g[s];
+        }
+        found += (uint32_t)__popcll(mk);
+    }
+    if (found > k) found = k;
+    for (uint32_t i = found + lane; i < k; i += kWave) {
+        oi[i] = ~0ull;
+        od[i] = INFINITY;
+        if (og) og[i] = ~0u;
+    }
+    if (lane == 0) {
+        a.out_count[q] = found;
+        // (fewer than k groups in a full list: rows outside it may hold further groups)
+        if (found < k && cnt >= fk) a.fail[atomicAdd(a.fail_cnt, 1u)] = q;
+    }
+}
+
+// k_range_scan's tile loop (the same staging, seq_chunk and finish_distance) with a table entry
+// per (query slot, group) in the place of a radius: a row that is live and allowed lowers the entry
+// of its group to its key.  The plain read ahead of the atomic only skips atomics that could not
+// lower the entry (entries never rise).  Only the launch's first nqf queries count.
+template <int QF>
+__global__ __launch_bounds__(256, 2) void k_collapse_scan(CollapseScanArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    float* ldq = lds + 256 * 68;
+    const int t = threadIdx.x;
+    const float* __restrict__ rows = a.rows;
+    const uint32_t ld = a.ld, dim = a.dim;
+    const uint64_t n = a.n, n_tiles = (n + 255) / 256;
+    const uint32_t nch = ld / 64;
+
+    const float* qp[QF];
+    float mag_b[QF];
+    const uint32_t* aw[QF];  // the query's own mask, as 32-bit words (nullptr: every row allowed)
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        const uint32_t id = (uint32_t)a.qids[j];
+        qp[j] = a.qf32 + (uint64_t)id * ld;
+        mag_b[j] = a.nb[id];
+        const uint64_t mask = a.allow && a.query_mask ? a.query_mask[id] : 0u;
+        aw[j] = a.allow ? reinterpret_cast<const uint32_t*>(a.allow + mask * a.allow_words) : nullptr;
+    }
+    const uint32_t lrow0 = (uint32_t)t >> 4;
+    const uint32_t lcol = ((uint32_t)t & 15) * 4;
+    uint64_t tile = blockIdx.x;
+    uint32_t ch = 0;
+    f32x4_t pre[16];
+    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
+    auto issue = [&](uint64_t tl, uint32_t c) {
+        const float* base = rows + (tl * 256 + lrow0) * ld + c * 64 + lcol;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const f32x4_t*>(base + (uint64_t)i * 16 * ld);
+        if constexpr (QF > 1) {
+            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + c * 64);
+        }
+    };
+    if (tile < n_tiles) issue(tile, 0);
+    float acc[QF], mx[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+
+    while (tile < n_tiles) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
+        if constexpr (QF > 1) {
+            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
+        }
+        __syncthreads();
+        uint64_t ntile = tile;
+        uint32_t nch_ = ch + 1;
+        if (nch_ == nch) { nch_ = 0; ntile = tile + gridDim.x; }
+        if (ntile >= n_tiles) { ntile = tile; nch_ = ch; }
+        issue(ntile, nch_);
+
+        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+        const float* bq[QF];
+#pragma unroll
+        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
+        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
+
+        if (ch == nch - 1) {
+            const uint64_t row = tile * 256 + t;
+            const bool valid = row < n;
+            const float mag_a = valid ? a.na[row] : 0.0f;
+            const uint32_t dw = valid && a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[row >> 5] : 0u;
+            const bool live = valid && !((dw >> (row & 31)) & 1u);
+            const uint32_t grp = live ? a.row_group[row] : 0u;
+#pragma unroll
+            for (int j = 0; j < QF; ++j) {
+                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+                bool hit = live && (uint32_t)j < a.nqf;
+                if (hit && aw[j]) hit = (aw[j][row >> 5] >> (row & 31)) & 1u;
+                if (hit) {
+                    const uint64_t key = dist_key(d, (uint32_t)row);
+                    unsigned long long* const e =
+                        reinterpret_cast<unsigned long long*>(a.best + (uint64_t)j * a.n_groups + grp);
+                    if (key < *e) atomicMin(e, (unsigned long long)key);
+                }
+                acc[j] = -0.0f;
+                mx[j] = 0.0f;
+            }
+            ch = 0;
+            tile += gridDim.x;
+        } else {
+            ++ch;
+        }
+    }
+}
+
+// Workgroup (g, j): the k smallest keys of its slice of query slot j's table, a wave list per
+// quarter of the slice (table entries of groups without an allowed live row are kKeyNone: no key),
+// the four lists merged through LDS as k_merge_parts merges -- into partial list g of slot j.
+template <int E>
+__global__ __launch_bounds__(256) void k_collapse_select(const uint64_t* __restrict__ best, uint32_t n_groups,
+                                                         uint32_t qf, uint32_t k, uint64_t* __restrict__ part) {
+    __shared__ uint64_t lk[4][64 * E];
+    const uint32_t g = blockIdx.x, j = blockIdx.y;
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    const uint64_t* const row = best + (uint64_t)j * n_groups;
+    const uint64_t per = ((uint64_t)n_groups + gridDim.x - 1) / gridDim.x;
+    const uint64_t lo = g * per, hi = lo + per < n_groups ? lo + per : n_groups;
+    WaveTopK<E> L;
+    L.init();
+    uint64_t thr = kKeyNone;
+    for (uint64_t base = lo + 64u * w; base < hi; base += 4 * kWave) {
+        const uint64_t i = base + lane;
+        L.offer(i < hi ? row[i] : kKeyNone, (int)k, thr);
+    }
+    L.store(&lk[w][0], (int)k);
+    __syncthreads();
+    if (w == 0) {
+        WaveTopK<E> M;
+        M.init();
+        uint64_t mt = kKeyNone;
+        for (int src = 0; src < 4; ++src)
+            for (uint32_t b = 0; b < k; b += kWave) {
+                const uint32_t i = b + lane;
+                M.offer(i < k ? lk[src][i] : kKeyNone, (int)k, mt);
+            }
+        M.store(part + ((uint64_t)g * qf + j) * k, (int)k);
+    }
+}
+
+// One workgroup per scanned query, thread e its e-th key (k <= 256).
+__global__ __launch_bounds__(256) void k_collapse_finish(const uint64_t* __restrict__ keys,
+                                                         const int32_t* __restrict__ qids, uint32_t k,
+                                                         uint64_t offset, const uint32_t* __restrict__ row_group,
+                                                         uint64_t* __restrict__ out_idx, float* __restrict__ out_dist,
+                                                         uint32_t* __restrict__ out_group,
+                                                         uint32_t* __restrict__ out_count) {
+    __shared__ uint32_t s_c;
+    const uint32_t q = (uint32_t)qids[blockIdx.x], e = threadIdx.x;
+    if (e == 0) s_c = 0;
+    __syncthreads();
+    const uint64_t key = e < k ? keys[(uint64_t)q * k + e] : kKeyNone;
+    const bool has = key != kKeyNone;
+    const uint64_t mk = __ballot(has);
+    if (mk && lane_id() == 0) atomicAdd(&s_c, (uint32_t)__popcll(mk));
+    if (e < k) {
+        const uint64_t o = (uint64_t)q * k + e;
+        out_idx[o] = has ? offset + key_row(key) : ~0ull;
+        out_dist[o] = has ? key_dist(key) : INFINITY;
+        if (out_group) out_group[o] = has ? row_group[key_row(key)] : ~0u;
+    }
+    __syncthreads();
+    if (e == 0) out_count[q] = s_c;
+}
+
+// ------------------------------------------------------------------------------------
 // Launchers
 // ------------------------------------------------------------------------------------
 #ifdef BSR_RESCORE_STAMPS
@@ -2499,6 +2731,60 @@ hipError_t launch_mmr_select(const MmrArgs& a, hipStream_t s) {
         !(a.lambda >= 0.0f && a.lambda <= 1.0f))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mmr_select, dim3(a.nq), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- collapsed search ----------------------------------------------------------------------
+hipError_t launch_group_check(const uint32_t* row_group, uint64_t n, uint32_t n_groups, uint32_t* flag,
+                              hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_group_check, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, row_group, n, n_groups, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_collapse_walk(const CollapseWalkArgs& a, hipStream_t s) {
+    if (!a.nq || !a.k || a.k > a.fetch_k || a.fetch_k > kCollapseMaxFetch) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_collapse_walk, dim3((a.nq + 3) / 4), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_collapse_scan(const CollapseScanArgs& a, uint32_t grid, hipStream_t s) {
+    if (!a.nqf || a.nqf > kScanQF || !grid || !a.n_groups || a.ld == 0 || a.ld % 64 != 0) return hipErrorInvalidValue;
+    if (a.nqf <= 1) hipLaunchKernelGGL(k_collapse_scan<1>, dim3(grid), dim3(256), 0, s, a);
+    else if (a.nqf <= 2) hipLaunchKernelGGL(k_collapse_scan<2>, dim3(grid), dim3(256), 0, s, a);
+    else if (a.nqf <= 4) hipLaunchKernelGGL(k_collapse_scan<4>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_collapse_scan<8>, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// (a slice of at least 4096 table entries per workgroup, at most 256 partial lists per query)
+uint32_t collapse_select_grid(uint32_t n_groups) {
+    const uint32_t g = (n_groups + 4095) / 4096;
+    return g < 1 ? 1 : g > 256 ? 256 : g;
+}
+
+hipError_t launch_collapse_select(const uint64_t* best, uint32_t n_groups, uint32_t nqf, uint32_t k, uint32_t grid,
+                                  uint64_t* part, hipStream_t s) {
+    if (!nqf || nqf > kScanQF || !grid || !n_groups || !k || k > 256) return hipErrorInvalidValue;
+    const uint32_t qf = nqf <= 1 ? 1 : nqf <= 2 ? 2 : nqf <= 4 ? 4 : 8;  // (launch_merge_parts' width)
+    const dim3 g(grid, nqf);
+#define BSR_CSEL(E) hipLaunchKernelGGL(k_collapse_select<E>, g, dim3(256), 0, s, best, n_groups, qf, k, part)
+    switch ((k + 63) / 64) {
+        case 1: BSR_CSEL(1); break;
+        case 2: BSR_CSEL(2); break;
+        case 3: BSR_CSEL(3); break;
+        default: BSR_CSEL(4); break;
+    }
+#undef BSR_CSEL
+    return hipGetLastError();
+}
+
+hipError_t launch_collapse_finish(const uint64_t* keys, const int32_t* qids, uint32_t nqf, uint32_t k, uint64_t offset,
+                                  const uint32_t* row_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                  uint32_t* out_count, hipStream_t s) {
+    if (!nqf || !k || k > 256) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_collapse_finish, dim3(nqf), dim3(256), 0, s, keys, qids, k, offset, row_group, out_idx,
+                       out_dist, out_group, out_count);
     return hipGetLastError();
 }
 

@@ -609,6 +609,72 @@ struct MmrArgs {
 };
 hipError_t launch_mmr_select(const MmrArgs& a, hipStream_t s);
 
+// ---- collapsed search (bsr_local_top_k_collapsed; k_exact.hip) ------------------
+// The group check: *flag |= 1 when an entry of row_group[0 .. n) is >= n_groups (zero before the
+// launch; 4 n bytes read, no pass over the rows).
+hipError_t launch_group_check(const uint32_t* row_group, uint64_t n, uint32_t n_groups, uint32_t* flag,
+                              hipStream_t s);
+// The walk: one wave per query over its candidate list -- the first m = min(cand_cnt[q], fetch_k)
+// slots of row q of cand_idx / cand_dist [nq][fetch_k], in (distance asc, id asc) order as a search
+// leaves them; an id outside [offset, offset + n) is no candidate and nothing is read through it.
+// The first occurrence of every group, in list order, and the first k of those: row q of out_idx /
+// out_dist / out_group (nullable) [nq][k] holds (global id, distance, group), then (~0, +inf, ~0u);
+// out_count[q] = their number.  A query that found fewer than k groups in a full list (cand_cnt[q]
+// >= fetch_k) is appended to fail[] (any order), *fail_cnt (zero before the launch) counts them.
+// 1 <= k <= fetch_k <= kCollapseMaxFetch.
+constexpr uint32_t kCollapseMaxFetch = 256;
+struct CollapseWalkArgs {
+    const uint64_t* cand_idx;   // [nq][fetch_k]
+    const float* cand_dist;     // [nq][fetch_k]
+    const uint32_t* cand_cnt;   // [nq]
+    uint32_t nq, fetch_k, k;
+    uint64_t n, offset;         // rows of the shard; the global id of row 0
+    const uint32_t* row_group;  // [n], every entry < n_groups (launch_group_check)
+    uint64_t* out_idx;          // [nq][k]
+    float* out_dist;            // [nq][k]
+    uint32_t* out_group;        // [nq][k], nullable
+    uint32_t* out_count;        // [nq]
+    uint32_t* fail;             // [nq]
+    uint32_t* fail_cnt;         // one word
+};
+hipError_t launch_collapse_walk(const CollapseWalkArgs& a, hipStream_t s);
+// The group scan, launch_range_scan's tile loop: every valid row that is live (dead, nullable) and
+// allowed lowers best[j][row_group[row]] to dist_key(d, row) by an atomic min, j the query's slot
+// in the launch (best: u64 [template width][n_groups], all-ones before the launch).  The allow bit
+// of slot j's query id: word row / 64 of mask query_mask[id] (mask 0 without a query_mask) of allow
+// [n_masks][allow_words]; allow == nullptr allows every row.  qids: as RangeArgs has them.
+struct CollapseScanArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t n;
+    const float* na;            // row magnitudes
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const uint64_t* dead;       // the bitset of deleted rows (nullable)
+    const uint32_t* row_group;  // [n]
+    uint32_t n_groups;
+    const uint64_t* allow;      // [n_masks][allow_words] (nullable)
+    uint64_t allow_words;
+    const uint32_t* query_mask; // [nq] (nullable: mask 0)
+    const int32_t* qids;
+    uint32_t nqf;
+    uint64_t* best;             // [1, 2, 4 or 8][n_groups]
+};
+hipError_t launch_collapse_scan(const CollapseScanArgs& a, uint32_t grid, hipStream_t s);
+// The selection over the tables of a launch's nqf queries: workgroup (g, j) keeps the k smallest keys
+// of its slice of best[j][0 .. n_groups) and writes them as partial list g of query slot j in
+// launch_merge_parts' layout (part: grid * width * k keys, width = nqf rounded up to 1, 2, 4, 8).
+// grid: collapse_select_grid(n_groups).  k <= 256.
+uint32_t collapse_select_grid(uint32_t n_groups);
+hipError_t launch_collapse_select(const uint64_t* best, uint32_t n_groups, uint32_t nqf, uint32_t k, uint32_t grid,
+                                  uint64_t* part, hipStream_t s);
+// The finish: the merged keys [.][k] of the queries qids[0 .. nqf) (ascending, kKeyNone behind them)
+// into row qids[j] of the outputs as (offset + row, distance, row_group[row]), then (~0, +inf, ~0u);
+// out_count = the number of keys.  k <= 256.
+hipError_t launch_collapse_finish(const uint64_t* keys, const int32_t* qids, uint32_t nqf, uint32_t k, uint64_t offset,
+                                  const uint32_t* row_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                  uint32_t* out_count, hipStream_t s);
+
 uint32_t scan_grid_for(uint64_t n);
 
 }  // namespace bsr

@@ -123,6 +123,8 @@ typedef struct {
 #define BSR_PATH_RANGE      1024u /* bsr_local_range_search ran */
 #define BSR_PATH_RANGE_SCAN 2048u /* ... and a query of the batch was answered by the exact range scan */
 #define BSR_PATH_MMR        4096u /* bsr_local_top_k_mmr ran (with the bits of the candidate search) */
+#define BSR_PATH_COLLAPSE       8192u  /* bsr_local_top_k_collapsed ran (with the candidate search's bits) */
+#define BSR_PATH_COLLAPSE_SCAN 16384u  /* ... and a query of the batch was answered by the group scan */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -454,6 +456,64 @@ int bsr_local_top_k_mmr(bsr_index* ix, const float* queries, uint32_t n_queries,
                         const uint32_t* query_mask, uint32_t mode,
                         uint64_t* out_idx, float* out_dist, uint32_t* out_rank /* nullable */,
                         uint32_t* out_count);
+
+/* ---- Collapsed search: the exact top-k of distinct groups, the best row of each (field
+ * collapsing, DISTINCT ON).  The rows of a shard are often chunks of documents, and the exact top-k
+ * of a query several chunks of one document; this call returns the k best documents, each with its
+ * best chunk, exactly and in one call.
+ * row_group[i] < n_groups is the group of local row i.  It is passed per call, like an allow mask,
+ * and never stored on the index: load, append, delete, update and compact do not know it, and after
+ * a compaction the caller remaps it through out_old_ids.  row_group_len must equal the index's row
+ * count; row_group is host or device memory, detected per call (a host array is copied into a
+ * buffer the index keeps).
+ * For one query, over the rows that are live and allowed (masks exactly as bsr_local_top_k_mmr
+ * takes them):
+ *   1. the head of a group is its row that comes first in (reference distance asc, global index
+ *      asc) order;
+ *   2. the result is the heads of the k groups whose heads come first in that same order;
+ *   3. out_count[q] = min(k, distinct groups among the allowed live rows);
+ *   4. row q holds (global index, the reference's f32 distance bits, group id in out_group,
+ *      nullable) in (distance asc, index asc) order, then (~0, +inf, ~0u).
+ * row_group[i] = i with n_groups = n is bsr_local_top_k(k) bit for bit; all rows in one group
+ * gives the top-1; the result is the same for every legal fetch_k.
+ * fetch_k is the length of the exact candidate list (bsr_local_top_k / _masked / _masked_groups
+ * with k = fetch_k) the call walks first: a query whose list shows k groups, or holds every allowed
+ * live row, is answered from it.  Any other query takes an exact scan of the shard that keeps the
+ * best row of every group in a table of 8 * n_groups bytes, in rounds of up to 8 queries and of at
+ * most BSR_COLLAPSE_TABLE_BUDGET bytes of tables (read from the environment per call, 256 MB by
+ * default; at least one query a round).  The scan reads the whole shard even under a sparse mask:
+ * it is the fallback, so choose fetch_k to make it rare.  The tables are allocated at the first
+ * scan that needs them and kept; like the first update of its size, that allocation makes the plain
+ * search re-capture its graph once.
+ * 1 <= k <= fetch_k <= cfg.max_k; n_groups >= 1.  queries, row_group, the masks and the four
+ * outputs are, independently, host or device pointers.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; k = 0, k > fetch_k or fetch_k >
+ *      cfg.max_k; n_groups = 0; an inconsistent mask argument set (bsr_local_top_k_mmr's); an
+ *      unknown mode; with n_queries > 0 a null queries pointer or a null out_idx / out_dist /
+ *      out_count;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. BSR_E_INVALID: row_group_len != the index's rows, or a null row_group with rows;
+ *   4. n_queries = 0: BSR_OK;
+ *   5. BSR_E_INVALID, found on the device: a row_group entry >= n_groups;
+ *   6. everything else as the candidate search reports it: allow_words != ceil(n / 64), a
+ *      query_mask entry >= n_masks, BSR_E_NONFINITE for a non-finite query, BSR_E_DIM.
+ * An empty shard gives every count 0.
+ * bsr_search_stats: search_path carries the candidate search's bits plus BSR_PATH_COLLAPSE, and
+ * BSR_PATH_COLLAPSE_SCAN when a query of the batch took the group scan; the other fields are the
+ * candidate search's, and graph_replay is 1 wherever bsr_local_top_k(n_queries, fetch_k) would
+ * replay.
+ * Out of scope: more than one row per group ("at most m per document"); group ids stored on the
+ * index; a multi-rank collapsed search (each rank calls this with its own row_group; a merge that
+ * keeps one head per group is the caller's); a list-driven scan for sparse masks; group sizes or
+ * counts in the output. */
+int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_queries,
+                              uint32_t k, uint32_t fetch_k,
+                              const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                              const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                              const uint32_t* query_mask, uint32_t mode,
+                              uint64_t* out_idx, float* out_dist, uint32_t* out_group /* nullable */,
+                              uint32_t* out_count);
 
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]

@@ -1,0 +1,180 @@
+"""Kernel-level checks of the collapsed search: the ctypes loader of the test-only shim
+(tests/kcheck/kcheck_collapse.cpp -> lib/libbsr_kcheck_collapse.so) and the exact model of the
+contract of bsr_local_top_k_collapsed (include/bsr.h).
+
+The model needs no tolerance: from the full distance vector of a query over the stored rows (the
+reference's bits, oracle.np_cosine_distances) it drops the deleted and the disallowed rows, takes
+each group's minimum by (distance, index) and then the k smallest heads by the same order.
+
+tests/test_collapse_models.py pins the model with hand-worked cases (CPU);
+tests/test_gpu_kernels_collapse.py compares the kernels with it, tests/test_gpu_collapse.py whole
+calls."""
+import ctypes
+import os
+
+import numpy as np
+
+from kcheck_exact import IDX_NONE, POS_INF, _fill, _rc, _struct
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB_PATH = os.path.join(ROOT, "better-search-rag-rust_amd", "lib", "libbsr_kcheck_collapse.so")
+
+MAX_FETCH = 256  # kCollapseMaxFetch = BSR_MAX_K
+SCAN_QF = 8      # kScanQF
+GROUP_NONE = np.uint32(0xFFFFFFFF)
+KEY_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+# (the order of struct KcWalk / KcScan in kcheck_collapse.cpp)
+_WALK_SPEC = (
+    ("cand_idx", "buf"), ("cand_dist", "buf"), ("cand_cnt", "buf"), ("nq", "u32"), ("fetch_k", "u32"), ("k", "u32"),
+    ("n", "u64"), ("offset", "u64"), ("row_group", "buf"), ("out_idx", "buf"), ("out_dist", "buf"),
+    ("out_group", "buf"), ("out_count", "buf"), ("fail", "buf"), ("fail_cnt", "buf"))
+_SCAN_SPEC = (
+    ("rows", "buf"), ("ld", "u32"), ("dim", "u32"), ("n", "u64"), ("offset", "u64"), ("na", "buf"), ("qf32", "buf"),
+    ("nb", "buf"), ("dead", "buf"), ("row_group", "buf"), ("n_groups", "u32"), ("nqf", "u32"), ("allow", "buf"),
+    ("allow_words", "u64"), ("query_mask", "buf"), ("qids", "buf"), ("k", "u32"), ("grid", "u32"),
+    ("sel_grid", "u32"), ("pad_", "u32"), ("best", "buf"), ("part", "buf"), ("keys", "buf"), ("out_idx", "buf"),
+    ("out_dist", "buf"), ("out_group", "buf"), ("out_count", "buf"))
+_Walk, _Scan = _struct(_WALK_SPEC), _struct(_SCAN_SPEC)
+_lib = None
+
+
+def lib() -> ctypes.CDLL:
+    """libbsr_kcheck_collapse.so (raises if it has not been built).  Load it after the `gpu` fixture."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f"{LIB_PATH} not built (run __graft_entry__.build())")
+        _lib = ctypes.CDLL(LIB_PATH)
+        for f in ("kc_collapse_max_fetch", "kc_collapse_scan_qf", "kc_collapse_select_grid", "kc_collapse_scan_grid"):
+            getattr(_lib, f).restype = ctypes.c_uint32
+        _lib.kc_collapse_select_grid.argtypes = [ctypes.c_uint32]
+        _lib.kc_collapse_scan_grid.argtypes = [ctypes.c_uint64]
+        sizes = (ctypes.c_uint32 * 2)()
+        _lib.kc_collapse_sizes(sizes)
+        assert list(sizes) == [ctypes.sizeof(_Walk), ctypes.sizeof(_Scan)], "struct layouts differ from the shim's"
+        assert _lib.kc_collapse_max_fetch() == MAX_FETCH and _lib.kc_collapse_scan_qf() == SCAN_QF
+    return _lib
+
+
+def group_check(row_group, n, n_groups):
+    """launch_group_check over row_group[0 .. n): the flag word afterwards (0 before)."""
+    row_group = np.ascontiguousarray(row_group, np.uint32)
+    flag = np.zeros(1, np.uint32)
+    rc = lib().kc_collapse_check(ctypes.c_void_p(row_group.ctypes.data), ctypes.c_uint64(row_group.nbytes),
+                                 ctypes.c_uint64(n), ctypes.c_uint32(n_groups), ctypes.c_void_p(flag.ctypes.data))
+    assert _rc(rc) == 0
+    return int(flag[0])
+
+
+def walk(cand_idx, cand_dist, cand_cnt, k, n, offset, row_group, with_group=True):
+    """launch_collapse_walk over the lists cand_idx / cand_dist [nq][fetch_k], cand_cnt [nq]; the
+    outputs and the fail list start as a pattern, the fail count as 0.  Returns (rc, idx [nq][k],
+    dist, count, group or None, fail list [nq], fail count)."""
+    cand_idx = np.ascontiguousarray(cand_idx, np.uint64)
+    cand_dist = np.ascontiguousarray(cand_dist, np.float32)
+    cand_cnt = np.ascontiguousarray(cand_cnt, np.uint32)
+    row_group = np.ascontiguousarray(row_group, np.uint32)
+    nq, fetch_k = cand_idx.shape
+    assert cand_dist.shape == (nq, fetch_k) and cand_cnt.shape == (nq,) and row_group.shape == (n,)
+    idx = np.full((nq, max(k, 1)), 0x1234, np.uint64)
+    dist = np.full((nq, max(k, 1)), np.nan, np.float32)
+    grp = np.full((nq, max(k, 1)), 0x5A5A5A5A, np.uint32) if with_group else None
+    cnt = np.full(nq, 0x5A5A5A5A, np.uint32)
+    fail = np.full(nq, 0x5A5A5A5A, np.uint32)
+    fail_cnt = np.zeros(1, np.uint32)
+    s = _Walk()
+    keep = _fill(s, _WALK_SPEC, dict(cand_idx=cand_idx, cand_dist=cand_dist, cand_cnt=cand_cnt, nq=nq, fetch_k=fetch_k,
+                                     k=k, n=n, offset=offset, row_group=row_group, out_idx=idx, out_dist=dist,
+                                     out_group=grp, out_count=cnt, fail=fail, fail_cnt=fail_cnt))
+    rc = lib().kc_collapse_walk(ctypes.byref(s))
+    del keep
+    return _rc(rc), idx, dist, cnt, grp, fail, int(fail_cnt[0])
+
+
+def scan(rows, dim, n, offset, na, qf32, nb, row_group, n_groups, qids, nqf, k, dead=None, allow=None,
+         query_mask=None):
+    """One round of the group scan over the slab rows [n_pad][ld] for the launch's nqf queries (qids
+    padded to the template width): the tables, launch_collapse_scan, launch_collapse_select,
+    launch_merge_parts, launch_collapse_finish.  The outputs [nq_all][k] (nq_all = len(qf32)) are
+    indexed by query id and start as a pattern.  Returns (rc, idx, dist, count, group, best
+    [nqf][n_groups])."""
+    L = lib()
+    qids = np.ascontiguousarray(qids, np.int32)
+    row_group = np.ascontiguousarray(row_group, np.uint32)
+    assert rows.dtype == np.float32 and rows.flags.c_contiguous and rows.shape[0] >= n and row_group.shape == (n,)
+    nq_all = qf32.shape[0]
+    width = 1 if nqf <= 1 else 2 if nqf <= 2 else 4 if nqf <= 4 else 8
+    assert len(qids) >= width and qids.max() < nq_all
+    sel_grid = L.kc_collapse_select_grid(n_groups)
+    idx = np.full((nq_all, k), 0x1234, np.uint64)
+    dist = np.full((nq_all, k), np.nan, np.float32)
+    grp = np.full((nq_all, k), 0x5A5A5A5A, np.uint32)
+    cnt = np.full(nq_all, 0x5A5A5A5A, np.uint32)
+    best = np.full((nqf, n_groups), KEY_NONE, np.uint64)
+    part = np.full(sel_grid * width * k, 0x77, np.uint64)
+    keys = np.full((nq_all, k), 0x77, np.uint64)
+    words = 0
+    if allow is not None:
+        allow = np.ascontiguousarray(allow, np.uint64)
+        words = allow.shape[-1]
+    s = _Scan()
+    keep = _fill(s, _SCAN_SPEC, dict(
+        rows=rows, ld=rows.shape[1], dim=dim, n=n, offset=offset, na=np.ascontiguousarray(na, np.float32),
+        qf32=np.ascontiguousarray(qf32, np.float32), nb=np.ascontiguousarray(nb, np.float32), dead=dead,
+        row_group=row_group, n_groups=n_groups, nqf=nqf, allow=allow, allow_words=words,
+        query_mask=None if query_mask is None else np.ascontiguousarray(query_mask, np.uint32), qids=qids, k=k,
+        grid=L.kc_collapse_scan_grid(n), sel_grid=sel_grid, best=best, part=part, keys=keys, out_idx=idx,
+        out_dist=dist, out_group=grp, out_count=cnt))
+    rc = L.kc_collapse_scan(ctypes.byref(s))
+    del keep
+    return _rc(rc), idx, dist, cnt, grp, best
+
+
+# ----------------------------------------------------------------------------------------
+# The model
+# ----------------------------------------------------------------------------------------
+def collapse_model(dist, row_group, k, live=None, allowed=None, offset=0):
+    """The contract for one query: dist [n] the reference's distances of the stored rows, row_group
+    [n] their groups, live / allowed [n] bool (None: every row).  The head of a group is its row that
+    comes first in (distance asc, index asc) order among the live allowed rows; the result is the
+    heads of the k groups whose heads come first in that order.  Returns (idx [k] u64, dist [k] f32,
+    group [k] u32, count) with the (~0, +inf, ~0u) tail."""
+    dist = np.asarray(dist, np.float32)
+    row_group = np.asarray(row_group, np.int64)
+    n = len(dist)
+    assert row_group.shape == (n,)
+    ok = np.ones(n, bool)
+    if live is not None:
+        ok &= np.asarray(live, bool)
+    if allowed is not None:
+        ok &= np.asarray(allowed, bool)
+    rows = np.flatnonzero(ok)
+    order = rows[np.lexsort((rows, dist[rows]))]  # (distance asc, index asc)
+    heads, seen = [], set()
+    for r in order:
+        g = int(row_group[r])
+        if g not in seen:
+            seen.add(g)
+            heads.append(int(r))
+            if len(heads) == k:
+                break
+    idx = np.full(k, IDX_NONE, np.uint64)
+    od = np.full(k, POS_INF, np.float32)
+    og = np.full(k, GROUP_NONE, np.uint32)
+    c = len(heads)
+    h = np.asarray(heads, np.int64)
+    idx[:c] = (h + offset).astype(np.uint64)
+    od[:c] = dist[h]
+    og[:c] = row_group[h]
+    return idx, od, og, c
+
+
+def collapse_batch(dists, row_group, k, live=None, allowed=None, offset=0):
+    """collapse_model for every query: dists [nq][n]; allowed None, [n], or one array per query.
+    Returns (idx [nq][k], dist, count [nq], group)."""
+    nq = len(dists)
+    per_query = allowed is not None and (isinstance(allowed, list) or np.asarray(allowed).ndim == 2)
+    out = [collapse_model(dists[q], row_group, k, live, allowed[q] if per_query else allowed, offset) for q in range(nq)]
+    return (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]),
+            np.array([o[3] for o in out], np.uint32), np.stack([o[2] for o in out]))
