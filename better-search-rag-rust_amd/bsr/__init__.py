@@ -63,6 +63,9 @@ BSR_PATH_RANGE_SCAN = 2048  # ... and a query of the batch was answered by the e
 BSR_PATH_MMR = 4096         # bsr_local_top_k_mmr ran (with the bits of the candidate search)
 BSR_PATH_COLLAPSE = 8192        # bsr_local_top_k_collapsed ran (with the bits of the candidate search)
 BSR_PATH_COLLAPSE_SCAN = 16384  # ... and a query of the batch was answered by the group scan
+BSR_PATH_CAP = 32768            # bsr_local_top_k_capped ran (with the bits of the candidate search)
+BSR_PATH_CAP_SCAN = 65536       # ... and a query of the batch was answered by the capped group scan
+BSR_CAP_MAX_PER_GROUP = 16      # the largest per_group of a capped search (include/bsr.h)
 BSR_RANGE_MAX_RESULTS = 4096  # result slots per query of a range search (include/bsr.h)
 BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
 BSR_MASK_LIST = 1
@@ -153,7 +156,10 @@ def lib() -> ctypes.CDLL:
                                                _P, _P]),
         "bsr_local_top_k_collapsed": (ctypes.c_int, [_P, _P, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P, _P,
                                                      _P, _P]),
+        "bsr_local_top_k_capped": (ctypes.c_int, [_P, _P, u32, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P,
+                                                  _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
+        "bsr_global_top_k_capped": (ctypes.c_int, [_P, _P, _P, _P, u32, u32, u32, u32, u32, _P, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
         "bsr_comm_init": (ctypes.c_int, [_P, i32, i32, i32, ctypes.POINTER(_P)]),
         "bsr_comm_destroy": (None, [_P]),
@@ -176,7 +182,8 @@ def lib() -> ctypes.CDLL:
     # (absent in older builds used for A/B runs)
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
-                "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed"}
+                "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
+                "bsr_local_top_k_capped", "bsr_global_top_k_capped"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -711,6 +718,29 @@ class Index:
         count is min(k, distinct groups among the allowed live rows).  fetch_k (default min(max_k,
         max(4 k, 32))) is the candidate list walked first; the result does not depend on it.
         allow_mask / allow_ids, or allow_masks with query_mask, and mask_mode: as mmr_search's."""
+        return self._group_search(None, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids, allow_masks,
+                                  query_mask, mask_mode, return_groups)
+
+    def capped_search(self, queries, k: int, row_group, per_group: int, n_groups=None, fetch_k=None,
+                      allow_mask=None, allow_ids=None, allow_masks=None, query_mask=None, mask_mode="auto",
+                      return_groups: bool = False):
+        """The exact top-k with at most per_group rows of any one group (bsr_local_top_k_capped) ->
+        (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32[, group [Q,k] u32]).  Every argument but
+        per_group (1 .. BSR_CAP_MAX_PER_GROUP) is collapsed_search's.  Row q holds the first k rows
+        in (distance asc, index asc) order that have fewer than per_group rows of their group ahead
+        of them; count is min(k, sum over groups of min(per_group, allowed live rows)).
+        per_group = 1 is collapsed_search, per_group >= k is search(k).  fetch_k (default
+        min(max_k, max(4 k, 32))) is the candidate list walked first; the result does not depend on
+        it."""
+        per_group = int(per_group)
+        if per_group < 1 or per_group > BSR_CAP_MAX_PER_GROUP:
+            raise BsrError(-1, f"per_group={per_group} outside 1 <= per_group <= {BSR_CAP_MAX_PER_GROUP}")
+        return self._group_search(per_group, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids,
+                                  allow_masks, query_mask, mask_mode, return_groups)
+
+    def _group_search(self, per_group, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids, allow_masks,
+                      query_mask, mask_mode, return_groups):
+        """collapsed_search (per_group None) and capped_search on host arrays."""
         one = allow_mask is not None or allow_ids is not None
         if one and (allow_masks is not None or query_mask is not None):
             raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
@@ -742,9 +772,12 @@ class Index:
                 qm = self._query_mask_ids(query_mask, nq)
             # (an empty shard's masks have no words: a valid, non-null pointer all the same)
             wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
-        _check(lib().bsr_local_top_k_collapsed(self._h, _ptr(q), nq, k, fk, _ptr(rg), n_rg, ng, wp, nw, n_masks,
-                                               _ptr(qm), _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(og),
-                                               _ptr(oc)))
+        tail = (_ptr(rg), n_rg, ng, wp, nw, n_masks, _ptr(qm), _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(og),
+                _ptr(oc))
+        if per_group is None:
+            _check(lib().bsr_local_top_k_collapsed(self._h, _ptr(q), nq, k, fk, *tail))
+        else:
+            _check(lib().bsr_local_top_k_capped(self._h, _ptr(q), nq, k, fk, per_group, *tail))
         return (oi, od, oc, og) if return_groups else (oi, od, oc)
 
     @staticmethod
@@ -779,6 +812,24 @@ class Index:
         out_idx / out_dist / out_group (optional) [nq][k], out_count [nq].  allow_words: the packed
         allow masks, [G][ceil(n / 64)] uint64 with query_mask [nq] 32-bit mask ids, or
         [ceil(n / 64)] -- one mask, no query_mask."""
+        _check(lib().bsr_local_top_k_collapsed(self._h, _ptr(queries), nq, k, fetch_k,
+                                               *self._group_device_tail(row_group, n_groups, out_idx, out_dist,
+                                                                        out_count, out_group, allow_words, query_mask,
+                                                                        mask_mode)))
+
+    def capped_search_device(self, queries, nq: int, k: int, fetch_k: int, per_group: int, row_group, n_groups: int,
+                             out_idx, out_dist, out_count, out_group=None, allow_words=None, query_mask=None,
+                             mask_mode="auto"):
+        """Zero-copy variant of capped_search on caller buffers: collapsed_search_device's arguments
+        and shapes, with per_group behind fetch_k."""
+        _check(lib().bsr_local_top_k_capped(self._h, _ptr(queries), nq, k, fetch_k, int(per_group),
+                                            *self._group_device_tail(row_group, n_groups, out_idx, out_dist, out_count,
+                                                                     out_group, allow_words, query_mask, mask_mode)))
+
+    @staticmethod
+    def _group_device_tail(row_group, n_groups, out_idx, out_dist, out_count, out_group, allow_words, query_mask,
+                           mask_mode):
+        """The arguments from row_group on of bsr_local_top_k_collapsed / _capped, for caller buffers."""
         if allow_words is None:
             if query_mask is not None:
                 raise BsrError(-1, "a query_mask needs allow_words")
@@ -789,10 +840,8 @@ class Index:
                 raise BsrError(-1, "packed allow masks have shape [G][words] or [words]")
             wp, nw, n_masks = _ptr(allow_words), int(shape[-1]), int(shape[0]) if len(shape) == 2 else 1
         n_rg = int(row_group.numel()) if hasattr(row_group, "numel") else int(np.asarray(row_group).size)
-        _check(lib().bsr_local_top_k_collapsed(self._h, _ptr(queries), nq, k, fetch_k, _ptr(row_group) if n_rg else None,
-                                               n_rg, int(n_groups), wp, nw, n_masks, _ptr(query_mask),
-                                               _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_group),
-                                               _ptr(out_count)))
+        return (_ptr(row_group) if n_rg else None, n_rg, int(n_groups), wp, nw, n_masks, _ptr(query_mask),
+                _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_group), _ptr(out_count))
 
     def _allow_group_words(self, allow_masks):
         """(buffer, masks, words per mask) of a grouped search's allow masks: a bool array [G][n]
@@ -1047,6 +1096,28 @@ def merge_top_k_lists(idx, dist, count, top_k: int):
     _check(lib().bsr_global_top_k(_ptr(idx), _ptr(dist), _ptr(count), L, Q, k_in, top_k, _ptr(oi),
                                   _ptr(od), _ptr(oc)))
     return oi, od, oc
+
+
+def merge_top_k_lists_capped(idx, dist, group, count, top_k: int, per_group: int):
+    """bsr_global_top_k_capped: the merge of per-rank capped (or collapsed, per_group = 1) lists,
+    idx / dist / group [L,Q,k_in] (global group ids), count [L,Q], on the host -> (idx [Q,top_k],
+    dist, group, count [Q]): per query the first top_k rows in (distance asc, index asc) order,
+    deduplicated by index, with at most per_group rows of any one group."""
+    idx = np.ascontiguousarray(idx, np.uint64)
+    dist = np.ascontiguousarray(dist, np.float32)
+    group = np.ascontiguousarray(group, np.uint32)
+    count = np.ascontiguousarray(count, np.uint32)
+    L, Q, k_in = idx.shape
+    if dist.shape != idx.shape or group.shape != idx.shape or count.shape != (L, Q):
+        raise BsrError(-1, "idx, dist and group are [L,Q,k_in], count [L,Q]")
+    top_k = int(top_k)
+    oi = np.empty((Q, max(top_k, 0)), np.uint64)
+    od = np.empty((Q, max(top_k, 0)), np.float32)
+    og = np.empty((Q, max(top_k, 0)), np.uint32)
+    oc = np.empty(Q, np.uint32)
+    _check(lib().bsr_global_top_k_capped(_ptr(idx), _ptr(dist), _ptr(group), _ptr(count), L, Q, k_in, top_k,
+                                         int(per_group), _ptr(oi), _ptr(od), _ptr(og), _ptr(oc)))
+    return oi, od, og, oc
 
 
 def gather_top_k_results(world, rank: int, local_top_k: List[Tuple[int, float]]):

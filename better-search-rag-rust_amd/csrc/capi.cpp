@@ -52,6 +52,11 @@ int bsr_local_top_k_collapsed_impl(bsr_index* ix, const float* queries, uint32_t
                                    const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                                    const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
                                    uint32_t* out_group, uint32_t* out_count);
+int bsr_local_top_k_capped_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                uint32_t per_group, const uint32_t* row_group, uint64_t row_group_len,
+                                uint32_t n_groups, const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                uint32_t* out_group, uint32_t* out_count);
 int bsr_index_collect_profile_impl(bsr_index* ix);
 int bsr_copy_out_impl(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist,
                       uint32_t* out_count);
@@ -407,6 +412,16 @@ int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_qu
                                              out_group, out_count));
 }
 
+int bsr_local_top_k_capped(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint32_t fetch_k,
+                           uint32_t per_group, const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                           const uint64_t* allow, uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
+                           uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                           uint32_t* out_count) {
+    BSR_GUARD(bsr_local_top_k_capped_impl(ix, queries, n_queries, k, fetch_k, per_group, row_group, row_group_len,
+                                          n_groups, allow, allow_words, n_masks, query_mask, mode, out_idx, out_dist,
+                                          out_group, out_count));
+}
+
 // The device merge's limits (k_merge_lists: one wave per query, the concatenation in LDS).
 static bool device_merge_fits(uint32_t P, uint32_t k_in, uint32_t k) {
     return P <= 64 && (uint64_t)P * k_in <= kMergeMaxEntries && k <= 256;
@@ -450,6 +465,31 @@ int bsr_global_top_k(const uint64_t* idx, const float* dist, const uint32_t* cou
                      uint32_t n_queries, uint32_t k_in, uint32_t k, uint64_t* out_idx, float* out_dist,
                      uint32_t* out_count) {
     BSR_GUARD(global_top_k_impl(idx, dist, count, n_lists, n_queries, k_in, k, out_idx, out_dist, out_count));
+}
+
+static int global_top_k_capped_impl(const uint64_t* idx, const float* dist, const uint32_t* group,
+                                    const uint32_t* count, uint32_t n_lists, uint32_t n_queries, uint32_t k_in,
+                                    uint32_t k, uint32_t per_group, uint64_t* out_idx, float* out_dist,
+                                    uint32_t* out_group, uint32_t* out_count) {
+    if (!n_queries) return BSR_OK;
+    const bool entries = n_lists && k_in;
+    if (!count || !out_idx || !out_dist || !out_count || (entries && (!idx || !dist || !group)))
+        return set_error(BSR_E_INVALID, "null argument");
+    if (k == 0) return set_error(BSR_E_INVALID, "k must be >= 1");
+    if (per_group == 0) return set_error(BSR_E_INVALID, "per_group must be >= 1");
+    if (is_device_ptr(count) || is_device_ptr(out_idx) || is_device_ptr(out_dist) || is_device_ptr(out_count) ||
+        (out_group && is_device_ptr(out_group)) ||
+        (entries && (is_device_ptr(idx) || is_device_ptr(dist) || is_device_ptr(group))))
+        return set_error(BSR_E_INVALID, "the capped merge takes host arrays only (copy device lists to the host first)");
+    return merge_top_k_lists_capped(ListsView{idx, dist, count, n_lists, n_queries, k_in}, group, n_queries, k,
+                                    per_group, out_idx, out_dist, out_group, out_count);
+}
+
+int bsr_global_top_k_capped(const uint64_t* idx, const float* dist, const uint32_t* group, const uint32_t* count,
+                            uint32_t n_lists, uint32_t n_queries, uint32_t k_in, uint32_t k, uint32_t per_group,
+                            uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_count) {
+    BSR_GUARD(global_top_k_capped_impl(idx, dist, group, count, n_lists, n_queries, k_in, k, per_group, out_idx,
+                                       out_dist, out_group, out_count));
 }
 
 int bsr_comm_unique_id(uint8_t out_id[BSR_UNIQUE_ID_BYTES]) {

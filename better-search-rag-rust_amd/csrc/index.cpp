@@ -2553,20 +2553,47 @@ int bsr_local_top_k_mmr_impl(bsr_index* ix, const float* queries, uint32_t nq, u
 }
 
 // ---------------------------------------------------------------------------------------
-// Collapsed search (bsr_local_top_k_collapsed)
+// Collapsed search (bsr_local_top_k_collapsed) and capped search
+// (bsr_local_top_k_capped): one host sequence.  per_group = 0 is the collapsed search
+// with its own walk and scan kernels; per_group >= 1 the capped search, whose walk counts up to
+// m_eff = min(per_group, k) rows of a group and whose tables hold m_eff entries per (query, group).
 // ---------------------------------------------------------------------------------------
 int bsr_index::collapsed_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
                                        const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow,
                                        uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
                                        uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
                                        uint32_t* out_count) {
+    return group_search_device(queries, nq, k, fetch_k, 0, row_group, n_groups, allow, allow_words, n_masks,
+                               query_mask, mode, out_idx, out_dist, out_group, out_count);
+}
+
+int bsr_index::capped_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                    uint32_t per_group, const uint32_t* row_group, uint32_t n_groups,
+                                    const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                    const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                    uint32_t* out_group, uint32_t* out_count) {
+    return group_search_device(queries, nq, k, fetch_k, per_group, row_group, n_groups, allow, allow_words, n_masks,
+                               query_mask, mode, out_idx, out_dist, out_group, out_count);
+}
+
+static_assert(kCapMaxPerGroup == BSR_CAP_MAX_PER_GROUP, "the capped scan's limit is the ABI's");
+
+int bsr_index::group_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                   uint32_t per_group, const uint32_t* row_group, uint32_t n_groups,
+                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                   const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                   uint32_t* out_group, uint32_t* out_count) {
     bsr_index* ix = this;
+    const bool capped = per_group != 0;
+    // (table entries per (query, group); m_eff * n_groups fits 32 bits, the entry point checked it)
+    const uint32_t m_eff = capped ? std::min(per_group, k) : 1;
+    const uint32_t n_entries = m_eff * n_groups;
     BSR_HIP(hipSetDevice(device));
     // Every buffer of the stage but the scan's tables first: an allocation after the candidate
     // search would fall between the capture of its graph and the replay (the key carries the
     // allocation generation), as mmr_search_device has it.
     const size_t nk = (size_t)nq * k;
-    const uint32_t sel_grid = collapse_select_grid(n_groups);
+    const uint32_t sel_grid = collapse_select_grid(n_entries);
     BSR_TRY(col_flag.ensure(2 * sizeof(uint32_t)));
     BSR_TRY(col_fail.ensure((size_t)nq * sizeof(uint32_t)));
     BSR_TRY(col_qids.ensure((size_t)nq * kScanQF * sizeof(int32_t)));
@@ -2592,7 +2619,7 @@ int bsr_index::collapsed_search_device(const float* queries, uint32_t nq, uint32
     if (!allow) BSR_TRY(search_device(queries, nq, fetch_k));
     else if (n_masks == 1 && !query_mask) BSR_TRY(search_device_masked(queries, nq, fetch_k, allow, allow_words, mode));
     else BSR_TRY(search_device_masked_groups(queries, nq, fetch_k, allow, allow_words, n_masks, query_mask, mode));
-    stats.search_path |= BSR_PATH_COLLAPSE;
+    stats.search_path |= capped ? BSR_PATH_CAP : BSR_PATH_COLLAPSE;
     // The walk, straight into the caller's arrays when they are all on the device, else into the
     // index's own, copied out at the end.
     const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count) &&
@@ -2613,18 +2640,19 @@ int bsr_index::collapsed_search_device(const float* queries, uint32_t nq, uint32
     wa.out_count = out_dev ? out_count : col_cnt.as<uint32_t>();
     wa.fail = col_fail.as<uint32_t>();
     wa.fail_cnt = flag + 1;
-    BSR_HIP(launch_collapse_walk(wa, stream));
+    if (capped) BSR_HIP(launch_cap_walk(CapWalkArgs{wa, m_eff}, stream));
+    else BSR_HIP(launch_collapse_walk(wa, stream));
     uint32_t nfail = 0;
     BSR_HIP(hipMemcpyAsync(&nfail, flag + 1, sizeof nfail, hipMemcpyDeviceToHost, stream));
     BSR_HIP(hipStreamSynchronize(stream));
     if (nfail) {
-        // The queries whose full list held fewer than k groups: the group scan, in rounds of as many
-        // queries as the table budget holds.
-        stats.search_path |= BSR_PATH_COLLAPSE_SCAN;
+        // The queries whose full list held fewer than k groups (kept rows): the group scan, in rounds
+        // of as many queries as the table budget holds.
+        stats.search_path |= capped ? BSR_PATH_CAP_SCAN : BSR_PATH_COLLAPSE_SCAN;
         h_fail.resize(nfail);
         BSR_HIP(hipMemcpy(h_fail.data(), col_fail.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost));
         std::sort(h_fail.begin(), h_fail.end());
-        const uint64_t table = 8ull * n_groups;
+        const uint64_t table = 8ull * n_entries;
         const uint64_t budget = env_bytes("BSR_COLLAPSE_TABLE_BUDGET", 256ull << 20);
         const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({kScanQF, budget / table, nfail}));
         const uint32_t rounds = (nfail + per - 1) / per;
@@ -2663,8 +2691,9 @@ int bsr_index::collapsed_search_device(const float* queries, uint32_t nq, uint32
             sa.qids = qid;
             sa.nqf = nr;
             BSR_HIP(hipMemsetAsync(col_best.p, 0xff, (size_t)nr * table, stream));
-            BSR_HIP(launch_collapse_scan(sa, grid, stream));
-            BSR_HIP(launch_collapse_select(sa.best, n_groups, nr, k, sel_grid, part.as<uint64_t>(), stream));
+            if (capped) BSR_HIP(launch_cap_scan(CapScanArgs{sa, m_eff}, grid, stream));
+            else BSR_HIP(launch_collapse_scan(sa, grid, stream));
+            BSR_HIP(launch_collapse_select(sa.best, n_entries, nr, k, sel_grid, part.as<uint64_t>(), stream));
             BSR_HIP(launch_merge_parts(part.as<uint64_t>(), sel_grid, qid, nr, k, col_keys.as<uint64_t>(), stream));
             BSR_HIP(launch_collapse_finish(col_keys.as<uint64_t>(), qid, nr, k, global_offset, dgrp, wa.out_idx,
                                            wa.out_dist, wa.out_group, wa.out_count, stream));
@@ -2707,6 +2736,43 @@ int bsr_local_top_k_collapsed_impl(bsr_index* ix, const float* queries, uint32_t
     if (nq == 0) return BSR_OK;
     BSR_TRY(ix->collapsed_search_device(queries, nq, k, fetch_k, row_group, n_groups, allow, allow_words, n_masks,
                                         query_mask, mode, out_idx, out_dist, out_group, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+int bsr_local_top_k_capped_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                uint32_t per_group, const uint32_t* row_group, uint64_t row_group_len,
+                                uint32_t n_groups, const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                uint32_t* out_group, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > fetch_k || fetch_k > ix->cfg.max_k)
+        return set_error(BSR_E_INVALID, "k=%u, fetch_k=%u outside 1 <= k <= fetch_k <= max_k=%u", k, fetch_k,
+                         ix->cfg.max_k);
+    if (per_group == 0 || per_group > BSR_CAP_MAX_PER_GROUP)
+        return set_error(BSR_E_INVALID, "per_group=%u outside 1 <= per_group <= %u", per_group, BSR_CAP_MAX_PER_GROUP);
+    if (n_groups == 0) return set_error(BSR_E_INVALID, "n_groups = 0");
+    // (the tables' entries per query go through the selection's 32-bit length)
+    if ((uint64_t)std::min(per_group, k) * n_groups > 0xFFFFFFFFull)
+        return set_error(BSR_E_INVALID, "min(per_group, k) * n_groups = %u * %u exceeds 2^32 - 1", std::min(per_group, k),
+                         n_groups);
+    if (!allow && (n_masks != 0 || query_mask))
+        return set_error(BSR_E_INVALID, "n_masks = %u or a query_mask without allow masks", n_masks);
+    if (allow && n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 with allow masks");
+    if (allow && !query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (row_group_len != ix->n)
+        return set_error(BSR_E_INVALID, "row_group_len=%llu, the index holds %llu rows", (unsigned long long)row_group_len,
+                         (unsigned long long)ix->n);
+    if (ix->n && !row_group) return set_error(BSR_E_INVALID, "null row_group");
+    if (nq == 0) return BSR_OK;
+    BSR_TRY(ix->capped_search_device(queries, nq, k, fetch_k, per_group, row_group, n_groups, allow, allow_words,
+                                     n_masks, query_mask, mode, out_idx, out_dist, out_group, out_count));
     collect_profile(ix);
     return BSR_OK;
 }

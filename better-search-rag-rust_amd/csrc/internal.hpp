@@ -275,12 +275,23 @@ struct bsr_index {
                                 const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow,
                                 uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
                                 uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_count);
+    // Capped search (bsr_local_top_k_capped): the same sequence with the capped walk
+    // and scan, min(per_group, k) table entries per (query, group), and the same buffers -- the two
+    // are group_search_device (per_group = 0: the collapsed search).
+    int capped_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k, uint32_t per_group,
+                             const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow, uint64_t allow_words,
+                             uint32_t n_masks, const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx,
+                             float* out_dist, uint32_t* out_group, uint32_t* out_count);
+    int group_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k, uint32_t per_group,
+                            const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow, uint64_t allow_words,
+                            uint32_t n_masks, const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx,
+                            float* out_dist, uint32_t* out_group, uint32_t* out_count);
     bsr::DevBuf col_grp;    // u32 [n]: a host row_group's device copy
     bsr::DevBuf col_flag;   // u32 [2]: the group check's flag; the fail list's count
     bsr::DevBuf col_fail;   // u32 [nq]: the queries the walk could not certify
     bsr::DevBuf col_qids;   // i32 [rounds][kScanQF]: their ids by scan round, each round padded
     bsr::DevBuf col_keys;   // u64 [nq][k]: the merged keys of the scanned queries
-    bsr::DevBuf col_best;   // u64 [queries of a round][n_groups]: the scan's tables
+    bsr::DevBuf col_best;   // u64 [queries of a round][n_groups][entries per group]: the scan's tables
     bsr::DevBuf col_idx, col_dist, col_group, col_cnt;  // the result rows [nq][k], the counts [nq]
 
     // Parallel search with a global emission threshold (P > 1), in two halves

@@ -2378,6 +2378,189 @@ __global__ __launch_bounds__(256) void k_collapse_finish(const uint64_t* __restr
 }
 
 // ------------------------------------------------------------------------------------
+// Capped search (bsr_local_top_k_capped): the k nearest rows with at most m of any
+// one group.  The walk answers a query from its exact candidate list when the list proves the
+// answer; the others take the capped group scan -- the m smallest keys per (query, group) over
+// every row -- and the collapsed search's selection, merge and finish over the table read as
+// m * n_groups entries.
+// ------------------------------------------------------------------------------------
+// k_collapse_walk's shape (one wave per query, four per workgroup, no barrier; the same ownership of
+// positions, LDS row and compaction).  The list is a prefix of the (distance, id) order, so every
+// earlier row of a listed row's group is listed ahead of it: a position is kept when fewer than m
+// earlier positions hold its group (the uniform loop of broadcast reads counts them).
+__global__ __launch_bounds__(256) void k_cap_walk(CapWalkArgs c) {
+    constexpr int QPW = 4, S = (int)kCollapseMaxFetch / 64;
+    __shared__ uint32_t s_grp[QPW][kCollapseMaxFetch];
+    const CollapseWalkArgs& a = c.w;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t q = blockIdx.x * QPW + w;
+    if (q >= a.nq) return;
+    uint32_t* const grp = s_grp[w];
+    const uint32_t fk = a.fetch_k, k = a.k, cap = c.per_group;
+    const uint32_t cnt = a.cand_cnt[q];
+    const uint32_t m = cnt < fk ? cnt : fk;
+    uint64_t gidx[S];
+    float dq[S];
+    uint32_t g[S];
+    bool valid[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const uint32_t pos = s * 64 + lane;
+        gidx[s] = pos < m ? a.cand_idx[(uint64_t)q * fk + pos] : ~0ull;
+        // (an id outside the shard is no candidate: no group is read through it)
+        valid[s] = pos < m && gidx[s] >= a.offset && gidx[s] - a.offset < a.n;
+        dq[s] = valid[s] ? a.cand_dist[(uint64_t)q * fk + pos] : INFINITY;
+        g[s] = valid[s] ? a.row_group[gidx[s] - a.offset] : ~0u;
+        grp[pos] = g[s];
+    }
+    wave_sync();
+    uint64_t* const oi = a.out_idx + (uint64_t)q * k;
+    float* const od = a.out_dist + (uint64_t)q * k;
+    uint32_t* const og = a.out_group ? a.out_group + (uint64_t)q * k : nullptr;
+    uint32_t found = 0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        if ((uint32_t)s * 64 >= m) break;  // (uniform)
+        const uint32_t pos = s * 64 + lane;
+        const uint32_t jend = m < (uint32_t)s * 64 + 64 ? m : (uint32_t)s * 64 + 64;
+        uint32_t before = 0;
+        for (uint32_t j = 0; j < jend; ++j) before += (j < pos && grp[j] == g[s]) ? 1u : 0u;
+        const bool kept = valid[s] && before < cap;
+        const uint64_t mk = __ballot(kept);
+        const uint32_t slot =
+            found + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        if (kept && slot < k) {
+            oi[slot] = gidx[s];
+            od[slot] = dq[s];
+            if (og) og[slot] = g[s];
+        }
+        found += (uint32_t)__popcll(mk);
+    }
+    if (found > k) found = k;
+    for (uint32_t i = found + lane; i < k; i += kWave) {
+        oi[i] = ~0ull;
+        od[i] = INFINITY;
+        if (og) og[i] = ~0u;
+    }
+    if (lane == 0) {
+        a.out_count[q] = found;
+        // (fewer than k kept rows in a full list: rows outside it may be kept too)
+        if (found < k && cnt >= fk) a.fail[atomicAdd(a.fail_cnt, 1u)] = q;
+    }
+}
+
+// A key into the m entries of its (query slot, group): after every insert has ended the entries
+// hold the m smallest keys inserted, in no order, whatever the interleaving.  Each atomic min either
+// leaves the entry and carries v on, or puts v in and carries the old value on, so a key ends in an
+// entry or is carried off the end; a carried value passed an entry only while it was above it, and
+// entries only fall, so every dropped key is above every final entry.  The plain reads ahead only
+// skip a key that is below no entry (a stale read is not lower than the entry: it costs atomics,
+// never a key).
+__device__ __forceinline__ void cap_insert(unsigned long long* e, uint32_t m, uint64_t key) {
+    bool below = false;
+    for (uint32_t s = 0; s < m; ++s) below |= key < e[s];
+    if (!below) return;
+    unsigned long long v = key;
+    for (uint32_t s = 0; s < m; ++s) {
+        const unsigned long long old = atomicMin(&e[s], v);
+        if (old == kKeyNone) break;
+        v = old > v ? old : v;
+    }
+}
+
+// k_collapse_scan's tile loop and epilogue conditions (the same staging, seq_chunk and
+// finish_distance, the same tombstone word, mask bit and nqf) with m entries per (query slot, group)
+// in the place of one: best[(j * n_groups + grp) * m + s].
+template <int QF>
+__global__ __launch_bounds__(256, 2) void k_cap_scan(CapScanArgs c) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    float* ldq = lds + 256 * 68;
+    const CollapseScanArgs& a = c.s;
+    const int t = threadIdx.x;
+    const float* __restrict__ rows = a.rows;
+    const uint32_t ld = a.ld, dim = a.dim;
+    const uint64_t n = a.n, n_tiles = (n + 255) / 256;
+    const uint32_t nch = ld / 64;
+
+    const float* qp[QF];
+    float mag_b[QF];
+    const uint32_t* aw[QF];  // the query's own mask, as 32-bit words (nullptr: every row allowed)
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        const uint32_t id = (uint32_t)a.qids[j];
+        qp[j] = a.qf32 + (uint64_t)id * ld;
+        mag_b[j] = a.nb[id];
+        const uint64_t mask = a.allow && a.query_mask ? a.query_mask[id] : 0u;
+        aw[j] = a.allow ? reinterpret_cast<const uint32_t*>(a.allow + mask * a.allow_words) : nullptr;
+    }
+    const uint32_t lrow0 = (uint32_t)t >> 4;
+    const uint32_t lcol = ((uint32_t)t & 15) * 4;
+    uint64_t tile = blockIdx.x;
+    uint32_t ch = 0;
+    f32x4_t pre[16];
+    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
+    auto issue = [&](uint64_t tl, uint32_t cc) {
+        const float* base = rows + (tl * 256 + lrow0) * ld + cc * 64 + lcol;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const f32x4_t*>(base + (uint64_t)i * 16 * ld);
+        if constexpr (QF > 1) {
+            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + cc * 64);
+        }
+    };
+    if (tile < n_tiles) issue(tile, 0);
+    float acc[QF], mx[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+
+    while (tile < n_tiles) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
+        if constexpr (QF > 1) {
+            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
+        }
+        __syncthreads();
+        uint64_t ntile = tile;
+        uint32_t nch_ = ch + 1;
+        if (nch_ == nch) { nch_ = 0; ntile = tile + gridDim.x; }
+        if (ntile >= n_tiles) { ntile = tile; nch_ = ch; }
+        issue(ntile, nch_);
+
+        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+        const float* bq[QF];
+#pragma unroll
+        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
+        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
+
+        if (ch == nch - 1) {
+            const uint64_t row = tile * 256 + t;
+            const bool valid = row < n;
+            const float mag_a = valid ? a.na[row] : 0.0f;
+            const uint32_t dw = valid && a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[row >> 5] : 0u;
+            const bool live = valid && !((dw >> (row & 31)) & 1u);
+            const uint32_t grp = live ? a.row_group[row] : 0u;
+#pragma unroll
+            for (int j = 0; j < QF; ++j) {
+                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+                bool hit = live && (uint32_t)j < a.nqf;
+                if (hit && aw[j]) hit = (aw[j][row >> 5] >> (row & 31)) & 1u;
+                if (hit)
+                    cap_insert(reinterpret_cast<unsigned long long*>(a.best) + ((uint64_t)j * a.n_groups + grp) * c.m,
+                               c.m, dist_key(d, (uint32_t)row));
+                acc[j] = -0.0f;
+                mx[j] = 0.0f;
+            }
+            ch = 0;
+            tile += gridDim.x;
+        } else {
+            ++ch;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Launchers
 // ------------------------------------------------------------------------------------
 #ifdef BSR_RESCORE_STAMPS
@@ -2785,6 +2968,25 @@ hipError_t launch_collapse_finish(const uint64_t* keys, const int32_t* qids, uin
     if (!nqf || !k || k > 256) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_collapse_finish, dim3(nqf), dim3(256), 0, s, keys, qids, k, offset, row_group, out_idx,
                        out_dist, out_group, out_count);
+    return hipGetLastError();
+}
+
+// ---- capped search ---------------------------------------------------------------------------
+hipError_t launch_cap_walk(const CapWalkArgs& c, hipStream_t s) {
+    const CollapseWalkArgs& a = c.w;
+    if (!a.nq || !a.k || a.k > a.fetch_k || a.fetch_k > kCollapseMaxFetch || !c.per_group) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_cap_walk, dim3((a.nq + 3) / 4), dim3(256), 0, s, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_cap_scan(const CapScanArgs& c, uint32_t grid, hipStream_t s) {
+    const CollapseScanArgs& a = c.s;
+    if (!a.nqf || a.nqf > kScanQF || !grid || !a.n_groups || a.ld == 0 || a.ld % 64 != 0 || !c.m || c.m > kCapMaxPerGroup)
+        return hipErrorInvalidValue;
+    if (a.nqf <= 1) hipLaunchKernelGGL(k_cap_scan<1>, dim3(grid), dim3(256), 0, s, c);
+    else if (a.nqf <= 2) hipLaunchKernelGGL(k_cap_scan<2>, dim3(grid), dim3(256), 0, s, c);
+    else if (a.nqf <= 4) hipLaunchKernelGGL(k_cap_scan<4>, dim3(grid), dim3(256), 0, s, c);
+    else hipLaunchKernelGGL(k_cap_scan<8>, dim3(grid), dim3(256), 0, s, c);
     return hipGetLastError();
 }
 

@@ -675,6 +675,28 @@ hipError_t launch_collapse_finish(const uint64_t* keys, const int32_t* qids, uin
                                   const uint32_t* row_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
                                   uint32_t* out_count, hipStream_t s);
 
+// ---- capped search (bsr_local_top_k_capped; k_exact.hip) ------------------------
+// The walk, launch_collapse_walk's arguments and contract with "first occurrence of its group"
+// replaced by "fewer than per_group earlier list positions hold its group": the kept rows in list
+// order, the first k of them, the same tail and count.  A query that kept fewer than k rows in a
+// full list is appended to fail[].  per_group = 1 writes what launch_collapse_walk writes.
+constexpr uint32_t kCapMaxPerGroup = 16;  // BSR_CAP_MAX_PER_GROUP
+struct CapWalkArgs {
+    CollapseWalkArgs w;
+    uint32_t per_group;  // >= 1 (a value >= k caps nothing)
+};
+hipError_t launch_cap_walk(const CapWalkArgs& a, hipStream_t s);
+// The capped group scan, launch_collapse_scan's arguments and tile loop with m entries per (query
+// slot, group): s.best is u64 [template width][n_groups][m], all-ones before the launch, and ends
+// holding, for every (slot, group), the m smallest keys dist_key(d, row) of the group's live allowed
+// rows in no particular order (kKeyNone where the group has fewer).  1 <= m <= kCapMaxPerGroup.
+// Read as m * n_groups entries per slot the tables are launch_collapse_select's input.
+struct CapScanArgs {
+    CollapseScanArgs s;
+    uint32_t m;
+};
+hipError_t launch_cap_scan(const CapScanArgs& a, uint32_t grid, hipStream_t s);
+
 uint32_t scan_grid_for(uint64_t n);
 
 }  // namespace bsr

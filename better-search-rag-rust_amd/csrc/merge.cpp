@@ -176,4 +176,67 @@ int merge_top_k_lists(const ListsView& in, uint32_t n_queries, uint32_t k, uint6
     return BSR_OK;
 }
 
+int merge_top_k_lists_capped(const ListsView& in, const uint32_t* group, uint32_t n_queries, uint32_t k,
+                             uint32_t per_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                             uint32_t* out_count) {
+    if (!n_queries) return BSR_OK;
+    if (k == 0) return set_error(BSR_E_INVALID, "k must be >= 1");
+    if (per_group == 0) return set_error(BSR_E_INVALID, "per_group must be >= 1");
+    struct Row {
+        uint64_t idx;
+        float dist;
+        uint32_t group;
+    };
+    std::vector<Row> rows;
+    std::vector<uint32_t> kept_group(k);
+    // (a first pass over every distance, so that a NaN leaves the outputs untouched)
+    for (uint32_t q = 0; q < n_queries; ++q)
+        for (uint32_t l = 0; l < in.n_lists; ++l) {
+            const float* d = in.dist_of(l, q);
+            for (uint32_t i = 0, c = in.count_of(l, q); i < c; ++i)
+                if (d[i] != d[i])
+                    return set_error(BSR_E_NONFINITE, "NaN distance in query %u (the reference panics)", q);
+        }
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        rows.clear();
+        for (uint32_t l = 0; l < in.n_lists; ++l) {
+            const uint64_t* ix = in.idx_of(l, q);
+            const float* d = in.dist_of(l, q);
+            const uint32_t* g = group + ((uint64_t)l * n_queries + q) * in.k_in;
+            for (uint32_t i = 0, c = in.count_of(l, q); i < c; ++i) rows.push_back({ix[i], d[i], g[i]});
+        }
+        // (stable: of two entries with one index and one distance the earlier list's comes first)
+        std::stable_sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {
+            return a.dist < b.dist || (a.dist == b.dist && a.idx < b.idx);
+        });
+        uint64_t* oi = out_idx + (size_t)q * k;
+        float* od = out_dist + (size_t)q * k;
+        uint32_t* og = out_group ? out_group + (size_t)q * k : nullptr;
+        uint32_t out = 0;
+        for (const Row& r : rows) {
+            if (out >= k) break;
+            // (at most k rows are kept: linear scans of them, as merge_one has for short lists)
+            bool dup = false;
+            uint32_t same = 0;
+            for (uint32_t i = 0; i < out; ++i) {
+                dup |= oi[i] == r.idx;
+                same += kept_group[i] == r.group;
+            }
+            if (dup || same >= per_group) continue;
+            oi[out] = r.idx;
+            od[out] = r.dist;
+            kept_group[out] = r.group;
+            ++out;
+        }
+        out_count[q] = out;
+        if (og) memcpy(og, kept_group.data(), (size_t)out * sizeof(uint32_t));
+        for (uint32_t i = out; i < k; ++i) {
+            oi[i] = ~0ull;
+            od[i] = __builtin_inff();
+            if (og) og[i] = ~0u;
+        }
+    }
+    return BSR_OK;
+}
+
 }  // namespace bsr

@@ -26,4 +26,12 @@ struct ListsView {
 int merge_top_k_lists(const ListsView& in, uint32_t n_queries, uint32_t k, uint64_t* out_idx, float* out_dist,
                       uint32_t* out_count);
 
+// bsr_global_top_k_capped for every query: the lists (with group ids [list][query][k_in] beside idx
+// and dist) concatenated, sorted by (distance asc, index asc), deduplicated by index; a row is kept
+// while fewer than per_group kept rows hold its group; the first k kept.  out_group is nullable;
+// entries past out_count[q] are (~0, +inf, ~0u).  A NaN distance returns BSR_E_NONFINITE.
+int merge_top_k_lists_capped(const ListsView& in, const uint32_t* group, uint32_t n_queries, uint32_t k,
+                             uint32_t per_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                             uint32_t* out_count);
+
 }  // namespace bsr

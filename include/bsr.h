@@ -125,6 +125,8 @@ typedef struct {
 #define BSR_PATH_MMR        4096u /* bsr_local_top_k_mmr ran (with the bits of the candidate search) */
 #define BSR_PATH_COLLAPSE       8192u  /* bsr_local_top_k_collapsed ran (with the candidate search's bits) */
 #define BSR_PATH_COLLAPSE_SCAN 16384u  /* ... and a query of the batch was answered by the group scan */
+#define BSR_PATH_CAP       32768u  /* bsr_local_top_k_capped ran (with the candidate search's bits) */
+#define BSR_PATH_CAP_SCAN  65536u  /* ... and a query of the batch was answered by the capped group scan */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -503,10 +505,11 @@ int bsr_local_top_k_mmr(bsr_index* ix, const float* queries, uint32_t n_queries,
  * BSR_PATH_COLLAPSE_SCAN when a query of the batch took the group scan; the other fields are the
  * candidate search's, and graph_replay is 1 wherever bsr_local_top_k(n_queries, fetch_k) would
  * replay.
- * Out of scope: more than one row per group ("at most m per document"); group ids stored on the
- * index; a multi-rank collapsed search (each rank calls this with its own row_group; a merge that
- * keeps one head per group is the caller's); a list-driven scan for sparse masks; group sizes or
- * counts in the output. */
+ * More than one row per group ("at most m per document") is bsr_local_top_k_capped, below; a
+ * multi-rank collapsed search is this call on every rank with out_group, bsr_allgather_bytes and
+ * bsr_global_top_k_capped with per_group = 1.
+ * Out of scope: group ids stored on the index; a parallel entry point that runs those collectives
+ * itself; a list-driven scan for sparse masks; group sizes or counts in the output. */
 int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_queries,
                               uint32_t k, uint32_t fetch_k,
                               const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
@@ -514,6 +517,70 @@ int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_qu
                               const uint32_t* query_mask, uint32_t mode,
                               uint64_t* out_idx, float* out_dist, uint32_t* out_group /* nullable */,
                               uint32_t* out_count);
+
+/* ---- Capped search: the exact top-k with at most per_group rows of any one group ("the k nearest
+ * chunks, no more than m from one document"), between bsr_local_top_k (k rows, any groups) and
+ * bsr_local_top_k_collapsed (one row of each of k groups), exactly and in one call.
+ * row_group, row_group_len, n_groups, the masks, mode and fetch_k are taken exactly as
+ * bsr_local_top_k_collapsed takes them.  For one query, over the rows that are live and allowed,
+ * with m = per_group:
+ *   1. order the rows by (reference distance asc, global index asc);
+ *   2. a row is kept when fewer than m rows of its group come before it in that order;
+ *   3. the result is the first k kept rows, in that order;
+ *   4. out_count[q] = min(k, sum over the groups of min(m, the group's allowed live rows));
+ *   5. row q holds (global index, the reference's f32 distance bits, group id in out_group,
+ *      nullable), then (~0, +inf, ~0u).
+ * per_group = 1 is bsr_local_top_k_collapsed byte for byte; per_group >= k is bsr_local_top_k(k)
+ * bit for bit and never scans; all rows in one group gives the top-min(m, k); the result is the
+ * same for every legal fetch_k.
+ * The candidate list of length fetch_k is a prefix of the order, so every earlier row of a listed
+ * row's group is listed too, and counting groups along the list decides "kept" exactly.  A query
+ * whose list keeps k rows, or holds every allowed live row, is answered from it.  Any other query
+ * takes an exact scan of the shard that keeps the min(m, k) best rows of every group in a table of
+ * 8 * min(m, k) * n_groups bytes, in rounds of up to 8 queries and of at most
+ * BSR_COLLAPSE_TABLE_BUDGET bytes of tables (the collapsed search's variable, read per call; at
+ * least one query a round).  The tables are the collapsed search's buffer, allocated at the first
+ * scan that needs them and kept; that allocation makes the plain search re-capture its graph once.
+ * 1 <= k <= fetch_k <= cfg.max_k; 1 <= per_group <= BSR_CAP_MAX_PER_GROUP; n_groups >= 1.  queries,
+ * row_group, the masks and the four outputs are, independently, host or device pointers.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; k = 0, k > fetch_k or fetch_k >
+ *      cfg.max_k; per_group = 0 or above BSR_CAP_MAX_PER_GROUP; n_groups = 0; min(per_group, k) *
+ *      n_groups > 2^32 - 1 (a table's entries are counted in 32 bits); an inconsistent mask argument
+ *      set (bsr_local_top_k_mmr's); an unknown mode; with n_queries > 0 a null queries pointer or a
+ *      null out_idx / out_dist / out_count;
+ *   2. to 6.: bsr_local_top_k_collapsed's, word for word.
+ * bsr_search_stats: search_path carries the candidate search's bits plus BSR_PATH_CAP (never
+ * BSR_PATH_COLLAPSE), and BSR_PATH_CAP_SCAN when a query of the batch took the scan; the other
+ * fields are the candidate search's, and graph_replay is 1 wherever bsr_local_top_k(n_queries,
+ * fetch_k) would replay.
+ * A multi-rank capped search: this call on every rank with its own row_group (global group ids)
+ * and out_group, bsr_allgather_bytes of the four outputs, bsr_global_top_k_capped.
+ * Out of scope: "k groups with up to m rows each"; a per-query per_group; group ids stored on the
+ * index; a list-driven scan for sparse masks; counts per group in the output. */
+#define BSR_CAP_MAX_PER_GROUP 16u
+int bsr_local_top_k_capped(bsr_index* ix, const float* queries, uint32_t n_queries,
+                           uint32_t k, uint32_t fetch_k, uint32_t per_group,
+                           const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                           const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                           const uint32_t* query_mask, uint32_t mode,
+                           uint64_t* out_idx, float* out_dist, uint32_t* out_group /* nullable */,
+                           uint32_t* out_count);
+
+/* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists, on the host.  Layout and
+ * null rules are bsr_global_top_k's, with group[(l*n_queries+q)*k_in ..] the group ids beside idx
+ * and dist (global group ids: a group may span ranks) and out_group [n_queries][k] (nullable).
+ * Per query: the lists concatenated, ordered by (distance asc, index asc), deduplicated by index; a
+ * row is kept while fewer than per_group kept rows hold its group; the first k kept rows.  Entries
+ * past out_count[q] are (~0, +inf, ~0u).  Over per-rank results of bsr_local_top_k_capped(k,
+ * per_group) (k_in = k) this is the capped search over the whole store.
+ * BSR_E_INVALID: a null array (group included, when there are entries), k = 0, per_group = 0 (there
+ * is no upper cap here), any array in device memory (a device merge is out of scope).
+ * BSR_E_NONFINITE: a NaN distance. */
+int bsr_global_top_k_capped(const uint64_t* idx, const float* dist, const uint32_t* group, const uint32_t* count,
+                            uint32_t n_lists, uint32_t n_queries, uint32_t k_in, uint32_t k, uint32_t per_group,
+                            uint64_t* out_idx, float* out_dist, uint32_t* out_group /* nullable */,
+                            uint32_t* out_count);
 
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]

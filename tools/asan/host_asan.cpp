@@ -1,6 +1,6 @@
 // host_asan.cpp -- the library's host code under AddressSanitizer + UBSan (VERDICT r04
 // item 6).  No GPU: everything here is host-side -- the host merge (merge.cpp, behind
-// bsr_global_top_k), the exchange over a host transport (capi.cpp: bsr_gather_top_k,
+// bsr_global_top_k and bsr_global_top_k_capped), the exchange over a host transport (capi.cpp: bsr_gather_top_k,
 // bsr_gather_global_top_k, the parallel search's header + standard path with empty contributions,
 // bsr_allgather_bytes, bsr_broadcast), interval_by_rank and the parquet vector store
 // (vstore.cpp).  P ranks are P threads of this process; the host transport is a barrier-based
@@ -87,6 +87,57 @@ static void test_merge(std::mt19937_64& rng) {
     uint64_t oi[2];
     float od[2];
     EXPECT(bsr_global_top_k(i1, d1, &c1, 1, 1, 2, 2, oi, od, &oc) == BSR_E_NONFINITE, "NaN not reported");
+}
+
+// bsr_global_top_k_capped: (distance, index) order, dedupe by index, at most m kept rows a group
+static void test_merge_capped(std::mt19937_64& rng) {
+    for (int it = 0; it < 300; ++it) {
+        const uint32_t L = 1 + rng() % 9, Q = 1 + rng() % 7, kin = 1 + rng() % 20, k = 1 + rng() % 25, m = 1 + rng() % 4;
+        std::vector<uint64_t> idx((size_t)L * Q * kin);
+        std::vector<float> dist(idx.size());
+        std::vector<uint32_t> grp(idx.size()), cnt((size_t)L * Q);
+        for (auto& c : cnt) c = rng() % (kin + 3);  // (counts past k_in read k_in entries)
+        for (size_t i = 0; i < idx.size(); ++i) {
+            idx[i] = rng() % 40;                    // duplicates across lists on purpose
+            dist[i] = (float)(idx[i] * 7 % 16) / 8.0f;  // ties on purpose; a duplicate carries its distance
+            grp[i] = (uint32_t)(idx[i] % 5);
+        }
+        std::vector<uint64_t> oi((size_t)Q * k);
+        std::vector<float> od((size_t)Q * k);
+        std::vector<uint32_t> og((size_t)Q * k), oc(Q);
+        const int st = bsr_global_top_k_capped(idx.data(), dist.data(), grp.data(), cnt.data(), L, Q, kin, k, m,
+                                               oi.data(), od.data(), it % 2 ? og.data() : nullptr, oc.data());
+        EXPECT(st == BSR_OK, "capped merge status %d: %s", st, bsr_last_error());
+        for (uint32_t q = 0; q < Q; ++q) {
+            std::vector<std::pair<float, uint64_t>> cat;
+            for (uint32_t l = 0; l < L; ++l)
+                for (uint32_t j = 0; j < std::min(cnt[(size_t)l * Q + q], kin); ++j)
+                    cat.push_back({dist[((size_t)l * Q + q) * kin + j], idx[((size_t)l * Q + q) * kin + j]});
+            std::sort(cat.begin(), cat.end());
+            std::vector<uint64_t> wi;
+            uint32_t have[5] = {0, 0, 0, 0, 0};
+            for (auto& e : cat) {
+                if (wi.size() == k) break;
+                if (std::find(wi.begin(), wi.end(), e.second) != wi.end() || have[e.second % 5] >= m) continue;
+                ++have[e.second % 5];
+                wi.push_back(e.second);
+            }
+            EXPECT(oc[q] == wi.size(), "capped count q%u %u vs %zu", q, oc[q], wi.size());
+            for (uint32_t j = 0; j < oc[q] && j < wi.size(); ++j)
+                EXPECT(oi[(size_t)q * k + j] == wi[j] && (it % 2 == 0 || og[(size_t)q * k + j] == wi[j] % 5),
+                       "capped entry q%u j%u", q, j);
+            for (uint32_t j = oc[q]; j < k; ++j) EXPECT(oi[(size_t)q * k + j] == ~0ull, "capped tail q%u j%u", q, j);
+        }
+    }
+    uint64_t i1[2] = {1, 2};
+    float d1[2] = {0.5f, NAN};
+    uint32_t g1[2] = {0, 0}, c1 = 2, oc = 0;
+    uint64_t oi[2];
+    float od[2];
+    EXPECT(bsr_global_top_k_capped(i1, d1, g1, &c1, 1, 1, 2, 2, 1, oi, od, nullptr, &oc) == BSR_E_NONFINITE,
+           "NaN not reported");
+    EXPECT(bsr_global_top_k_capped(i1, d1, g1, &c1, 1, 1, 2, 2, 0, oi, od, nullptr, &oc) == BSR_E_INVALID,
+           "per_group = 0 accepted");
 }
 
 static void test_interval(std::mt19937_64& rng) {
@@ -285,6 +336,7 @@ static void test_vstore(std::mt19937_64& rng) {
 int main() {
     std::mt19937_64 rng(20251018);
     test_merge(rng);
+    test_merge_capped(rng);
     test_interval(rng);
     test_exchange(rng);
     test_vstore(rng);
