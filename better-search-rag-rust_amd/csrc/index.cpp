@@ -1224,6 +1224,18 @@ static int read_failed(bsr_index* ix, uint32_t nq, uint32_t nfail) {
     BSR_HIP(hipStreamSynchronize(ix->stream));
     return BSR_OK;
 }
+// The first n ids of h_fail as the exact scans take them: rounds of `per` <= kScanQF queries, every
+// round padded to kScanQF ids with its first id.
+static std::vector<int32_t> padded_scan_ids(const std::vector<uint32_t>& h_fail, uint32_t n, uint32_t per = kScanQF) {
+    const uint32_t rounds = (n + per - 1) / per;
+    std::vector<int32_t> padded((size_t)rounds * kScanQF);
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint32_t nr = std::min(per, n - r * per);
+        for (uint32_t i = 0; i < kScanQF; ++i)
+            padded[(size_t)r * kScanQF + i] = (int32_t)h_fail[(size_t)r * per + (i < nr ? i : 0)];
+    }
+    return padded;
+}
 // ... as the exact scans' input: their ids in ascending order, counted into stats (direct: the filter
 // cannot serve the query; fallback: it was left uncertified), in qids (device) in groups of kScanQF,
 // the last group padded with its first id.  rerun (optional): set, with nothing counted or
@@ -1240,9 +1252,7 @@ static int failed_queries(bsr_index* ix, uint32_t nq, uint32_t nfail, bool* reru
         if (ix->h_qflags[q] & kQueryNoApprox) ++ix->stats.n_exact_direct;
         else ++ix->stats.n_fallback;
     }
-    std::vector<int32_t> padded(round_up(nfail, kScanQF));
-    for (size_t i = 0; i < padded.size(); ++i)
-        padded[i] = (int32_t)(i < nfail ? h_fail[i] : h_fail[i / kScanQF * kScanQF]);
+    const std::vector<int32_t> padded = padded_scan_ids(h_fail, nfail);
     BSR_TRY(ix->qids.ensure(padded.size() * sizeof(int32_t)));
     BSR_HIP(hipMemcpyAsync(ix->qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                            ix->stream));
@@ -1617,7 +1627,63 @@ static uint64_t mask_list_budget_ids() {
     return std::max<uint64_t>(env_bytes("BSR_MASK_LIST_BUDGET", 256ull << 20) / sizeof(uint32_t), 1);
 }
 
-// The exact list scan of the queries with on_list[q] set, every one over the list of its own mask
+// What the two grouped list scans (top-k here, the range in §17) plan alike.
+// The queries `listed` (ascending ids) whose mask allows a row, by mask and ascending within a mask
+// (a counting sort): mask g's are order[start[g] .. start[g + 1]).
+struct QueriesByMask { std::vector<uint32_t> start, order; };
+static QueriesByMask queries_by_mask(const bsr_index* ix, uint32_t n_masks, const std::vector<uint32_t>& listed) {
+    const std::vector<uint32_t>& qmask = ix->h_grp_qmask;
+    const std::vector<uint32_t>& A = ix->h_grp_out;
+    QueriesByMask by{std::vector<uint32_t>(n_masks + 1, 0), {}};
+    for (uint32_t q : listed)
+        if (A[qmask[q]]) ++by.start[qmask[q] + 1];
+    for (uint32_t g = 0; g < n_masks; ++g) by.start[g + 1] += by.start[g];
+    by.order.resize(by.start[n_masks]);
+    std::vector<uint32_t> at(by.start.begin(), by.start.end() - 1);
+    for (uint32_t q : listed)
+        if (A[qmask[q]]) by.order[at[qmask[q]]++] = q;
+    return by;
+}
+
+// A chunk's query groups, one width qf in {8, 4, 2, 1} after the other, appended to h_grp_scan and
+// h_grp_ids: every list d[i] (.off, .n_list, .mask: a mask's row list or a segment of it) meets
+// every group of its mask's queries -- full groups of kScanQF and one narrower group of the rest in
+// the narrowest width that holds it (as launch_scan_list does), padded with the group's first id.
+// Returned: the launches, per width one for as many groups as max_groups and, with partial lists
+// of k keys (k = 0: none), kListPartBytes hold.
+struct GroupLaunch { uint32_t qf, groups, grid; size_t scan0, ids0; };
+template <class Desc>
+static std::vector<GroupLaunch> plan_query_groups(bsr_index* ix, const Desc* d, size_t n_d, const QueriesByMask& by,
+                                                  uint32_t max_groups, uint32_t k) {
+    std::vector<ScanGroupDesc>& scans = ix->h_grp_scan;
+    std::vector<int32_t>& ids = ix->h_grp_ids;
+    std::vector<GroupLaunch> launches;
+    for (uint32_t qf = kScanQF; qf >= 1; qf /= 2) {
+        const size_t scan0 = scans.size(), ids0 = ids.size();
+        uint32_t longest = 0;
+        for (size_t l = 0; l < n_d; ++l) {
+            const uint32_t q0 = by.start[d[l].mask], nqg = by.start[d[l].mask + 1] - q0, rest = nqg % kScanQF;
+            auto group = [&](uint32_t first, uint32_t cnt) {
+                scans.push_back(ScanGroupDesc{d[l].off, d[l].n_list, cnt});
+                for (uint32_t j = 0; j < qf; ++j) ids.push_back((int32_t)by.order[first + (j < cnt ? j : 0)]);
+                longest = std::max(longest, d[l].n_list);
+            };
+            if (qf == kScanQF)
+                for (uint32_t f = 0; f + kScanQF <= nqg; f += kScanQF) group(q0 + f, kScanQF);
+            if (rest && rest <= qf && rest > qf / 2) group(q0 + nqg - rest, rest);
+        }
+        const size_t n_groups = scans.size() - scan0;
+        if (!n_groups) continue;
+        const uint32_t grid = scan_grid_for(longest);
+        size_t per = max_groups;
+        if (k) per = std::min(std::max<size_t>(kListPartBytes / ((size_t)grid * qf * k * sizeof(uint64_t)), 1), per);
+        for (size_t g0 = 0; g0 < n_groups; g0 += per)
+            launches.push_back(GroupLaunch{qf, (uint32_t)std::min(per, n_groups - g0), grid, scan0 + g0, ids0 + g0 * qf});
+    }
+    return launches;
+}
+
+// The exact list scan of the queries `listed` (ascending ids), every one over the list of its own mask
 // (DESIGN.md §12).  The masks that have such a query (and a row) are taken in ascending order into
 // chunks whose lists fit the budget (a list longer than the budget is a chunk of its own); a
 // chunk is one scatter launch, and per width qf in {8, 4, 2, 1} one grouped scan and one merge
@@ -1625,25 +1691,14 @@ static uint64_t mask_list_budget_ids() {
 // full groups of kScanQF and one narrower group of the rest, padded with the group's first id;
 // no group holds queries of two masks.  The launch count depends on the chunks and the batch size,
 // not on n_masks.  keys of queries whose mask allows no row are left as they are (kKeyNone).
-static int run_list_scan_groups(bsr_index* ix, uint32_t nq, uint32_t k, const uint64_t* allow, uint64_t words,
-                                uint32_t n_masks, const std::vector<uint8_t>& on_list) {
-    const std::vector<uint32_t>& qmask = ix->h_grp_qmask;
+static int run_list_scan_groups(bsr_index* ix, uint32_t k, const uint64_t* allow, uint64_t words, uint32_t n_masks,
+                                const std::vector<uint32_t>& listed) {
     const std::vector<uint32_t>& A = ix->h_grp_out;
-    // the listed queries by mask, ascending within a mask (a counting sort)
-    std::vector<uint32_t> start(n_masks + 1, 0), order;
-    for (uint32_t q = 0; q < nq; ++q)
-        if (on_list[q] && A[qmask[q]]) ++start[qmask[q] + 1];
-    for (uint32_t g = 0; g < n_masks; ++g) start[g + 1] += start[g];
-    order.resize(start[n_masks]);
-    {
-        std::vector<uint32_t> at(start.begin(), start.end() - 1);
-        for (uint32_t q = 0; q < nq; ++q)
-            if (on_list[q] && A[qmask[q]]) order[at[qmask[q]]++] = q;
-    }
-    if (order.empty()) return BSR_OK;
+    const QueriesByMask by = queries_by_mask(ix, n_masks, listed);
+    const std::vector<uint32_t>& start = by.start;
+    if (by.order.empty()) return BSR_OK;
 
-    struct Launch { uint32_t qf, groups, grid; size_t scan0, ids0; };
-    struct Chunk { size_t list0; uint32_t n_lists; std::vector<Launch> launches; };
+    struct Chunk { size_t list0; uint32_t n_lists; std::vector<GroupLaunch> launches; };
     std::vector<Chunk> chunks;
     std::vector<MaskListDesc>& lists = ix->h_grp_lists;
     std::vector<ScanGroupDesc>& scans = ix->h_grp_scan;
@@ -1667,36 +1722,9 @@ static int run_list_scan_groups(bsr_index* ix, uint32_t nq, uint32_t k, const ui
             ++c.n_lists;
         }
         list_ids = std::max(list_ids, total);
-        // its query groups, one width after the other
-        for (uint32_t qf = kScanQF; qf >= 1; qf /= 2) {
-            std::vector<ScanGroupDesc> sg;
-            std::vector<int32_t> gid;
-            uint32_t longest = 0;
-            for (size_t l = c.list0; l < c.list0 + c.n_lists; ++l) {
-                const MaskListDesc& d = lists[l];
-                const uint32_t q0 = start[d.mask], nqg = start[d.mask + 1] - q0, rest = nqg % kScanQF;
-                auto group = [&](uint32_t first, uint32_t cnt) {
-                    sg.push_back(ScanGroupDesc{d.off, d.n_list, cnt});
-                    for (uint32_t j = 0; j < qf; ++j) gid.push_back((int32_t)order[first + (j < cnt ? j : 0)]);
-                    longest = std::max(longest, d.n_list);
-                };
-                if (qf == kScanQF)
-                    for (uint32_t f = 0; f + kScanQF <= nqg; f += kScanQF) group(q0 + f, kScanQF);
-                // (the rest takes the narrowest width that holds it, as launch_scan_list does)
-                if (rest && rest <= qf && rest > qf / 2) group(q0 + nqg - rest, rest);
-            }
-            if (sg.empty()) continue;
-            const uint32_t grid = scan_grid_for(longest);
-            const size_t group_bytes = (size_t)grid * qf * k * sizeof(uint64_t);
-            const uint32_t per = (uint32_t)std::min<size_t>(std::max<size_t>(kListPartBytes / group_bytes, 1), 65535);
-            for (size_t g0 = 0; g0 < sg.size(); g0 += per) {
-                const uint32_t n_g = (uint32_t)std::min<size_t>(per, sg.size() - g0);
-                c.launches.push_back(Launch{qf, n_g, grid, scans.size() + g0, ids.size() + g0 * qf});
-                part_bytes = std::max(part_bytes, group_bytes * n_g);
-            }
-            scans.insert(scans.end(), sg.begin(), sg.end());
-            ids.insert(ids.end(), gid.begin(), gid.end());
-        }
+        c.launches = plan_query_groups(ix, lists.data() + c.list0, c.n_lists, by, 65535, k);
+        for (const GroupLaunch& l : c.launches)
+            part_bytes = std::max(part_bytes, (size_t)l.grid * l.qf * k * sizeof(uint64_t) * l.groups);
         if (c.n_lists) chunks.push_back(std::move(c));
         g = g_end;
     }
@@ -1717,7 +1745,7 @@ static int run_list_scan_groups(bsr_index* ix, uint32_t nq, uint32_t k, const ui
         BSR_HIP(launch_mask_groups_scatter(allow, words, ix->n, ix->dead_bits(), ix->grp_blk.as<uint32_t>(),
                                            ix->grp_lists.as<MaskListDesc>() + c.list0, c.n_lists,
                                            ix->mask_list.as<uint32_t>(), ix->stream));
-        for (const Launch& l : c.launches) {
+        for (const GroupLaunch& l : c.launches) {
             const ScanGroupDesc* sg = ix->grp_scan.as<ScanGroupDesc>() + l.scan0;
             const int32_t* gid = ix->qids.as<int32_t>() + l.ids0;
             BSR_HIP(launch_scan_list_groups(ix->rows.as<float>(), ix->ld, ix->dim, ix->mask_list.as<uint32_t>(), sg,
@@ -1851,7 +1879,10 @@ int bsr_index::search_device_masked_groups(const float* queries, uint32_t nq, ui
             stats.search_path |= BSR_PATH_MASK_LIST;
         }
     }
-    BSR_TRY(run_list_scan_groups(ix, nq, k, dallow, allow_words, n_masks, on_list));
+    std::vector<uint32_t> listed;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (on_list[q]) listed.push_back(q);
+    BSR_TRY(run_list_scan_groups(ix, k, dallow, allow_words, n_masks, listed));
     BSR_TRY(finalize_and_read(ix, nq, k, 0, true, grp_aq.as<uint32_t>()));
     return check_queries(ix, nq);
 }
@@ -2099,9 +2130,7 @@ int bsr_index::range_search_device(const float* queries, uint32_t nq, const floa
             h_fail.resize(nscan);
             BSR_HIP(hipMemcpy(h_fail.data(), fail.p, (size_t)nscan * sizeof(uint32_t), hipMemcpyDeviceToHost));
             std::sort(h_fail.begin(), h_fail.end());
-            std::vector<int32_t> padded(round_up(nscan, kScanQF));
-            for (size_t i = 0; i < padded.size(); ++i)
-                padded[i] = (int32_t)(i < nscan ? h_fail[i] : h_fail[i / kScanQF * kScanQF]);
+            const std::vector<int32_t> padded = padded_scan_ids(h_fail, nscan);
             BSR_TRY(qids.ensure(padded.size() * sizeof(int32_t)));
             BSR_HIP(hipMemcpyAsync(qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                                    stream));
@@ -2168,23 +2197,12 @@ static bool range_auto_prefers_list(uint64_t n, uint64_t A, uint32_t nq, uint32_
 
 static int run_range_list_scan(bsr_index* ix, RangeListArgs la, const uint64_t* allow, uint64_t words,
                                uint32_t n_masks, const std::vector<uint32_t>& listed) {
-    const std::vector<uint32_t>& qmask = ix->h_grp_qmask;
     const std::vector<uint32_t>& A = ix->h_grp_out;
-    // the listed queries by mask, ascending within a mask (a counting sort)
-    std::vector<uint32_t> start(n_masks + 1, 0), order;
-    for (uint32_t q : listed)
-        if (A[qmask[q]]) ++start[qmask[q] + 1];
-    for (uint32_t g = 0; g < n_masks; ++g) start[g + 1] += start[g];
-    order.resize(start[n_masks]);
-    {
-        std::vector<uint32_t> at(start.begin(), start.end() - 1);
-        for (uint32_t q : listed)
-            if (A[qmask[q]]) order[at[qmask[q]]++] = q;
-    }
-    if (order.empty()) return BSR_OK;
+    const QueriesByMask by = queries_by_mask(ix, n_masks, listed);
+    const std::vector<uint32_t>& start = by.start;
+    if (by.order.empty()) return BSR_OK;
 
-    struct Launch { uint32_t qf, groups, grid; size_t scan0, ids0; };
-    struct Chunk { size_t seg0; uint32_t n_segs; std::vector<Launch> launches; };
+    struct Chunk { size_t seg0; uint32_t n_segs; std::vector<GroupLaunch> launches; };
     std::vector<Chunk> chunks;
     std::vector<MaskSegDesc>& segs = ix->h_rng_segs;
     std::vector<ScanGroupDesc>& scans = ix->h_grp_scan;
@@ -2197,32 +2215,8 @@ static int run_range_list_scan(bsr_index* ix, RangeListArgs la, const uint64_t* 
     Chunk cur{0, 0, {}};
     auto close = [&]() {
         if (!cur.n_segs) return;
-        // the chunk's query groups, one width after the other: every segment meets every group of its mask
-        for (uint32_t qf = kScanQF; qf >= 1; qf /= 2) {
-            std::vector<ScanGroupDesc> sg;
-            std::vector<int32_t> gid;
-            uint32_t longest = 0;
-            for (size_t l = cur.seg0; l < cur.seg0 + cur.n_segs; ++l) {
-                const MaskSegDesc& d = segs[l];
-                const uint32_t q0 = start[d.mask], nqg = start[d.mask + 1] - q0, rest = nqg % kScanQF;
-                auto group = [&](uint32_t first, uint32_t cnt) {
-                    sg.push_back(ScanGroupDesc{d.off, d.n_list, cnt});
-                    for (uint32_t j = 0; j < qf; ++j) gid.push_back((int32_t)order[first + (j < cnt ? j : 0)]);
-                    longest = std::max(longest, d.n_list);
-                };
-                if (qf == kScanQF)
-                    for (uint32_t f = 0; f + kScanQF <= nqg; f += kScanQF) group(q0 + f, kScanQF);
-                if (rest && rest <= qf && rest > qf / 2) group(q0 + nqg - rest, rest);
-            }
-            if (sg.empty()) continue;
-            const uint32_t grid = scan_grid_for(longest);
-            for (size_t g0 = 0; g0 < sg.size(); g0 += 65535) {
-                const uint32_t n_g = (uint32_t)std::min<size_t>(65535, sg.size() - g0);
-                cur.launches.push_back(Launch{qf, n_g, grid, scans.size() + g0, ids.size() + g0 * qf});
-            }
-            scans.insert(scans.end(), sg.begin(), sg.end());
-            ids.insert(ids.end(), gid.begin(), gid.end());
-        }
+        // (no partial lists: the counts accumulate on rcnt)
+        cur.launches = plan_query_groups(ix, segs.data() + cur.seg0, cur.n_segs, by, 65535, 0);
         list_ids = std::max(list_ids, used);
         chunks.push_back(std::move(cur));
         cur = Chunk{segs.size(), 0, {}};
@@ -2257,7 +2251,7 @@ static int run_range_list_scan(bsr_index* ix, RangeListArgs la, const uint64_t* 
         BSR_HIP(launch_mask_groups_scatter_seg(allow, words, ix->n, ix->dead_bits(), ix->grp_blk.as<uint32_t>(),
                                                ix->rng_segs.as<MaskSegDesc>() + c.seg0, c.n_segs,
                                                ix->mask_list.as<uint32_t>(), ix->stream));
-        for (const Launch& l : c.launches) {
+        for (const GroupLaunch& l : c.launches) {
             la.grp = ix->grp_scan.as<ScanGroupDesc>() + l.scan0;
             la.qids = ix->qids.as<int32_t>() + l.ids0;
             la.groups = l.groups;
@@ -2656,12 +2650,7 @@ int bsr_index::group_search_device(const float* queries, uint32_t nq, uint32_t k
         const uint64_t budget = env_bytes("BSR_COLLAPSE_TABLE_BUDGET", 256ull << 20);
         const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({kScanQF, budget / table, nfail}));
         const uint32_t rounds = (nfail + per - 1) / per;
-        std::vector<int32_t> padded((size_t)rounds * kScanQF);
-        for (uint32_t r = 0; r < rounds; ++r) {
-            const uint32_t nr = std::min(per, nfail - r * per);
-            for (uint32_t i = 0; i < kScanQF; ++i)
-                padded[(size_t)r * kScanQF + i] = (int32_t)h_fail[(size_t)r * per + (i < nr ? i : 0)];
-        }
+        const std::vector<int32_t> padded = padded_scan_ids(h_fail, nfail, per);
         // (the one allocation behind the candidate search: the plain search re-captures once)
         BSR_TRY(col_best.ensure((size_t)per * table));
         BSR_HIP(hipMemcpyAsync(col_qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,

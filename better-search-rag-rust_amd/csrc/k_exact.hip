@@ -967,50 +967,61 @@ __global__ __launch_bounds__(1024) void k_rescore_kp(RescoreArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
-// Exact full scan (src/mpi_helpers/metrics.rs:36-50 for up to QF queries at once): 256
-// rows per tile (lane = row), 64-element chunks of the row-major slab staged through LDS
-// (padded to 68 floats: conflict-free ds_read_b128), next chunk prefetched into registers.
-// Each lane walks its row in index order per query: sequential dot, max|a_i-b_i|.  Per
-// wave a sorted top-k per query; the 4 waves merge through LDS into one list per block.
+// The exact scans' tile loop (src/mpi_helpers/metrics.rs:36-50 for up to QF
+// queries at once): 256 rows per tile (lane = row), 64-element chunks of the rows staged through
+// LDS (padded to 68 floats: conflict-free ds_read_b128), next chunk prefetched into registers.
+// Each lane walks its row in index order per query: sequential dot, max|a_i-b_i|.  scan_tiles
+// walks 256 consecutive rows per tile; what happens to a finished row is the calling kernel's
+// `epilogue`.  (The two kernels over row lists keep their gather loops written out.)
+// lds: rows [256][68] + (QF > 1) query chunk [QF][64]; QF == 1 reads the query through the
+// scalar cache instead (64 SGPRs per chunk), QF > 1 would spill SGPRs.
 // ------------------------------------------------------------------------------------
-template <int QF, int E>
-__global__ __launch_bounds__(256, 2) void k_scan_exact(const float* __restrict__ rows, uint32_t ld,
-                                                       uint32_t dim, uint64_t n,
-                                                       const float* __restrict__ na,
-                                                       const float* __restrict__ qf32,
-                                                       const int32_t* __restrict__ qids,
-                                                       const float* __restrict__ nb, uint32_t k,
-                                                       uint64_t* __restrict__ part) {
-    // rows [256][68] + (QF > 1) query chunk [QF][64]; QF == 1 reads the query through the
-    // scalar cache instead (64 SGPRs per chunk), QF > 1 would spill SGPRs.
-    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
-    float* ldq = lds + 256 * 68;
-    const int t = threadIdx.x, w = t >> 6;
+// Thread t < QF*16 also stages float4 (t&15) of query t>>4's chunk: its source (else nullptr).
+template <int QF>
+__device__ __forceinline__ const float* scan_query_src(const float* const (&qp)[QF], int t) {
+    return (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + ((uint32_t)t & 15) * 4 : nullptr;
+}
+
+// The prefetched chunk into LDS: this lane's 16 float4 (row (i*256+t)>>4 of the tile, float4
+// t&15) and its float4 of the query chunk.
+template <int QF>
+__device__ __forceinline__ void scan_stage(float* lds, const f32x4_t (&pre)[16], f32x4_t qpre, bool has_q, int t) {
+    const uint32_t lrow0 = (uint32_t)t >> 4, lcol = ((uint32_t)t & 15) * 4;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
+    if constexpr (QF > 1) {
+        if (has_q) *reinterpret_cast<f32x4_t*>(lds + 256 * 68 + (t >> 4) * 64 + lcol) = qpre;
+    }
+}
+
+// Chunk ch of this lane's row against the QF queries.
+template <int QF>
+__device__ __forceinline__ void scan_walk(const float* lds, const float* const (&qp)[QF], uint32_t ch, uint32_t dim,
+                                          int t, float (&acc)[QF], float (&mx)[QF]) {
+    const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+    const float* bq[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? lds + 256 * 68 + j * 64 : qp[j] + ch * 64;
+    seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
+}
+
+// Tiles blockIdx.x, + gridDim.x, ... of the n rows.  epilogue(row, valid, mag_a, acc, mx) once
+// per finished tile: the lane's row, row < n, na[row] (0 for a row past n: na is not read there)
+// and the sums, which are reset behind it.
+template <int QF, class Epilogue>
+__device__ __forceinline__ void scan_tiles(float* lds, const float* rows, uint32_t ld, uint32_t dim, uint64_t n,
+                                           const float* na, const float* const (&qp)[QF], Epilogue&& epilogue) {
+    const int t = threadIdx.x;
     const uint64_t n_tiles = (n + 255) / 256;
     const uint32_t nch = ld / 64;
-
-    const float* qp[QF];
-    float mag_b[QF];
-#pragma unroll
-    for (int j = 0; j < QF; ++j) {
-        const int32_t id = qids[j];
-        qp[j] = qf32 + (uint64_t)id * ld;
-        mag_b[j] = nb[id];
-    }
-    WaveTopK<E> L[QF];
-    uint64_t thr[QF];
-#pragma unroll
-    for (int j = 0; j < QF; ++j) { L[j].init(); thr[j] = kKeyNone; }
-
-    // This lane's 16 load addresses within a tile chunk: row (i*256+t)>>4, float4 (t&15).
     const uint32_t lrow0 = (uint32_t)t >> 4;   // + 16*i
     const uint32_t lcol = ((uint32_t)t & 15) * 4;
     uint64_t tile = blockIdx.x;
     uint32_t ch = 0;
     f32x4_t pre[16];
     f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
-    // thread t < QF*16 also stages float4 (t&15) of query t>>4's chunk
-    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
+    const float* qsrc = scan_query_src<QF>(qp, t);
     auto issue = [&](uint64_t tl, uint32_t c) {
         const float* base = rows + (tl * 256 + lrow0) * ld + c * 64 + lcol;
 #pragma unroll
@@ -1026,12 +1037,7 @@ __global__ __launch_bounds__(256, 2) void k_scan_exact(const float* __restrict__
 
     while (tile < n_tiles) {
         __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
-        if constexpr (QF > 1) {
-            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
-        }
+        scan_stage<QF>(lds, pre, qpre, qsrc != nullptr, t);
         __syncthreads();
         // next (tile, chunk); past the end: reload the current chunk (branch-free prefetch)
         uint64_t ntile = tile;
@@ -1039,34 +1045,28 @@ __global__ __launch_bounds__(256, 2) void k_scan_exact(const float* __restrict__
         if (nch_ == nch) { nch_ = 0; ntile = tile + gridDim.x; }
         if (ntile >= n_tiles) { ntile = tile; nch_ = ch; }
         issue(ntile, nch_);
-
-        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
-        const float* bq[QF];
-#pragma unroll
-        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
-        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
+        scan_walk<QF>(lds, qp, ch, dim, t, acc, mx);
 
         if (ch == nch - 1) {
             const uint64_t row = tile * 256 + t;
             const bool valid = row < n;
-            const float mag_a = valid ? na[row] : 0.0f;
+            epilogue(row, valid, valid ? na[row] : 0.0f, acc, mx);
 #pragma unroll
-            for (int j = 0; j < QF; ++j) {
-                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
-                L[j].offer(valid ? dist_key(d, (uint32_t)row) : kKeyNone, (int)k, thr[j]);
-                acc[j] = -0.0f;
-                mx[j] = 0.0f;
-            }
+            for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
             ch = 0;
             tile += gridDim.x;
         } else {
             ++ch;
         }
     }
+}
 
-    // Block merge: 4 wave lists per query -> one list per query.
-    __syncthreads();
-    uint64_t* lk = reinterpret_cast<uint64_t*>(lds);  // [4][QF][64E] keys (<= 64 KiB)
+// Block merge: 4 wave lists per query -> one list per query, query j's at dst + j * k.  lk: LDS
+// for [4][QF][64E] keys (<= 64 KiB) that no thread still reads as anything else.
+template <int QF, int E>
+__device__ __forceinline__ void block_merge_lists(uint64_t* lk, const WaveTopK<E> (&L)[QF], uint32_t k,
+                                                  uint64_t* dst) {
+    const int t = threadIdx.x, w = t >> 6;
 #pragma unroll
     for (int j = 0; j < QF; ++j) L[j].store(lk + ((uint64_t)w * QF + j) * 64 * E, (int)k);
     __syncthreads();
@@ -1081,12 +1081,68 @@ __global__ __launch_bounds__(256, 2) void k_scan_exact(const float* __restrict__
                 M.offer(i < k ? src[i] : kKeyNone, (int)k, mt);
             }
         }
-        M.store(part + ((uint64_t)blockIdx.x * QF + j) * k, (int)k);
+        M.store(dst + (uint64_t)j * k, (int)k);
     }
 }
 
+// The lanes of a wave with `hit` claim consecutive slots behind *counter with one atomic add (by
+// the first of them): the lane's slot (0 for a wave without a hit).
+__device__ __forceinline__ uint32_t wave_claim(bool hit, uint32_t* counter, int lane) {
+    const uint64_t m = __ballot(hit);
+    if (!m) return 0u;
+    const int leader = __builtin_ctzll(m);
+    uint32_t b0 = 0;
+    if (lane == leader) b0 = atomicAdd(counter, (uint32_t)__popcll(m));
+    b0 = (uint32_t)__shfl((int)b0, leader, kWave);
+    return b0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// A valid row without a tombstone (dead: the bitset of deleted rows, nullable; read for valid rows).
+__device__ __forceinline__ bool row_live(const uint64_t* dead, uint64_t row, bool valid) {
+    const uint32_t dw = valid && dead ? reinterpret_cast<const uint32_t*>(dead)[row >> 5] : 0u;
+    return valid && !((dw >> (row & 31)) & 1u);
+}
+
 // ------------------------------------------------------------------------------------
-// Exact top-k over a row list (masked search): k_scan_exact's tile loop with the
+// Exact full scan: scan_tiles with a sorted top-k per wave and query; the 4 waves merge through
+// LDS into one list per block.
+// ------------------------------------------------------------------------------------
+template <int QF, int E>
+__global__ __launch_bounds__(256, 2) void k_scan_exact(const float* __restrict__ rows, uint32_t ld,
+                                                       uint32_t dim, uint64_t n,
+                                                       const float* __restrict__ na,
+                                                       const float* __restrict__ qf32,
+                                                       const int32_t* __restrict__ qids,
+                                                       const float* __restrict__ nb, uint32_t k,
+                                                       uint64_t* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    const float* qp[QF];
+    float mag_b[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        const int32_t id = qids[j];
+        qp[j] = qf32 + (uint64_t)id * ld;
+        mag_b[j] = nb[id];
+    }
+    WaveTopK<E> L[QF];
+    uint64_t thr[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) { L[j].init(); thr[j] = kKeyNone; }
+
+    scan_tiles<QF>(lds, rows, ld, dim, n, na, qp,
+                   [&](uint64_t row, bool valid, float mag_a, const float (&acc)[QF], const float (&mx)[QF]) {
+#pragma unroll
+        for (int j = 0; j < QF; ++j) {
+            const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+            L[j].offer(valid ? dist_key(d, (uint32_t)row) : kKeyNone, (int)k, thr[j]);
+        }
+    });
+    __syncthreads();
+    block_merge_lists<QF, E>(reinterpret_cast<uint64_t*>(lds), L, k, part + (uint64_t)blockIdx.x * QF * k);
+}
+
+// ------------------------------------------------------------------------------------
+// Exact top-k over a row list (masked search): scan_tiles' loop, written out, with the
 // tile's 256 rows taken from list[] (ascending local row ids) instead of 256 consecutive rows.
 // Every listed row is gathered whole, 64-element chunks through LDS, and walked by its lane in
 // index order with the same arithmetic.  Thread t fetches entry t of the next tile a tile ahead
@@ -1737,114 +1793,50 @@ __global__ __launch_bounds__(256) void k_range_rescore(RangeArgs a) {
         const uint32_t dw = a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[myrow >> 5] : 0u;
         const float d = finish_distance(acc[0], mx[0], mag_a, mag_b);
         const bool hit = valid && !((dw >> (myrow & 31)) & 1u) && d <= rad;
-        const uint64_t m = __ballot(hit);
-        if (m) {
-            const int leader = __builtin_ctzll(m);
-            uint32_t b0 = 0;
-            if (lane == leader) b0 = atomicAdd(&s_n, (uint32_t)__popcll(m));
-            b0 = (uint32_t)__shfl((int)b0, leader, kWave);
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            if (hit) dst[b0 + rank] = dist_key(d, myrow);  // (b0 + rank < c <= cap)
-        }
+        const uint32_t slot = wave_claim(hit, &s_n, lane);
+        if (hit) dst[slot] = dist_key(d, myrow);  // (slot < c <= cap)
     }
     __syncthreads();
     if (threadIdx.x == 0) a.rcnt[q] = s_n;
 }
 
-// k_scan_exact's tile loop (the same staging, seq_chunk and finish_distance) with a radius per
-// query instead of a top-k list: the in-range live rows of a wave claim slots of the query's list
-// with one atomic add on its count and store their keys below cap.  Only the launch's first nqf
-// queries count (the ids past them pad the template width).
+// The range scans' set-up: the launch's query ids with their rows, magnitudes and radii.
+template <int QF>
+__device__ __forceinline__ void range_queries(const int32_t* qids, const float* qf32, uint32_t ld, const float* nb,
+                                              const float* radius, uint32_t (&id)[QF], const float* (&qp)[QF],
+                                              float (&mag_b)[QF], float (&rad)[QF]) {
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        id[j] = (uint32_t)qids[j];
+        qp[j] = qf32 + (uint64_t)id[j] * ld;
+        mag_b[j] = nb[id[j]];
+        rad[j] = radius[id[j]];
+    }
+}
+
+// scan_tiles with a radius per query instead of a top-k list: the in-range live rows of a wave
+// claim slots of the query's list with one atomic add on its count and store their keys below cap.
+// Only the launch's first nqf queries count (the ids past them pad the template width).
 template <int QF>
 __global__ __launch_bounds__(256, 2) void k_range_scan(RangeArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
-    float* ldq = lds + 256 * 68;
-    const int t = threadIdx.x, lane = t & 63;
-    const float* __restrict__ rows = a.rows;
-    const uint32_t ld = a.ld, dim = a.dim;
-    const uint64_t n = a.n, n_tiles = (n + 255) / 256;
-    const uint32_t nch = ld / 64;
-
+    const int lane = threadIdx.x & 63;
     const float* qp[QF];
     float mag_b[QF], rad[QF];
     uint32_t id[QF];
-#pragma unroll
-    for (int j = 0; j < QF; ++j) {
-        id[j] = (uint32_t)a.qids[j];
-        qp[j] = a.qf32 + (uint64_t)id[j] * ld;
-        mag_b[j] = a.nb[id[j]];
-        rad[j] = a.radius[id[j]];
-    }
-    const uint32_t lrow0 = (uint32_t)t >> 4;
-    const uint32_t lcol = ((uint32_t)t & 15) * 4;
-    uint64_t tile = blockIdx.x;
-    uint32_t ch = 0;
-    f32x4_t pre[16];
-    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
-    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
-    auto issue = [&](uint64_t tl, uint32_t c) {
-        const float* base = rows + (tl * 256 + lrow0) * ld + c * 64 + lcol;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const f32x4_t*>(base + (uint64_t)i * 16 * ld);
-        if constexpr (QF > 1) {
-            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + c * 64);
-        }
-    };
-    if (tile < n_tiles) issue(tile, 0);
-    float acc[QF], mx[QF];
-#pragma unroll
-    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+    range_queries<QF>(a.qids, a.qf32, a.ld, a.nb, a.radius, id, qp, mag_b, rad);
 
-    while (tile < n_tiles) {
-        __syncthreads();
+    scan_tiles<QF>(lds, a.rows, a.ld, a.dim, a.n, a.na, qp,
+                   [&](uint64_t row, bool valid, float mag_a, const float (&acc)[QF], const float (&mx)[QF]) {
+        const bool live = row_live(a.dead, row, valid);
 #pragma unroll
-        for (int i = 0; i < 16; ++i)
-            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
-        if constexpr (QF > 1) {
-            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
+        for (int j = 0; j < QF; ++j) {
+            const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+            const bool hit = live && (uint32_t)j < a.nqf && d <= rad[j];
+            const uint32_t slot = wave_claim(hit, a.rcnt + id[j], lane);
+            if (hit && slot < a.cap) a.keys[(uint64_t)id[j] * a.cap + slot] = dist_key(d, (uint32_t)row);
         }
-        __syncthreads();
-        uint64_t ntile = tile;
-        uint32_t nch_ = ch + 1;
-        if (nch_ == nch) { nch_ = 0; ntile = tile + gridDim.x; }
-        if (ntile >= n_tiles) { ntile = tile; nch_ = ch; }
-        issue(ntile, nch_);
-
-        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
-        const float* bq[QF];
-#pragma unroll
-        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
-        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
-
-        if (ch == nch - 1) {
-            const uint64_t row = tile * 256 + t;
-            const bool valid = row < n;
-            const float mag_a = valid ? a.na[row] : 0.0f;
-            const uint32_t dw = valid && a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[row >> 5] : 0u;
-            const bool live = valid && !((dw >> (row & 31)) & 1u);
-#pragma unroll
-            for (int j = 0; j < QF; ++j) {
-                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
-                const bool hit = live && (uint32_t)j < a.nqf && d <= rad[j];
-                const uint64_t m = __ballot(hit);
-                if (m) {
-                    const int leader = __builtin_ctzll(m);
-                    uint32_t b0 = 0;
-                    if (lane == leader) b0 = atomicAdd(a.rcnt + id[j], (uint32_t)__popcll(m));
-                    b0 = (uint32_t)__shfl((int)b0, leader, kWave);
-                    const uint32_t slot = b0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (hit && slot < a.cap) a.keys[(uint64_t)id[j] * a.cap + slot] = dist_key(d, (uint32_t)row);
-                }
-                acc[j] = -0.0f;
-                mx[j] = 0.0f;
-            }
-            ch = 0;
-            tile += gridDim.x;
-        } else {
-            ++ch;
-        }
-    }
+    });
 }
 
 // The masked range search's routing, one workgroup behind k_range_tau: a query
@@ -1875,8 +1867,9 @@ __global__ __launch_bounds__(1024) void k_range_route(const uint32_t* __restrict
 }
 
 // The range over row lists (bsr_local_range_search_masked): k_scan_list<QF, ., GRP>'s
-// gather loop -- group blockIdx.y walks the grp[y].n_list ids at list + grp[y].off, 256 per tile,
-// entry t of the next tile fetched a tile ahead and handed to the loading threads through s_ids --
+// gather loop (written out in both: on a shared loop they measured slower) -- group
+// blockIdx.y walks the grp[y].n_list ids at list + grp[y].off, 256 per tile, entry t of the next
+// tile fetched a tile ahead and handed to the loading threads through s_ids --
 // with k_range_scan's epilogue: the in-range rows of a wave claim slots of their query's list with
 // one atomic add on its count and store their keys below cap.  Only the group's first grp[y].nq
 // queries count (the ids past them pad the template width).  No mask and no tombstone is read: the
@@ -2223,99 +2216,46 @@ __global__ __launch_bounds__(256) void k_collapse_walk(CollapseWalkArgs a) {
     }
 }
 
-// k_range_scan's tile loop (the same staging, seq_chunk and finish_distance) with a table entry
-// per (query slot, group) in the place of a radius: a row that is live and allowed lowers the entry
-// of its group to its key.  The plain read ahead of the atomic only skips atomics that could not
-// lower the entry (entries never rise).  Only the launch's first nqf queries count.
-template <int QF>
-__global__ __launch_bounds__(256, 2) void k_collapse_scan(CollapseScanArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
-    float* ldq = lds + 256 * 68;
-    const int t = threadIdx.x;
-    const float* __restrict__ rows = a.rows;
-    const uint32_t ld = a.ld, dim = a.dim;
-    const uint64_t n = a.n, n_tiles = (n + 255) / 256;
-    const uint32_t nch = ld / 64;
-
+// The group scans (collapsed and capped): scan_tiles, and sink(j, grp, key) for every row that is
+// live and allowed by the mask of query slot j -- its group and its key.  Only the launch's first
+// nqf queries count.
+template <int QF, class Sink>
+__device__ __forceinline__ void group_scan_tiles(float* lds, const CollapseScanArgs& a, Sink&& sink) {
     const float* qp[QF];
     float mag_b[QF];
     const uint32_t* aw[QF];  // the query's own mask, as 32-bit words (nullptr: every row allowed)
 #pragma unroll
     for (int j = 0; j < QF; ++j) {
         const uint32_t id = (uint32_t)a.qids[j];
-        qp[j] = a.qf32 + (uint64_t)id * ld;
+        qp[j] = a.qf32 + (uint64_t)id * a.ld;
         mag_b[j] = a.nb[id];
         const uint64_t mask = a.allow && a.query_mask ? a.query_mask[id] : 0u;
         aw[j] = a.allow ? reinterpret_cast<const uint32_t*>(a.allow + mask * a.allow_words) : nullptr;
     }
-    const uint32_t lrow0 = (uint32_t)t >> 4;
-    const uint32_t lcol = ((uint32_t)t & 15) * 4;
-    uint64_t tile = blockIdx.x;
-    uint32_t ch = 0;
-    f32x4_t pre[16];
-    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
-    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
-    auto issue = [&](uint64_t tl, uint32_t c) {
-        const float* base = rows + (tl * 256 + lrow0) * ld + c * 64 + lcol;
+    scan_tiles<QF>(lds, a.rows, a.ld, a.dim, a.n, a.na, qp,
+                   [&](uint64_t row, bool valid, float mag_a, const float (&acc)[QF], const float (&mx)[QF]) {
+        const bool live = row_live(a.dead, row, valid);
+        const uint32_t grp = live ? a.row_group[row] : 0u;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const f32x4_t*>(base + (uint64_t)i * 16 * ld);
-        if constexpr (QF > 1) {
-            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + c * 64);
+        for (int j = 0; j < QF; ++j) {
+            const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
+            bool hit = live && (uint32_t)j < a.nqf;
+            if (hit && aw[j]) hit = (aw[j][row >> 5] >> (row & 31)) & 1u;
+            if (hit) sink(j, grp, dist_key(d, (uint32_t)row));
         }
-    };
-    if (tile < n_tiles) issue(tile, 0);
-    float acc[QF], mx[QF];
-#pragma unroll
-    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+    });
+}
 
-    while (tile < n_tiles) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
-        if constexpr (QF > 1) {
-            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
-        }
-        __syncthreads();
-        uint64_t ntile = tile;
-        uint32_t nch_ = ch + 1;
-        if (nch_ == nch) { nch_ = 0; ntile = tile + gridDim.x; }
-        if (ntile >= n_tiles) { ntile = tile; nch_ = ch; }
-        issue(ntile, nch_);
-
-        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
-        const float* bq[QF];
-#pragma unroll
-        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
-        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
-
-        if (ch == nch - 1) {
-            const uint64_t row = tile * 256 + t;
-            const bool valid = row < n;
-            const float mag_a = valid ? a.na[row] : 0.0f;
-            const uint32_t dw = valid && a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[row >> 5] : 0u;
-            const bool live = valid && !((dw >> (row & 31)) & 1u);
-            const uint32_t grp = live ? a.row_group[row] : 0u;
-#pragma unroll
-            for (int j = 0; j < QF; ++j) {
-                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
-                bool hit = live && (uint32_t)j < a.nqf;
-                if (hit && aw[j]) hit = (aw[j][row >> 5] >> (row & 31)) & 1u;
-                if (hit) {
-                    const uint64_t key = dist_key(d, (uint32_t)row);
-                    unsigned long long* const e =
-                        reinterpret_cast<unsigned long long*>(a.best + (uint64_t)j * a.n_groups + grp);
-                    if (key < *e) atomicMin(e, (unsigned long long)key);
-                }
-                acc[j] = -0.0f;
-                mx[j] = 0.0f;
-            }
-            ch = 0;
-            tile += gridDim.x;
-        } else {
-            ++ch;
-        }
-    }
+// A table entry per (query slot, group): a live allowed row lowers the entry of its group to its
+// key.  The plain read ahead of the atomic only skips atomics that could not lower the entry
+// (entries never rise).
+template <int QF>
+__global__ __launch_bounds__(256, 2) void k_collapse_scan(CollapseScanArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    group_scan_tiles<QF>(lds, a, [&](int j, uint32_t grp, uint64_t key) {
+        unsigned long long* const e = reinterpret_cast<unsigned long long*>(a.best + (uint64_t)j * a.n_groups + grp);
+        if (key < *e) atomicMin(e, (unsigned long long)key);
+    });
 }
 
 // Workgroup (g, j): the k smallest keys of its slice of query slot j's table, a wave list per
@@ -2330,26 +2270,14 @@ __global__ __launch_bounds__(256) void k_collapse_select(const uint64_t* __restr
     const uint64_t* const row = best + (uint64_t)j * n_groups;
     const uint64_t per = ((uint64_t)n_groups + gridDim.x - 1) / gridDim.x;
     const uint64_t lo = g * per, hi = lo + per < n_groups ? lo + per : n_groups;
-    WaveTopK<E> L;
-    L.init();
+    WaveTopK<E> L[1];
+    L[0].init();
     uint64_t thr = kKeyNone;
     for (uint64_t base = lo + 64u * w; base < hi; base += 4 * kWave) {
         const uint64_t i = base + lane;
-        L.offer(i < hi ? row[i] : kKeyNone, (int)k, thr);
+        L[0].offer(i < hi ? row[i] : kKeyNone, (int)k, thr);
     }
-    L.store(&lk[w][0], (int)k);
-    __syncthreads();
-    if (w == 0) {
-        WaveTopK<E> M;
-        M.init();
-        uint64_t mt = kKeyNone;
-        for (int src = 0; src < 4; ++src)
-            for (uint32_t b = 0; b < k; b += kWave) {
-                const uint32_t i = b + lane;
-                M.offer(i < k ? lk[src][i] : kKeyNone, (int)k, mt);
-            }
-        M.store(part + ((uint64_t)g * qf + j) * k, (int)k);
-    }
+    block_merge_lists<1, E>(&lk[0][0], L, k, part + ((uint64_t)g * qf + j) * k);
 }
 
 // One workgroup per scanned query, thread e its e-th key (k <= 256).
@@ -2468,96 +2396,15 @@ __device__ __forceinline__ void cap_insert(unsigned long long* e, uint32_t m, ui
     }
 }
 
-// k_collapse_scan's tile loop and epilogue conditions (the same staging, seq_chunk and
-// finish_distance, the same tombstone word, mask bit and nqf) with m entries per (query slot, group)
-// in the place of one: best[(j * n_groups + grp) * m + s].
+// k_collapse_scan with m entries per (query slot, group) in the place of one:
+// best[(j * n_groups + grp) * m + s].
 template <int QF>
 __global__ __launch_bounds__(256, 2) void k_cap_scan(CapScanArgs c) {
     __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
-    float* ldq = lds + 256 * 68;
     const CollapseScanArgs& a = c.s;
-    const int t = threadIdx.x;
-    const float* __restrict__ rows = a.rows;
-    const uint32_t ld = a.ld, dim = a.dim;
-    const uint64_t n = a.n, n_tiles = (n + 255) / 256;
-    const uint32_t nch = ld / 64;
-
-    const float* qp[QF];
-    float mag_b[QF];
-    const uint32_t* aw[QF];  // the query's own mask, as 32-bit words (nullptr: every row allowed)
-#pragma unroll
-    for (int j = 0; j < QF; ++j) {
-        const uint32_t id = (uint32_t)a.qids[j];
-        qp[j] = a.qf32 + (uint64_t)id * ld;
-        mag_b[j] = a.nb[id];
-        const uint64_t mask = a.allow && a.query_mask ? a.query_mask[id] : 0u;
-        aw[j] = a.allow ? reinterpret_cast<const uint32_t*>(a.allow + mask * a.allow_words) : nullptr;
-    }
-    const uint32_t lrow0 = (uint32_t)t >> 4;
-    const uint32_t lcol = ((uint32_t)t & 15) * 4;
-    uint64_t tile = blockIdx.x;
-    uint32_t ch = 0;
-    f32x4_t pre[16];
-    f32x4_t qpre = {0.0f, 0.0f, 0.0f, 0.0f};
-    const float* qsrc = (QF > 1 && t < QF * 16) ? qp[QF > 1 ? (t >> 4) % QF : 0] + lcol : nullptr;
-    auto issue = [&](uint64_t tl, uint32_t cc) {
-        const float* base = rows + (tl * 256 + lrow0) * ld + cc * 64 + lcol;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const f32x4_t*>(base + (uint64_t)i * 16 * ld);
-        if constexpr (QF > 1) {
-            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + cc * 64);
-        }
-    };
-    if (tile < n_tiles) issue(tile, 0);
-    float acc[QF], mx[QF];
-#pragma unroll
-    for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
-
-    while (tile < n_tiles) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            *reinterpret_cast<f32x4_t*>(lds + (lrow0 + 16 * i) * 68 + lcol) = pre[i];
-        if constexpr (QF > 1) {
-            if (qsrc) *reinterpret_cast<f32x4_t*>(ldq + (t >> 4) * 64 + lcol) = qpre;
-        }
-        __syncthreads();
-        uint64_t ntile = tile;
-        uint32_t nch_ = ch + 1;
-        if (nch_ == nch) { nch_ = 0; ntile = tile + gridDim.x; }
-        if (ntile >= n_tiles) { ntile = tile; nch_ = ch; }
-        issue(ntile, nch_);
-
-        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
-        const float* bq[QF];
-#pragma unroll
-        for (int j = 0; j < QF; ++j) bq[j] = (QF > 1) ? ldq + j * 64 : qp[j] + ch * 64;
-        seq_chunk<QF>(lds + t * 68, bq, nvalid, acc, mx);
-
-        if (ch == nch - 1) {
-            const uint64_t row = tile * 256 + t;
-            const bool valid = row < n;
-            const float mag_a = valid ? a.na[row] : 0.0f;
-            const uint32_t dw = valid && a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[row >> 5] : 0u;
-            const bool live = valid && !((dw >> (row & 31)) & 1u);
-            const uint32_t grp = live ? a.row_group[row] : 0u;
-#pragma unroll
-            for (int j = 0; j < QF; ++j) {
-                const float d = finish_distance(acc[j], mx[j], mag_a, mag_b[j]);
-                bool hit = live && (uint32_t)j < a.nqf;
-                if (hit && aw[j]) hit = (aw[j][row >> 5] >> (row & 31)) & 1u;
-                if (hit)
-                    cap_insert(reinterpret_cast<unsigned long long*>(a.best) + ((uint64_t)j * a.n_groups + grp) * c.m,
-                               c.m, dist_key(d, (uint32_t)row));
-                acc[j] = -0.0f;
-                mx[j] = 0.0f;
-            }
-            ch = 0;
-            tile += gridDim.x;
-        } else {
-            ++ch;
-        }
-    }
+    group_scan_tiles<QF>(lds, a, [&](int j, uint32_t grp, uint64_t key) {
+        cap_insert(reinterpret_cast<unsigned long long*>(a.best) + ((uint64_t)j * a.n_groups + grp) * c.m, c.m, key);
+    });
 }
 
 // ------------------------------------------------------------------------------------

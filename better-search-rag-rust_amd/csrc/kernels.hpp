@@ -529,9 +529,9 @@ struct RangeArgs {
 // One workgroup per query over its emitted rows: the reference distance of every listed row; the
 // live rows with d <= radius[q] become the query's list, their number rcnt[q].
 hipError_t launch_range_rescore(const RangeArgs& a, hipStream_t s);
-// The exact fallback, k_scan_exact's tile loop: every valid live row with d <= radius claims a slot
-// of its query's list by an atomic add on rcnt[id] (zero before the launch) and stores its key when
-// the slot is below cap; the count stays exact beyond that.
+// The exact fallback, the exact scans' tile loop: every valid live row with d <=
+// radius claims a slot of its query's list by an atomic add on rcnt[id] (zero before the launch)
+// and stores its key when the slot is below cap; the count stays exact beyond that.
 hipError_t launch_range_scan(const RangeArgs& a, uint32_t grid, hipStream_t s);
 // One workgroup per query: a list of rcnt[q] <= capacity keys sorted ascending (distance, then
 // row) into out_idx / out_dist [nq][capacity] as (offset + row, distance), (~0, +inf) behind them;
@@ -638,7 +638,7 @@ struct CollapseWalkArgs {
     uint32_t* fail_cnt;         // one word
 };
 hipError_t launch_collapse_walk(const CollapseWalkArgs& a, hipStream_t s);
-// The group scan, launch_range_scan's tile loop: every valid row that is live (dead, nullable) and
+// The group scan, the same tile loop: every valid row that is live (dead, nullable) and
 // allowed lowers best[j][row_group[row]] to dist_key(d, row) by an atomic min, j the query's slot
 // in the launch (best: u64 [template width][n_groups], all-ones before the launch).  The allow bit
 // of slot j's query id: word row / 64 of mask query_mask[id] (mask 0 without a query_mask) of allow
@@ -686,7 +686,7 @@ struct CapWalkArgs {
     uint32_t per_group;  // >= 1 (a value >= k caps nothing)
 };
 hipError_t launch_cap_walk(const CapWalkArgs& a, hipStream_t s);
-// The capped group scan, launch_collapse_scan's arguments and tile loop with m entries per (query
+// The capped group scan, launch_collapse_scan's arguments and loop with m entries per (query
 // slot, group): s.best is u64 [template width][n_groups][m], all-ones before the launch, and ends
 // holding, for every (slot, group), the m smallest keys dist_key(d, row) of the group's live allowed
 // rows in no particular order (kKeyNone where the group has fewer).  1 <= m <= kCapMaxPerGroup.

@@ -93,12 +93,12 @@ def walk(cand_idx, cand_dist, cand_cnt, k, n, offset, row_group, with_group=True
 
 
 def scan(rows, dim, n, offset, na, qf32, nb, row_group, n_groups, qids, nqf, k, dead=None, allow=None,
-         query_mask=None):
+         query_mask=None, grid=None):
     """One round of the group scan over the slab rows [n_pad][ld] for the launch's nqf queries (qids
-    padded to the template width): the tables, launch_collapse_scan, launch_collapse_select,
-    launch_merge_parts, launch_collapse_finish.  The outputs [nq_all][k] (nq_all = len(qf32)) are
-    indexed by query id and start as a pattern.  Returns (rc, idx, dist, count, group, best
-    [nqf][n_groups])."""
+    padded to the template width): the tables, launch_collapse_scan (on `grid` workgroups; None:
+    scan_grid_for(n)), launch_collapse_select, launch_merge_parts, launch_collapse_finish.  The
+    outputs [nq_all][k] (nq_all = len(qf32)) are indexed by query id and start as a pattern.  Returns
+    (rc, idx, dist, count, group, best [nqf][n_groups])."""
     L = lib()
     qids = np.ascontiguousarray(qids, np.int32)
     row_group = np.ascontiguousarray(row_group, np.uint32)
@@ -124,8 +124,8 @@ def scan(rows, dim, n, offset, na, qf32, nb, row_group, n_groups, qids, nqf, k, 
         qf32=np.ascontiguousarray(qf32, np.float32), nb=np.ascontiguousarray(nb, np.float32), dead=dead,
         row_group=row_group, n_groups=n_groups, nqf=nqf, allow=allow, allow_words=words,
         query_mask=None if query_mask is None else np.ascontiguousarray(query_mask, np.uint32), qids=qids, k=k,
-        grid=L.kc_collapse_scan_grid(n), sel_grid=sel_grid, best=best, part=part, keys=keys, out_idx=idx,
-        out_dist=dist, out_group=grp, out_count=cnt))
+        grid=L.kc_collapse_scan_grid(n) if grid is None else grid, sel_grid=sel_grid, best=best, part=part, keys=keys,
+        out_idx=idx, out_dist=dist, out_group=grp, out_count=cnt))
     rc = L.kc_collapse_scan(ctypes.byref(s))
     del keep
     return _rc(rc), idx, dist, cnt, grp, best

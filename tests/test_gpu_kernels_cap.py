@@ -218,6 +218,28 @@ def table_model(keys, rg, n_groups, m, ok):
     return t
 
 
+def tombstones_and_masks(rng, corp, ids, n, rg, k, m):
+    """The masked set-up of a launch over the first n rows for the queries ids: (live [n], masks
+    [3][n], allow words, mask id by query id, dead words)."""
+    # tombstones: a third of the rows, with every second row the first query keeps;
+    # three masks: a random half; everything but the rows the launch's last query
+    # keeps; everything
+    live = rng.random(n) >= 0.3
+    k0 = kp.cap_model(corp.all_dist[ids[0]][:n], rg, k, m)[0]
+    live[k0[k0 != IDX_NONE].astype(np.int64)[::2]] = False
+    masks = np.ones((3, n), bool)
+    masks[0] = rng.random(n) < 0.5
+    kl_ = kp.cap_model(corp.all_dist[ids[-1]][:n], rg, k, m, live=live)[0]
+    masks[1, kl_[kl_ != IDX_NONE].astype(np.int64)] = False
+    allow = np.stack([kr.pack_dead(x) for x in masks])
+    # (the mask ids by query id: two queries of one launch differ in their masks)
+    qm = np.arange(corp.nq, dtype=np.uint32) % 3
+    qm[ids[-1]] = 1
+    if len(ids) >= 2:
+        qm[ids[0]] = 0
+    return live, masks, allow, qm, kr.pack_dead(~live, corp.rows.shape[0] // 64)
+
+
 @pytest.mark.parametrize("nqf", [1, 2, 3, 5, 8])
 @pytest.mark.parametrize("n,dim", [(130, 768), (600, 768), (600, 200)])
 def test_scan_select_finish(gpu, n, dim, nqf):
@@ -236,23 +258,7 @@ def test_scan_select_finish(gpu, n, dim, nqf):
                 live = np.ones(n, bool)
                 dead = allow = qm = masks = None
                 if masked:
-                    # tombstones: a third of the rows, with every second row the first query keeps;
-                    # three masks: a random half; everything but the rows the launch's last query
-                    # keeps; everything
-                    live = rng.random(n) >= 0.3
-                    k0 = kp.cap_model(corp.all_dist[ids[0]], rg, k, m)[0]
-                    live[k0[k0 != IDX_NONE].astype(np.int64)[::2]] = False
-                    masks = np.ones((3, n), bool)
-                    masks[0] = rng.random(n) < 0.5
-                    kl_ = kp.cap_model(corp.all_dist[ids[-1]], rg, k, m, live=live)[0]
-                    masks[1, kl_[kl_ != IDX_NONE].astype(np.int64)] = False
-                    allow = np.stack([kr.pack_dead(x) for x in masks])
-                    # (the mask ids by query id: two queries of one launch differ in their masks)
-                    qm = np.arange(corp.nq, dtype=np.uint32) % 3
-                    qm[ids[-1]] = 1
-                    if nqf >= 2:
-                        qm[ids[0]] = 0
-                    dead = kr.pack_dead(~live, corp.rows.shape[0] // 64)
+                    live, masks, allow, qm, dead = tombstones_and_masks(rng, corp, ids, n, rg, k, m)
                 rc, oi, od, oc, og, best = kp.scan(corp.rows, corp.dim, n, OFFSET, corp.na, corp.qf32, corp.nb, rg, ng,
                                                    qids, nqf, k, m, dead=dead, allow=allow, query_mask=qm)
                 assert rc == 0
@@ -297,6 +303,55 @@ def test_scan_select_finish(gpu, n, dim, nqf):
                                                256, m, allow=allow)
             firsts = sorted(int(r) for g in set(rg[run].tolist()) for r in run[rg[run] == g][:m])
             assert rc == 0 and oc[q] == len(firsts) and list(oi[q][:oc[q]]) == firsts, (ng, m)
+
+
+def test_scan_grids(gpu):
+    """launch_cap_scan on other grids than scan_grid_for(n), which gives every workgroup one tile here:
+    on 2 workgroups one of them walks a second tile at n = 600 and both do at n = 1000 (the first chunk
+    of the next tile is prefetched during the last chunk of this one), and one has no tile at n = 1; on
+    5 there are more workgroups than tiles.  The same tables and outputs."""
+    corp = scan_corpus(1000, 200)
+    k = 10
+    launches = 0
+    for nqf in (1, 3, 8):
+        rng = np.random.default_rng(7100 + nqf)
+        width = 1 if nqf <= 1 else 2 if nqf <= 2 else 4 if nqf <= 4 else 8
+        perm = [int(x) for x in rng.permutation(corp.nq)]
+        ids = perm[:nqf]
+        qids = np.array(perm[:width], np.int32)  # (the padding ids: queries outside the launch)
+        for n in (1, 600, 1000):
+            rg, ng = np.arange(n) // 7, n // 7 + 1
+            for m in (1, 3):
+                for masked in (False, True):
+                    live = np.ones(n, bool)
+                    dead = allow = qm = masks = None
+                    if masked:
+                        live, masks, allow, qm, dead = tombstones_and_masks(rng, corp, ids, n, rg, k, m)
+                    want = []
+                    for q in ids:
+                        allowed = masks[qm[q]] if masked else None
+                        ok = live & (allowed if masked else True)
+                        want.append((table_model(corp.all_keys[q][:n], rg, ng, m, ok),
+                                     kp.cap_model(corp.all_dist[q][:n], rg, k, m, live=live, allowed=allowed,
+                                                  offset=OFFSET)))
+                    for grid in (2, 5):
+                        rc, oi, od, oc, og, best = kp.scan(corp.rows, corp.dim, n, OFFSET, corp.na, corp.qf32, corp.nb,
+                                                           rg, ng, qids, nqf, k, m, dead=dead, allow=allow,
+                                                           query_mask=qm, grid=grid)
+                        assert rc == 0
+                        launches += 1
+                        for j, q in enumerate(ids):
+                            what = (nqf, n, m, masked, grid, j, q)
+                            table, (wi, wd, wg, wc) = want[j]
+                            assert np.array_equal(np.sort(best[j], axis=1), table), (what, "table")
+                            assert oc[q] == wc, (what, oc[q], wc)
+                            assert np.array_equal(oi[q], wi), (what, oi[q], wi)
+                            assert np.array_equal(od[q].view(np.uint32), wd.view(np.uint32)), what
+                            assert np.array_equal(og[q], wg), what
+                        assert (best[nqf:] == KEY_NONE).all()
+                        others = np.setdiff1d(np.arange(corp.nq), ids)
+                        assert (oi[others] == 0x1234).all() and (oc[others] == FILL).all() and (og[others] == FILL).all()
+    assert launches == 72
 
 
 def test_scan_refusals(gpu):

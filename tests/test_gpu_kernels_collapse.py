@@ -213,6 +213,35 @@ def best_model(dist, n, rg, n_groups, ok):
     return t
 
 
+def tombstones_and_masks(rng, corp, ids, n, rg, ng, k):
+    """The masked set-up of a launch over the first n rows for the queries ids: (live [corp.n], masks
+    [3][n], allow words, mask id by query id)."""
+    # tombstones: a third of the rows, the unmasked heads of the first query among
+    # them, and the whole of group 1 (or of the first head's group)
+    live = rng.random(corp.n) >= 0.3
+    h0 = kl.collapse_model(corp.all_dist[ids[0]][:n], rg, k)[0]
+    heads0 = h0[h0 != IDX_NONE].astype(np.int64)
+    live[heads0[::2]] = False
+    if ng > 1:
+        live[:n][rg == rg[min(1, n - 1)]] = False
+    # three masks: a random half; everything but the heads of the launch's last query
+    # and one whole group; everything
+    masks = np.ones((3, n), bool)
+    masks[0] = rng.random(n) < 0.5
+    hl = kl.collapse_model(corp.all_dist[ids[-1]][:n], rg, k, live=live[:n])[0]
+    headsl = hl[hl != IDX_NONE].astype(np.int64)
+    masks[1, headsl] = False
+    if len(headsl) > 1:
+        masks[1, rg == rg[headsl[1]]] = False
+    allow = np.stack([kr.pack_dead(m) for m in masks])
+    # (the mask ids by query id: two queries of one launch differ in their masks)
+    qm = np.arange(corp.nq, dtype=np.uint32) % 3
+    qm[ids[-1]] = 1
+    if len(ids) >= 2:
+        qm[ids[0]] = 0
+    return live, masks, allow, qm
+
+
 SCAN_CASES = [(100, nqf) for nqf in range(1, 9)] + [(d, nqf) for d in (8, 768) for nqf in (1, 5, 8)]
 
 
@@ -235,29 +264,7 @@ def test_scan_select_finish(gpu, dim, nqf):
                 qm = None
                 masks = None
                 if masked:
-                    # tombstones: a third of the rows, the unmasked heads of the first query among
-                    # them, and the whole of group 1 (or of the first head's group)
-                    live = rng.random(corp.n) >= 0.3
-                    h0 = kl.collapse_model(corp.all_dist[ids[0]][:n], rg, k)[0]
-                    heads0 = h0[h0 != IDX_NONE].astype(np.int64)
-                    live[heads0[::2]] = False
-                    if ng > 1:
-                        live[:n][rg == rg[min(1, n - 1)]] = False
-                    # three masks: a random half; everything but the heads of the launch's last query
-                    # and one whole group; everything
-                    masks = np.ones((3, n), bool)
-                    masks[0] = rng.random(n) < 0.5
-                    hl = kl.collapse_model(corp.all_dist[ids[-1]][:n], rg, k, live=live[:n])[0]
-                    headsl = hl[hl != IDX_NONE].astype(np.int64)
-                    masks[1, headsl] = False
-                    if len(headsl) > 1:
-                        masks[1, rg == rg[headsl[1]]] = False
-                    allow = np.stack([kr.pack_dead(m) for m in masks])
-                    # (the mask ids by query id: two queries of one launch differ in their masks)
-                    qm = np.arange(corp.nq, dtype=np.uint32) % 3
-                    qm[ids[-1]] = 1
-                    if nqf >= 2:
-                        qm[ids[0]] = 0
+                    live, masks, allow, qm = tombstones_and_masks(rng, corp, ids, n, rg, ng, k)
                 dead = kr.pack_dead(~live, corp.rows.shape[0] // 64) if masked else None
                 rc, oi, od, oc, og, best = kl.scan(corp.rows, corp.dim, n, OFFSET, corp.na, corp.qf32, corp.nb, rg, ng,
                                                    qids, nqf, k, dead=dead, allow=allow, query_mask=qm)
@@ -301,6 +308,51 @@ def test_scan_select_finish(gpu, dim, nqf):
         groups = sorted(set(rg[run].tolist()))
         firsts = sorted(int(run[rg[run] == g][0]) for g in groups)
         assert rc == 0 and oc[q] == len(groups) and list(oi[q][:oc[q]]) == firsts
+
+
+def test_scan_grids(gpu):
+    """launch_collapse_scan on other grids than scan_grid_for(n), which gives every workgroup one tile
+    here: on 2 workgroups one of them walks a second tile at n = 600 and both do at n = 1000 (the first
+    chunk of the next tile is prefetched during the last chunk of this one), and one has no tile at
+    n = 1; on 5 there are more workgroups than tiles.  The same tables and outputs."""
+    corp = scan_corpus(100)
+    k = 10
+    launches = 0
+    for nqf in (1, 3, 8):
+        rng = np.random.default_rng(7000 + nqf)
+        width = 1 if nqf <= 1 else 2 if nqf <= 2 else 4 if nqf <= 4 else 8
+        ids = [int(x) for x in rng.permutation(corp.nq)[:nqf]]
+        qids = np.array(ids + [ids[0]] * (width - nqf), np.int32)
+        for n in (1, 600, 1000):
+            rg, ng = groups_of("7", n)
+            for masked in (False, True):
+                live, masks, allow, qm, dead = np.ones(corp.n, bool), None, None, None, None
+                if masked:
+                    live, masks, allow, qm = tombstones_and_masks(rng, corp, ids, n, rg, ng, k)
+                    dead = kr.pack_dead(~live, corp.rows.shape[0] // 64)
+                want = []
+                for q in ids:
+                    allowed = masks[qm[q]] if masked else None
+                    ok = live[:n] & (allowed if masked else True)
+                    want.append((best_model(corp.all_dist[q], n, rg, ng, ok),
+                                 kl.collapse_model(corp.all_dist[q][:n], rg, k, live=live[:n], allowed=allowed,
+                                                   offset=OFFSET)))
+                for grid in (2, 5):
+                    rc, oi, od, oc, og, best = kl.scan(corp.rows, corp.dim, n, OFFSET, corp.na, corp.qf32, corp.nb, rg,
+                                                       ng, qids, nqf, k, dead=dead, allow=allow, query_mask=qm, grid=grid)
+                    assert rc == 0
+                    launches += 1
+                    for j, q in enumerate(ids):
+                        what = (nqf, n, masked, grid, j, q)
+                        table, (wi, wd, wg, wc) = want[j]
+                        assert np.array_equal(best[j], table), (what, "table")
+                        assert oc[q] == wc, (what, oc[q], wc)
+                        assert np.array_equal(oi[q], wi), (what, oi[q], wi)
+                        assert np.array_equal(od[q].view(np.uint32), wd.view(np.uint32)), what
+                        assert np.array_equal(og[q], wg), what
+                    others = np.setdiff1d(np.arange(corp.nq), ids)
+                    assert (oi[others] == 0x1234).all() and (oc[others] == FILL).all() and (og[others] == FILL).all()
+    assert launches == 36
 
 
 def test_scan_refusals(gpu):
