@@ -65,6 +65,8 @@ BSR_PATH_COLLAPSE = 8192        # bsr_local_top_k_collapsed ran (with the bits o
 BSR_PATH_COLLAPSE_SCAN = 16384  # ... and a query of the batch was answered by the group scan
 BSR_PATH_CAP = 32768            # bsr_local_top_k_capped ran (with the bits of the candidate search)
 BSR_PATH_CAP_SCAN = 65536       # ... and a query of the batch was answered by the capped group scan
+BSR_PATH_SCORE = 131072         # bsr_local_score_ids / bsr_local_rerank_ids ran
+BSR_SCORE_MAX_IDS = 4096        # the longest id list bsr_local_rerank_ids orders (include/bsr.h)
 BSR_CAP_MAX_PER_GROUP = 16      # the largest per_group of a capped search (include/bsr.h)
 BSR_RANGE_MAX_RESULTS = 4096  # result slots per query of a range search (include/bsr.h)
 BSR_MASK_AUTO = 0    # bsr_local_top_k_masked modes (include/bsr.h)
@@ -158,6 +160,8 @@ def lib() -> ctypes.CDLL:
                                                      _P, _P]),
         "bsr_local_top_k_capped": (ctypes.c_int, [_P, _P, u32, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P,
                                                   _P, _P, _P]),
+        "bsr_local_score_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P]),
+        "bsr_local_rerank_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_global_top_k_capped": (ctypes.c_int, [_P, _P, _P, _P, u32, u32, u32, u32, u32, _P, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
@@ -183,7 +187,7 @@ def lib() -> ctypes.CDLL:
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
-                "bsr_local_top_k_capped", "bsr_global_top_k_capped"}
+                "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -640,6 +644,97 @@ class Index:
                                                    _ptr(allow_words), int(shape[-1]), n_masks, _ptr(query_mask),
                                                    _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist),
                                                    _ptr(out_count)))
+
+    # ---- score given ids (bsr_local_score_ids / bsr_local_rerank_ids) ----
+    def _queries_and_id_lists(self, queries, ids):
+        """(q [nq][dim] f32, ids [nq][m] u64) of a batch and its per-query lists of GLOBAL ids: a 2-D
+        integer array, or a list of lists -- ragged lists are padded with ~0, the value of an absent
+        slot, and a negative entry means the same.  A 1-D ids with one query is that query's list."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
+        nq = q.shape[0]
+        pad = np.uint64(0xFFFFFFFFFFFFFFFF)
+        if isinstance(ids, np.ndarray):
+            lists = ids.reshape(1, -1) if ids.ndim == 1 else ids
+            if lists.ndim != 2:
+                raise BsrError(-1, "ids is [n_queries][m]")
+            lists = list(lists)
+        else:
+            lists = list(ids)
+            if not any(isinstance(x, (list, tuple, np.ndarray)) for x in lists):
+                lists = [lists]  # (one flat list: one query's)
+        if len(lists) != nq:
+            raise BsrError(-1, f"{len(lists)} id lists for {nq} queries")
+        rows = []
+        for lst in lists:
+            a = np.asarray(lst).reshape(-1)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                # (Python integers on both sides of 2^63, or beside a negative one, have no common
+                # integer dtype: taken one by one)
+                flat = np.asarray(lst, dtype=object).reshape(-1).tolist()
+                if not all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in flat):
+                    raise BsrError(-1, "ids must be integers")
+                if any(x >= 1 << 64 for x in flat):
+                    raise BsrError(-1, "an id does not fit 64 bits")
+                rows.append(np.array([int(pad) if x < 0 else int(x) for x in flat], np.uint64))
+                continue
+            u = a.astype(np.uint64)
+            if a.size and np.issubdtype(a.dtype, np.signedinteger):
+                u[a < 0] = pad
+            rows.append(u)
+        m = max((r.size for r in rows), default=0)
+        if m == 0:
+            raise BsrError(-1, "an id list has at least one slot")
+        out = np.full((nq, m), pad, np.uint64)
+        for i, r in enumerate(rows):
+            out[i, :r.size] = r
+        return q, out
+
+    def score_ids(self, queries, ids, return_found: bool = False):
+        """The distance of stored rows the caller names (bsr_local_score_ids) -> dist [Q,m] f32,
+        aligned with ids: the reference's f32 distance of row ids[q][j] to query q, +inf where the
+        slot is absent -- padding, an id outside this shard, a deleted row; never an error.  ids:
+        GLOBAL ids as the searches return them, [Q][m] integers or a list of lists (ragged lists are
+        padded with ~0; negative entries are padding; a 1-D list with one query is accepted); an id
+        may repeat.  return_found: also the present slots per query, [Q] u32.  Over several ranks:
+        every rank scores the same ids and np.minimum of the results is the answer."""
+        q, lists = self._queries_and_id_lists(queries, ids)
+        nq, m = lists.shape
+        od = np.empty((nq, m), np.float32)
+        of = np.empty(nq, np.uint32)
+        _check(lib().bsr_local_score_ids(self._h, _ptr(q), nq, _ptr(lists), m, _ptr(od), _ptr(of)))
+        return (od, of) if return_found else od
+
+    def rerank(self, queries, ids, k=None):
+        """The k best of the caller's candidates (bsr_local_rerank_ids) -> (idx [Q,k] u64, dist [Q,k]
+        f32, count [Q] u32): the distinct present ids of each list in (distance asc, id asc) order,
+        (~0, +inf) behind count[q] = min(k, distinct present ids).  ids: as score_ids', at most
+        BSR_SCORE_MAX_IDS per query; k: the list length by default, not bounded by max_k."""
+        q, lists = self._queries_and_id_lists(queries, ids)
+        nq, m = lists.shape
+        k = m if k is None else int(k)
+        if m > BSR_SCORE_MAX_IDS:
+            raise BsrError(-1, f"m={m} above BSR_SCORE_MAX_IDS={BSR_SCORE_MAX_IDS}")
+        if k < 1 or k > m:
+            raise BsrError(-1, f"k={k} outside [1, m={m}]")
+        oi = np.empty((nq, k), np.uint64)
+        od = np.empty((nq, k), np.float32)
+        oc = np.empty(nq, np.uint32)
+        _check(lib().bsr_local_rerank_ids(self._h, _ptr(q), nq, _ptr(lists), m, k, _ptr(oi), _ptr(od), _ptr(oc)))
+        return oi, od, oc
+
+    def score_ids_device(self, queries, nq: int, ids, m: int, out_dist, out_found=None):
+        """Zero-copy variant of score_ids on caller buffers (torch tensors or numpy arrays, each host
+        or device): queries [nq][dim] f32, ids [nq][m] u64, out_dist [nq][m] f32, out_found [nq] u32."""
+        _check(lib().bsr_local_score_ids(self._h, _ptr(queries), nq, _ptr(ids), m, _ptr(out_dist), _ptr(out_found)))
+
+    def rerank_device(self, queries, nq: int, ids, m: int, k: int, out_idx, out_dist, out_count):
+        """Zero-copy variant of rerank on caller buffers: out_idx / out_dist [nq][k], out_count [nq]."""
+        _check(lib().bsr_local_rerank_ids(self._h, _ptr(queries), nq, _ptr(ids), m, k, _ptr(out_idx), _ptr(out_dist),
+                                          _ptr(out_count)))
 
     def mmr_search(self, queries, k: int, fetch_k=None, lambda_mult: float = 0.5, allow_mask=None, allow_ids=None,
                    allow_masks=None, query_mask=None, mask_mode="auto", return_rank: bool = False):

@@ -43,6 +43,10 @@ int bsr_local_range_search_masked_impl(bsr_index* ix, const float* queries, uint
                                        uint32_t capacity, const uint64_t* allow, uint64_t allow_words,
                                        uint32_t n_masks, const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx,
                                        float* out_dist, uint32_t* out_count);
+int bsr_local_score_ids_impl(bsr_index* ix, const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m,
+                             float* out_dist, uint32_t* out_found);
+int bsr_local_rerank_ids_impl(bsr_index* ix, const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m,
+                              uint32_t k, uint64_t* out_idx, float* out_dist, uint32_t* out_count);
 int bsr_local_top_k_mmr_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
                              float lambda, const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                              const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
@@ -392,6 +396,16 @@ int bsr_local_range_search_masked(bsr_index* ix, const float* queries, uint32_t 
                                   uint32_t* out_count) {
     BSR_GUARD(bsr_local_range_search_masked_impl(ix, queries, n_queries, radius, capacity, allow, allow_words, n_masks,
                                                  query_mask, mode, out_idx, out_dist, out_count));
+}
+
+int bsr_local_score_ids(bsr_index* ix, const float* queries, uint32_t n_queries, const uint64_t* ids, uint32_t m,
+                        float* out_dist, uint32_t* out_found) {
+    BSR_GUARD(bsr_local_score_ids_impl(ix, queries, n_queries, ids, m, out_dist, out_found));
+}
+
+int bsr_local_rerank_ids(bsr_index* ix, const float* queries, uint32_t n_queries, const uint64_t* ids, uint32_t m,
+                         uint32_t k, uint64_t* out_idx, float* out_dist, uint32_t* out_count) {
+    BSR_GUARD(bsr_local_rerank_ids_impl(ix, queries, n_queries, ids, m, k, out_idx, out_dist, out_count));
 }
 
 int bsr_local_top_k_mmr(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint32_t fetch_k,

@@ -2171,6 +2171,117 @@ int bsr_local_range_search_impl(bsr_index* ix, const float* queries, uint32_t nq
 }
 
 // ---------------------------------------------------------------------------------------
+// Scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids)
+// ---------------------------------------------------------------------------------------
+int bsr_index::score_ids_device(const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m, uint32_t k,
+                                uint64_t* out_idx, float* out_dist, uint32_t* out_cnt) {
+    bsr_index* ix = this;
+    if (!loaded) return set_error(BSR_E_STATE, "index not loaded");
+    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_SCORE));
+    stats.row_ebound = 0.0f;  // (no filter runs: every field but the three below stays 0)
+    stats.n_candidates = m;
+    if (nq == 0) return BSR_OK;
+
+    const bool rerank = k > 0;
+    const size_t nm = (size_t)nq * m;
+    const uint32_t qpad = qpad_for(nq);
+    BSR_TRY(query_buffers(ix, nq, qpad, 1));
+    BSR_TRY(scr_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    if (rerank) {
+        BSR_TRY(scr_keys.ensure(nm * sizeof(uint64_t)));
+        BSR_TRY(scr_idx.ensure((size_t)nq * k * sizeof(uint64_t)));
+        BSR_TRY(scr_odist.ensure((size_t)nq * k * sizeof(float)));
+        BSR_TRY(scr_ocnt.ensure((size_t)nq * sizeof(uint32_t)));
+    } else {
+        BSR_TRY(scr_dist.ensure(nm * sizeof(float)));
+    }
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
+    const uint64_t* isrc = nullptr;
+    BSR_TRY(on_device(ix, scr_ids, ids, nm * sizeof(uint64_t), is_device_ptr(ids), &isrc));
+    // (no filter operand: BSR_FLAG_EXACT_ONLY and the sticky norm flags do not matter here)
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, false), stream));
+    BSR_HIP(hipMemsetAsync(scr_cnt.p, 0, (size_t)nq * sizeof(uint32_t), stream));
+    ScoreArgs sa{};
+    sa.rows = rows.as<float>();
+    sa.ld = ld;
+    sa.dim = dim;
+    sa.n = n;
+    sa.offset = global_offset;
+    sa.na = na.as<float>();
+    sa.qf32 = qf32.as<float>();
+    sa.nb = nb.as<float>();
+    sa.dead = dead_bits();
+    sa.ids = isrc;
+    sa.m = m;
+    sa.nq = nq;
+    if (rerank) {
+        sa.keys = scr_keys.as<uint64_t>();
+        sa.kcnt = scr_cnt.as<uint32_t>();
+    } else {
+        sa.dist = scr_dist.as<float>();
+        sa.found = scr_cnt.as<uint32_t>();
+    }
+    ev_begin(ix, ev_rescore);
+    BSR_HIP(launch_score_ids(sa, stream));
+    if (rerank)
+        BSR_HIP(launch_score_finish(scr_keys.as<uint64_t>(), scr_cnt.as<uint32_t>(), m, nq, k, global_offset,
+                                    scr_idx.as<uint64_t>(), scr_odist.as<float>(), scr_ocnt.as<uint32_t>(), stream));
+    ev_end(ix, ev_rescore);
+    // The one status readback (a non-finite query), before any of the caller's arrays is written.
+    BSR_HIP(hipMemcpyAsync(h_res, d_status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BSR_HIP(stream_wait(stream));
+    BSR_TRY(check_queries(ix, nq));
+    if (rerank) {
+        const size_t nk = (size_t)nq * k;
+        BSR_HIP(hipMemcpyAsync(out_idx, scr_idx.p, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, scr_odist.p, nk * sizeof(float), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_cnt, scr_ocnt.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    } else {
+        BSR_HIP(hipMemcpyAsync(out_dist, scr_dist.p, nm * sizeof(float), hipMemcpyDefault, stream));
+        if (out_cnt) BSR_HIP(hipMemcpyAsync(out_cnt, scr_cnt.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    ev_end(ix, ev_total);
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+// The first checks of both entry points, before any device is touched.
+static int check_score_args(const bsr_index* ix, uint32_t nq, uint32_t m) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (m == 0) return set_error(BSR_E_INVALID, "m = 0 (an id list has at least one slot)");
+    if ((uint64_t)nq * m > 0xffffffffull)
+        return set_error(BSR_E_INVALID, "n_queries * m = %llu does not fit 32 bits", (unsigned long long)nq * m);
+    return BSR_OK;
+}
+
+int bsr_local_score_ids_impl(bsr_index* ix, const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m,
+                             float* out_dist, uint32_t* out_found) {
+    BSR_TRY(check_score_args(ix, nq, m));
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && !ids) return set_error(BSR_E_INVALID, "null ids");
+    if (nq && !out_dist) return set_error(BSR_E_INVALID, "null output");
+    BSR_TRY(ix->score_ids_device(queries, nq, ids, m, 0, nullptr, out_dist, out_found));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+int bsr_local_rerank_ids_impl(bsr_index* ix, const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m,
+                              uint32_t k, uint64_t* out_idx, float* out_dist, uint32_t* out_count) {
+    BSR_TRY(check_score_args(ix, nq, m));
+    if (m > BSR_SCORE_MAX_IDS) return set_error(BSR_E_INVALID, "m=%u above BSR_SCORE_MAX_IDS=%u", m, BSR_SCORE_MAX_IDS);
+    if (k == 0 || k > m) return set_error(BSR_E_INVALID, "k=%u outside [1, m=%u]", k, m);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && !ids) return set_error(BSR_E_INVALID, "null ids");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    BSR_TRY(ix->score_ids_device(queries, nq, ids, m, k, out_idx, out_dist, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // Masked range search (bsr_local_range_search_masked)
 // ---------------------------------------------------------------------------------------
 // The exact range over row lists for the queries `listed` (ascending ids), every one over the list

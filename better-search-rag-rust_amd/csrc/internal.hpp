@@ -245,6 +245,19 @@ struct bsr_index {
     bsr::DevBuf rng_cnt;     // u32 [nq]: their exact counts
     bsr::DevBuf rng_idx, rng_dist, rng_out_cnt;  // the result rows [nq][capacity], the counts [nq]
 
+    // Scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids): the
+    // distance of every id of ids [nq][m] (k = 0: into out_dist [nq][m] and out_found, nullable), or
+    // the k best distinct present ids of every list (k > 0: out_idx / out_dist [nq][k], out_count).
+    // Launched directly, never captured; everything goes to buffers of its own first and to the
+    // caller's arrays, host or device, only once the status words are read.
+    int score_ids_device(const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m, uint32_t k,
+                         uint64_t* out_idx, float* out_dist, uint32_t* out_cnt);
+    bsr::DevBuf scr_ids;    // u64 [nq][m]: a host id array's device copy
+    bsr::DevBuf scr_dist;   // f32 [nq][m]: the aligned distances
+    bsr::DevBuf scr_keys;   // u64 [nq][m]: the rerank's distance keys, any order
+    bsr::DevBuf scr_cnt;    // u32 [nq]: the present slots (score) or the keys (rerank) of a query
+    bsr::DevBuf scr_idx, scr_odist, scr_ocnt;  // the rerank's result rows [nq][k], the counts [nq]
+
     // Masked range search (bsr_local_range_search_masked): the range search with an
     // allow mask per query group -- the grouped masked search's mask buffers (grp_*), the range
     // search's result buffers (rng_*), and the row lists in segments.

@@ -1724,11 +1724,44 @@ __global__ __launch_bounds__(1024) void k_range_tau(const float* __restrict__ ra
     }
 }
 
+// One wave's exact walk of 64 rows against one vector (k_range_rescore, k_score_ids): lane l's row
+// myrow (any row below n_pad) goes chunk by chunk through the wave's own LDS stage `lds` (64 x 68
+// floats; load_cand_chunk, two chunks in flight) and the lane walks it in index order (seq_chunk)
+// against qv -- the vector's ld floats, in LDS or in global memory.  acc and mx: the sequential dot
+// and max|a_i - b_i| that finish_distance takes.
+__device__ __forceinline__ void wave_walk_rows(float* lds, const float* __restrict__ rows, uint32_t ld, uint32_t dim,
+                                               uint32_t myrow, const float* qv, int lane, float (&acc)[1],
+                                               float (&mx)[1]) {
+    const uint32_t nch = ld / 64;
+    uint32_t lrow[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) lrow[i] = (uint32_t)__shfl((int)myrow, (i * 64 + lane) >> 4, kWave);
+    auto step = [&](f32x4_t (&pre)[16], uint32_t ch) {
+        wave_sync();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int L16 = i * 64 + lane;
+            *reinterpret_cast<f32x4_t*>(lds + (L16 >> 4) * 68 + (L16 & 15) * 4) = pre[i];
+        }
+        wave_sync();
+        if (ch + 2 < nch) load_cand_chunk(pre, rows, ld, lrow, ch + 2, lane);
+        const float* const bb[1] = {qv + ch * 64};
+        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+        seq_chunk<1>(lds + lane * 68, bb, nvalid, acc, mx);
+    };
+    f32x4_t preA[16], preB[16];
+    load_cand_chunk(preA, rows, ld, lrow, 0, lane);
+    if (nch > 1) load_cand_chunk(preB, rows, ld, lrow, 1, lane);
+    for (uint32_t ch = 0; ch < nch; ch += 2) {
+        step(preA, ch);
+        if (ch + 1 < nch) step(preB, ch + 1);
+    }
+}
+
 // One workgroup of four waves per query; wave w takes the emitted keys w*64 + lane, + 256, ...:
-// its 64 rows go chunk by chunk through its own LDS stage (load_cand_chunk, two chunks in flight)
-// and each lane walks its row in index order (seq_chunk, finish_distance) against the query's LDS
-// copy -- the arithmetic of k_rescore.  The in-range live rows claim the slots of the query's list
-// from a counter in LDS, a wave at a time.
+// its 64 rows go through wave_walk_rows against the query's LDS copy and finish_distance -- the
+// arithmetic of k_rescore.  The in-range live rows claim the slots of the query's list from a
+// counter in LDS, a wave at a time.
 __global__ __launch_bounds__(256) void k_range_rescore(RangeArgs a) {
     constexpr int W = 4, STAGE = 64 * 68, QMAX = 1024;
     __shared__ __attribute__((aligned(16))) float lds_all[W * STAGE + QMAX];
@@ -1750,7 +1783,7 @@ __global__ __launch_bounds__(256) void k_range_rescore(RangeArgs a) {
         return;
     }
     if (threadIdx.x == 0) s_n = 0;
-    const uint32_t ld = a.ld, dim = a.dim, nch = ld / 64;
+    const uint32_t ld = a.ld, dim = a.dim;
     const float* const qrow = a.qf32 + (uint64_t)q * ld;
     const bool qlds = ld <= (uint32_t)QMAX;  // (longer rows read the query from global memory)
     if (qlds)
@@ -1766,29 +1799,7 @@ __global__ __launch_bounds__(256) void k_range_rescore(RangeArgs a) {
         const bool valid = ck != kKeyNone;
         const uint32_t myrow = valid ? key_row(ck) : 0u;
         float acc[1] = {-0.0f}, mx[1] = {0.0f};
-        uint32_t lrow[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) lrow[i] = (uint32_t)__shfl((int)myrow, (i * 64 + lane) >> 4, kWave);
-        auto step = [&](f32x4_t (&pre)[16], uint32_t ch) {
-            wave_sync();
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int L16 = i * 64 + lane;
-                *reinterpret_cast<f32x4_t*>(lds + (L16 >> 4) * 68 + (L16 & 15) * 4) = pre[i];
-            }
-            wave_sync();
-            if (ch + 2 < nch) load_cand_chunk(pre, rows, ld, lrow, ch + 2, lane);
-            const float* const bb[1] = {(qlds ? ldq : qrow) + ch * 64};
-            const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
-            seq_chunk<1>(lds + lane * 68, bb, nvalid, acc, mx);
-        };
-        f32x4_t preA[16], preB[16];
-        load_cand_chunk(preA, rows, ld, lrow, 0, lane);
-        if (nch > 1) load_cand_chunk(preB, rows, ld, lrow, 1, lane);
-        for (uint32_t ch = 0; ch < nch; ch += 2) {
-            step(preA, ch);
-            if (ch + 1 < nch) step(preB, ch + 1);
-        }
+        wave_walk_rows(lds, rows, ld, dim, myrow, qlds ? ldq : qrow, lane, acc, mx);
         const float mag_a = a.na[myrow];
         const uint32_t dw = a.dead ? reinterpret_cast<const uint32_t*>(a.dead)[myrow >> 5] : 0u;
         const float d = finish_distance(acc[0], mx[0], mag_a, mag_b);
@@ -1983,9 +1994,31 @@ __global__ __launch_bounds__(256, 2) void k_range_scan_list(RangeListArgs a) {
     }
 }
 
-// One workgroup per query: its list (any order) through a bitonic network in LDS over the next
-// power of two (at least 64) padded with kKeyNone -- u64 order is (distance, row) order -- then the
-// result rows.  A list longer than the capacity leaves only padding; the count is written either way.
+// A workgroup's list src[0 .. c) (any order, 0 < c <= kRangeMaxResults, uniform over the workgroup)
+// sorted ascending into sk: a bitonic network in LDS over the next power of two (at least 64) padded
+// with kKeyNone -- u64 order is (distance, row) order.  Ends behind a barrier.
+__device__ __forceinline__ void lds_sort_keys(uint64_t* sk, const uint64_t* __restrict__ src, uint32_t c,
+                                              uint32_t t) {
+    uint32_t P = 64;
+    while (P < c) P <<= 1;
+    for (uint32_t i = t; i < P; i += blockDim.x) sk[i] = i < c ? src[i] : kKeyNone;
+    __syncthreads();
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = t; i < P; i += blockDim.x) {
+                const uint32_t p = i ^ j;
+                if (p > i) {
+                    const uint64_t x = sk[i], y = sk[p];
+                    const bool up = (i & k) == 0;
+                    if ((x > y) == up) { sk[i] = y; sk[p] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// One workgroup per query: its list through lds_sort_keys, then the result rows.  A list longer
+// than the capacity leaves only padding; the count is written either way.
 __global__ __launch_bounds__(256) void k_range_finish(const uint64_t* __restrict__ keys,
                                                       const uint32_t* __restrict__ rcnt, uint32_t cap,
                                                       uint32_t capacity, uint64_t offset,
@@ -1997,31 +2030,105 @@ __global__ __launch_bounds__(256) void k_range_finish(const uint64_t* __restrict
     const uint32_t c = rcnt[q];
     const bool fits = c <= capacity;
     if (t == 0) out_count[q] = c;
-    if (fits && c > 0) {  // (uniform over the workgroup)
-        uint32_t P = 64;
-        while (P < c) P <<= 1;
-        const uint64_t* src = keys + (uint64_t)q * cap;
-        for (uint32_t i = t; i < P; i += blockDim.x) sk[i] = i < c ? src[i] : kKeyNone;
-        __syncthreads();
-        for (uint32_t k = 2; k <= P; k <<= 1)
-            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-                for (uint32_t i = t; i < P; i += blockDim.x) {
-                    const uint32_t p = i ^ j;
-                    if (p > i) {
-                        const uint64_t x = sk[i], y = sk[p];
-                        const bool up = (i & k) == 0;
-                        if ((x > y) == up) { sk[i] = y; sk[p] = x; }
-                    }
-                }
-                __syncthreads();
-            }
-    }
+    if (fits && c > 0) lds_sort_keys(sk, keys + (uint64_t)q * cap, c, t);  // (uniform over the workgroup)
     for (uint32_t i = t; i < capacity; i += blockDim.x) {
         const bool has = fits && i < c;
         const uint64_t key = has ? sk[i] : kKeyNone;
         out_idx[(uint64_t)q * capacity + i] = has ? offset + key_row(key) : ~0ull;
         out_dist[(uint64_t)q * capacity + i] = has ? key_dist(key) : INFINITY;
     }
+}
+
+// ------------------------------------------------------------------------------------
+// Scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids): the
+// reference's distance of every id of a per-query list, aligned with the list.
+// ------------------------------------------------------------------------------------
+// Workgroup (x, y) takes the slots x*256 .. x*256 + 255 of query q0 + y's list, a wave 64 consecutive
+// slots, lane = slot.  A slot is present when its id lies in [offset, offset + n) and its row has no
+// tombstone; the local row is formed only behind that check, and every other lane walks row 0 and
+// drops the result (a wave without a present slot walks nothing: an empty shard has no row 0).
+// The walk is wave_walk_rows against the query's LDS copy; na[row] is read, never recomputed.
+__global__ __launch_bounds__(256) void k_score_ids(ScoreArgs a) {
+    constexpr int W = 4, STAGE = 64 * 68, QMAX = 1024;
+    __shared__ __attribute__((aligned(16))) float lds_all[W * STAGE + QMAX];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float* const lds = lds_all + w * STAGE;
+    float* const ldq = lds_all + W * STAGE;
+    const uint32_t q = a.q0 + blockIdx.y;
+    const uint32_t ld = a.ld;
+    const float* const qrow = a.qf32 + (uint64_t)q * ld;
+    const bool qlds = ld <= (uint32_t)QMAX;  // (longer rows read the query from global memory)
+    if (qlds)
+        for (uint32_t cc = threadIdx.x; cc < ld; cc += 64 * W) ldq[cc] = qrow[cc];
+    __syncthreads();
+    const uint32_t base = blockIdx.x * 256u + 64u * w;
+    if (base >= a.m) return;  // (uniform over the wave; no barrier follows)
+    const uint32_t j = base + lane;
+    const bool inlist = j < a.m;
+    const uint64_t gid = inlist ? a.ids[(uint64_t)q * a.m + j] : ~0ull;
+    const bool inshard = inlist && gid >= a.offset && gid - a.offset < a.n;
+    const uint32_t myrow = inshard ? (uint32_t)(gid - a.offset) : 0u;
+    const bool present = row_live(a.dead, myrow, inshard);
+    const uint64_t pm = __ballot(present);
+    float d = INFINITY;
+    if (pm) {
+        float acc[1] = {-0.0f}, mx[1] = {0.0f};
+        wave_walk_rows(lds, a.rows, ld, a.dim, myrow, qlds ? ldq : qrow, lane, acc, mx);
+        const float dd = finish_distance(acc[0], mx[0], a.na[myrow], a.nb[q]);
+        if (present) d = dd;
+    }
+    if (a.dist && inlist) a.dist[(uint64_t)q * a.m + j] = d;
+    if (a.keys) {
+        const uint32_t slot = wave_claim(present, a.kcnt + q, lane);
+        if (present) a.keys[(uint64_t)q * a.m + slot] = dist_key(d, myrow);  // (slot < m: at most m lanes claim)
+    }
+    if (a.found && pm && lane == 0) atomicAdd(a.found + q, (uint32_t)__popcll(pm));
+}
+
+// One workgroup per query: its kcnt[q] <= m <= kScoreMaxIds keys through lds_sort_keys, a key equal
+// to its predecessor dropped (a repeated id gives the same key twice), and the first k of the rest
+// as result rows with (~0, +inf) behind them.  Thread t owns the sorted keys t*16 .. t*16 + 15; the
+// distinct keys before them come from a scan of the threads' counts in LDS.
+__global__ __launch_bounds__(256) void k_score_finish(const uint64_t* __restrict__ keys,
+                                                      const uint32_t* __restrict__ kcnt, uint32_t m, uint32_t k,
+                                                      uint64_t offset, uint64_t* __restrict__ out_idx,
+                                                      float* __restrict__ out_dist,
+                                                      uint32_t* __restrict__ out_count) {
+    constexpr uint32_t PER = kScoreMaxIds / 256;
+    __shared__ uint64_t sk[kScoreMaxIds];
+    __shared__ uint32_t s_pre[256];
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    const uint32_t c = kcnt[q] < m ? kcnt[q] : m;
+    if (c > 0) lds_sort_keys(sk, keys + (uint64_t)q * m, c, t);  // (uniform over the workgroup)
+    const uint32_t lo = t * PER, hi = lo + PER < c ? lo + PER : c;
+    uint32_t mine = 0;
+    for (uint32_t i = lo; i < hi; ++i) mine += i == 0 || sk[i] != sk[i - 1];
+    s_pre[t] = mine;
+    __syncthreads();
+    for (uint32_t s = 1; s < 256; s <<= 1) {  // (inclusive scan)
+        const uint32_t v = t >= s ? s_pre[t - s] : 0u;
+        __syncthreads();
+        s_pre[t] += v;
+        __syncthreads();
+    }
+    const uint32_t distinct = s_pre[255];
+    const uint32_t kept = distinct < k ? distinct : k;
+    uint64_t* const oi = out_idx + (uint64_t)q * k;
+    float* const od = out_dist + (uint64_t)q * k;
+    uint32_t pos = s_pre[t] - mine;
+    for (uint32_t i = lo; i < hi && pos < k; ++i) {
+        const uint64_t key = sk[i];
+        if (i == 0 || key != sk[i - 1]) {
+            oi[pos] = offset + key_row(key);
+            od[pos] = key_dist(key);
+            ++pos;
+        }
+    }
+    for (uint32_t i = kept + t; i < k; i += blockDim.x) {
+        oi[i] = ~0ull;
+        od[i] = INFINITY;
+    }
+    if (t == 0) out_count[q] = kept;
 }
 
 // ------------------------------------------------------------------------------------
@@ -2752,6 +2859,30 @@ hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint3
     if (!nq || !capacity || capacity > kRangeMaxResults || cap < capacity) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_range_finish, dim3(nq), dim3(256), 0, s, keys, rcnt, cap, capacity, offset, out_idx,
                        out_dist, out_count);
+    return hipGetLastError();
+}
+
+// ---- scoring caller-chosen rows --------------------------------------------------------------
+hipError_t launch_score_ids(const ScoreArgs& a, hipStream_t s) {
+    if (!a.nq || !a.m || a.ld == 0 || a.ld % 64 != 0 || a.dim > a.ld || (uint64_t)a.nq * a.m > 0xffffffffull ||
+        a.n > 0xffffffffull || (!a.dist && !a.keys) || (a.keys && !a.kcnt))
+        return hipErrorInvalidValue;
+    const uint32_t gx = (a.m + 255u) / 256u;
+    for (uint32_t q0 = 0; q0 < a.nq; q0 += 65535u) {  // (the grid's y extent is 16 bits)
+        ScoreArgs b = a;
+        b.q0 = q0;
+        const uint32_t gy = a.nq - q0 < 65535u ? a.nq - q0 : 65535u;
+        hipLaunchKernelGGL(k_score_ids, dim3(gx, gy), dim3(256), 0, s, b);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_score_finish(const uint64_t* keys, const uint32_t* kcnt, uint32_t m, uint32_t nq, uint32_t k,
+                               uint64_t offset, uint64_t* out_idx, float* out_dist, uint32_t* out_count,
+                               hipStream_t s) {
+    if (!nq || !k || k > m || m > kScoreMaxIds) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_score_finish, dim3(nq), dim3(256), 0, s, keys, kcnt, m, k, offset, out_idx, out_dist,
+                       out_count);
     return hipGetLastError();
 }
 

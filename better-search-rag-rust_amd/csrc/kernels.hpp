@@ -540,6 +540,39 @@ hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint3
                                uint32_t capacity, uint64_t offset, uint64_t* out_idx, float* out_dist,
                                uint32_t* out_count, hipStream_t s);
 
+// ---- scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids) -----
+// The longest list the rerank sorts (a list is sorted in LDS, as a range result is).
+constexpr uint32_t kScoreMaxIds = 4096;
+static_assert(kScoreMaxIds == kRangeMaxResults, "k_score_finish sorts with the range finish's network");
+// Per query q a list ids[q][0 .. m) of GLOBAL ids.  A slot is present when its id lies in [offset,
+// offset + n) and its row has no tombstone; no address is formed from an id outside that interval.
+struct ScoreArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t n, offset;         // rows of the shard, the shard's global offset
+    const float* na;            // row magnitudes (read, never recomputed)
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const uint64_t* dead;       // the bitset of deleted rows (nullable)
+    const uint64_t* ids;        // [nq][m]
+    uint32_t m, nq;
+    // the sinks, each nullable, at least one given:
+    float* dist;                // [nq][m]: the reference distance of a present slot, +inf otherwise
+    uint64_t* keys;             // [nq][m]: dist_key(d, row) of the present slots, in any order, in
+    uint32_t* kcnt;             //   the first kcnt[q] slots (zero before the launch; with keys)
+    uint32_t* found;            // [nq], nullable: += the present slots (zero before the launch)
+    uint32_t q0;                // (set by the launcher: the first query of a launch)
+};
+// Grid (ceil(m / 256), queries) x 256 threads, a wave per 64 consecutive slots, lane = slot: every
+// slot of dist is written, keys past kcnt[q] are untouched.
+hipError_t launch_score_ids(const ScoreArgs& a, hipStream_t s);
+// One workgroup per query: the kcnt[q] <= m <= kScoreMaxIds keys sorted ascending (distance, then
+// row), a key equal to its predecessor dropped, the first k as (offset + row, distance) in out_idx /
+// out_dist [nq][k] with (~0, +inf) behind them; out_count[q] = min(k, distinct keys).  1 <= k <= m.
+hipError_t launch_score_finish(const uint64_t* keys, const uint32_t* kcnt, uint32_t m, uint32_t nq, uint32_t k,
+                               uint64_t offset, uint64_t* out_idx, float* out_dist, uint32_t* out_count,
+                               hipStream_t s);
+
 // ---- masked range search (bsr_local_range_search_masked) ------------------------
 // The routing behind launch_range_tau: a query with to_list[q] != 0 (device, [nq]) is answered by
 // the list scan by design -- tau[q] = +inf, and q appended to scan_list (status[kStFail] and

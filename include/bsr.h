@@ -127,6 +127,7 @@ typedef struct {
 #define BSR_PATH_COLLAPSE_SCAN 16384u  /* ... and a query of the batch was answered by the group scan */
 #define BSR_PATH_CAP       32768u  /* bsr_local_top_k_capped ran (with the candidate search's bits) */
 #define BSR_PATH_CAP_SCAN  65536u  /* ... and a query of the batch was answered by the capped group scan */
+#define BSR_PATH_SCORE   131072u   /* bsr_local_score_ids / bsr_local_rerank_ids ran */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -566,6 +567,59 @@ int bsr_local_top_k_capped(bsr_index* ix, const float* queries, uint32_t n_queri
                            const uint32_t* query_mask, uint32_t mode,
                            uint64_t* out_idx, float* out_dist, uint32_t* out_group /* nullable */,
                            uint32_t* out_count);
+
+/* ---- score given ids: the distances of rows the caller already has ("BM25 gave me these 300
+ * chunk ids: how far is each from the query?", "re-check yesterday's answer", "rerank the list I
+ * assembled from several searches").  a-1 (bsr_cosine_distance) batched against STORED rows:
+ * ids[q][0 .. m) is query q's list of GLOBAL ids, as the searches return them.
+ * A slot is PRESENT when its id lies in [global_offset, global_offset + n) and its row is not
+ * deleted (bsr_index_delete).  Every other slot is ABSENT and never an error: the padding value ~0
+ * (ragged lists are padded with it), an id of another rank's shard, a deleted row.  So the
+ * multi-rank form needs no routing: every rank scores the same ids, and the element-wise fminf of
+ * the ranks' out_dist is the answer over the whole store -- an id is present on at most one rank.
+ * bsr_local_score_ids: out_dist[q][j] of a present slot is the reference's f32 distance of stored
+ *   row ids[q][j] to query q (src/metrics.rs:143-165: the sequential f32 dot in index order with no
+ *   FMA, the max|a-b| <= 1e-10 identical shortcut, a zero magnitude gives 1.0, the row's stored
+ *   magnitude), bit for bit what bsr_local_top_k returns for that row; of an absent slot +inf.
+ *   out_found[q] (nullable) = the present slots of row q.  An id may repeat: every slot gets its
+ *   value and counts.  m has no limit but n_queries * m < 2^32.
+ * bsr_local_rerank_ids: row q of out_idx / out_dist ([n_queries][k]) holds the DISTINCT present
+ *   ids of list q in (distance asc, global index asc) order, the first out_count[q] = min(k, distinct
+ *   present ids) of them, and (~0, +inf) behind them.  1 <= k <= m <= BSR_SCORE_MAX_IDS; k is not
+ *   bounded by cfg.max_k (the call owns its buffers).
+ * queries, ids and every output are, independently, host or device pointers, detected per call;
+ * device inputs follow the stream rule of device queries.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; m = 0; n_queries * m >= 2^32;
+ *      rerank only: k = 0, k > m or m > BSR_SCORE_MAX_IDS; with n_queries > 0 a null queries, ids
+ *      or mandatory output (out_found alone may be null);
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. n_queries = 0: BSR_OK;
+ *   4. BSR_E_NONFINITE: a non-finite query, read from the batch's status words before any of the
+ *      caller's arrays, host or device, is written.
+ * An empty shard: every slot absent, every count 0.  A bf16 index scores the widened stored values,
+ * as every search does.  BSR_FLAG_EXACT_ONLY and the sticky norm flags do not matter: no filter
+ * runs, and no filter operand of the queries is built.
+ * How: one kernel, a wave per 64 consecutive slots of a list, lane = slot -- the range search's
+ * rescore walk driven by the ids; no address is formed from an id that failed the interval check.
+ * The rerank adds one workgroup per query that sorts the present slots' keys in LDS, as a range
+ * result is sorted, and drops repeats.  Never graph-replayed; the plain search's graphs are left
+ * alone (the first call of a size allocates, and that makes the plain search re-capture once, as
+ * any allocation does).  bsr_search_stats: search_path = BSR_PATH_SCORE, n_queries,
+ * n_candidates = m, every other field 0.  BSR_FLAG_PROFILE: the kernels in rescore_ms /
+ * rescore_launches, the call in search_ms.
+ * Out of scope: one id list shared by the whole batch (bsr_local_top_k_masked with BSR_MASK_LIST);
+ * queries named by stored id; a collective that runs the fminf exchange itself; fused hybrid
+ * scoring (the caller fuses the two scores). */
+#define BSR_SCORE_MAX_IDS 4096u /* rerank only: the list is sorted in LDS, as a range result is */
+int bsr_local_score_ids(bsr_index* ix, const float* queries, uint32_t n_queries,
+                        const uint64_t* ids, uint32_t m,      /* [n_queries][m] GLOBAL ids */
+                        float* out_dist,                      /* [n_queries][m], aligned with ids */
+                        uint32_t* out_found /* [n_queries], nullable */);
+int bsr_local_rerank_ids(bsr_index* ix, const float* queries, uint32_t n_queries,
+                         const uint64_t* ids, uint32_t m, uint32_t k,
+                         uint64_t* out_idx, float* out_dist,  /* [n_queries][k] */
+                         uint32_t* out_count /* [n_queries] */);
 
 /* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists, on the host.  Layout and
  * null rules are bsr_global_top_k's, with group[(l*n_queries+q)*k_in ..] the group ids beside idx
