@@ -66,6 +66,9 @@ BSR_PATH_COLLAPSE_SCAN = 16384  # ... and a query of the batch was answered by t
 BSR_PATH_CAP = 32768            # bsr_local_top_k_capped ran (with the bits of the candidate search)
 BSR_PATH_CAP_SCAN = 65536       # ... and a query of the batch was answered by the capped group scan
 BSR_PATH_SCORE = 131072         # bsr_local_score_ids / bsr_local_rerank_ids ran
+BSR_PATH_GROUPS = 262144        # bsr_local_top_groups ran (with the bits of the candidate search)
+BSR_GROUPS_MAX_ROWS = 64        # the largest group_size of a group search (include/bsr.h)
+BSR_GROUPS_MAX_SLOTS = 4096     # ... and the largest k * group_size
 BSR_SCORE_MAX_IDS = 4096        # the longest id list bsr_local_rerank_ids orders (include/bsr.h)
 BSR_CAP_MAX_PER_GROUP = 16      # the largest per_group of a capped search (include/bsr.h)
 BSR_RANGE_MAX_RESULTS = 4096  # result slots per query of a range search (include/bsr.h)
@@ -160,6 +163,8 @@ def lib() -> ctypes.CDLL:
                                                      _P, _P]),
         "bsr_local_top_k_capped": (ctypes.c_int, [_P, _P, u32, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P,
                                                   _P, _P, _P]),
+        "bsr_local_top_groups": (ctypes.c_int, [_P, _P, u32, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P,
+                                                _P, _P, _P, _P]),
         "bsr_local_score_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P]),
         "bsr_local_rerank_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
@@ -187,7 +192,8 @@ def lib() -> ctypes.CDLL:
     optional = {"bsr_host_alloc", "bsr_host_free", "bsr_index_delete", "bsr_index_live_count",
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
-                "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids"}
+                "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids",
+                "bsr_local_top_groups"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -833,9 +839,25 @@ class Index:
         return self._group_search(per_group, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids,
                                   allow_masks, query_mask, mask_mode, return_groups)
 
+    def group_search(self, queries, k: int, row_group, group_size: int, n_groups=None, fetch_k=None,
+                     allow_mask=None, allow_ids=None, allow_masks=None, query_mask=None, mask_mode="auto"):
+        """The k best groups with up to group_size rows of each (bsr_local_top_groups) ->
+        (idx [Q,k,m] u64, dist [Q,k,m] f32, rows [Q,k] u32, group [Q,k] u32, count [Q] u32), m =
+        group_size (1 .. BSR_GROUPS_MAX_ROWS, k m <= BSR_GROUPS_MAX_SLOTS).  The groups are
+        collapsed_search's, in its order; slot g holds the first min(m, allowed live rows) rows of
+        result group g in (distance asc, index asc) order, then (~0, +inf); rows is that number,
+        group the group id (~0 past count).  Every other argument is collapsed_search's; the result
+        does not depend on fetch_k."""
+        group_size = int(group_size)
+        if group_size < 0 or group_size > 0xFFFFFFFF:
+            raise BsrError(-1, f"group_size={group_size} is no 32-bit count")
+        return self._group_search(None, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids, allow_masks,
+                                  query_mask, mask_mode, True, group_size)
+
     def _group_search(self, per_group, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids, allow_masks,
-                      query_mask, mask_mode, return_groups):
-        """collapsed_search (per_group None) and capped_search on host arrays."""
+                      query_mask, mask_mode, return_groups, group_size=None):
+        """collapsed_search (per_group None), capped_search and group_search (group_size) on host
+        arrays."""
         one = allow_mask is not None or allow_ids is not None
         if one and (allow_masks is not None or query_mask is not None):
             raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
@@ -852,8 +874,9 @@ class Index:
         if k < 1 or k > fk or fk > self.max_k:
             raise BsrError(-1, f"k={k}, fetch_k={fk} outside 1 <= k <= fetch_k <= max_k={self.max_k}")
         rg, n_rg, ng = self._row_groups(row_group, n_groups)
-        oi = np.empty((nq, k), np.uint64)
-        od = np.empty((nq, k), np.float32)
+        shape = (nq, k) if group_size is None else (nq, k, group_size)
+        oi = np.empty(shape, np.uint64)
+        od = np.empty(shape, np.float32)
         oc = np.empty(nq, np.uint32)
         og = np.empty((nq, k), np.uint32) if return_groups else None
         if not one and allow_masks is None:
@@ -869,6 +892,11 @@ class Index:
             wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
         tail = (_ptr(rg), n_rg, ng, wp, nw, n_masks, _ptr(qm), _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(og),
                 _ptr(oc))
+        if group_size is not None:
+            orows = np.empty((nq, k), np.uint32)
+            _check(lib().bsr_local_top_groups(self._h, _ptr(q), nq, k, group_size, fk, *tail[:-1], _ptr(orows),
+                                              tail[-1]))
+            return oi, od, orows, og, oc
         if per_group is None:
             _check(lib().bsr_local_top_k_collapsed(self._h, _ptr(q), nq, k, fk, *tail))
         else:
@@ -920,6 +948,17 @@ class Index:
         _check(lib().bsr_local_top_k_capped(self._h, _ptr(queries), nq, k, fetch_k, int(per_group),
                                             *self._group_device_tail(row_group, n_groups, out_idx, out_dist, out_count,
                                                                      out_group, allow_words, query_mask, mask_mode)))
+
+    def group_search_device(self, queries, nq: int, k: int, group_size: int, fetch_k: int, row_group, n_groups: int,
+                            out_idx, out_dist, out_count, out_group=None, out_rows=None, allow_words=None,
+                            query_mask=None, mask_mode="auto"):
+        """Zero-copy variant of group_search on caller buffers: collapsed_search_device's arguments
+        with group_size behind k, out_idx / out_dist [nq][k][group_size] and out_rows (optional)
+        [nq][k]."""
+        tail = self._group_device_tail(row_group, n_groups, out_idx, out_dist, out_count, out_group, allow_words,
+                                       query_mask, mask_mode)
+        _check(lib().bsr_local_top_groups(self._h, _ptr(queries), nq, k, int(group_size), fetch_k, *tail[:-1],
+                                          _ptr(out_rows), tail[-1]))
 
     @staticmethod
     def _group_device_tail(row_group, n_groups, out_idx, out_dist, out_count, out_group, allow_words, query_mask,

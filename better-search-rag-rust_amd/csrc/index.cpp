@@ -2877,6 +2877,148 @@ int bsr_local_top_k_capped_impl(bsr_index* ix, const float* queries, uint32_t nq
     return BSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Group search (bsr_local_top_groups): the collapsed search names every query's k
+// groups, the inverted list of row_group gives their rows, the fill keeps the m best of each.
+// ---------------------------------------------------------------------------------------
+static_assert(kGroupsMaxRows == BSR_GROUPS_MAX_ROWS && kGroupsMaxSlots == BSR_GROUPS_MAX_SLOTS,
+              "the fill's limits are the ABI's");
+
+int bsr_index::top_groups_device(const float* queries, uint32_t nq, uint32_t k, uint32_t group_size, uint32_t fetch_k,
+                                 const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow,
+                                 uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
+                                 uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_rows,
+                                 uint32_t* out_count) {
+    const uint32_t m = group_size;
+    BSR_HIP(hipSetDevice(device));
+    // Every buffer of the stage before the candidate search (an allocation after it would fall between
+    // the capture of its graph and the replay, as group_search_device has it) -- the split table too,
+    // for nq split queries: once the fill writes to the caller's arrays no allocation is left to fail.
+    const size_t nk = (size_t)nq * k, nkm = nk * m;
+    const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count) &&
+                         (!out_group || is_device_ptr(out_group)) && (!out_rows || is_device_ptr(out_rows));
+    BSR_TRY(tg_gcnt.ensure((size_t)n_groups * sizeof(uint32_t)));
+    BSR_TRY(tg_gpos.ensure((size_t)n_groups * sizeof(uint32_t)));
+    BSR_TRY(tg_list.ensure((size_t)n * sizeof(uint32_t)));
+    BSR_TRY(tg_info.ensure(3 * sizeof(uint32_t)));
+    BSR_TRY(tg_split.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_TRY(tg_table.ensure(nkm * sizeof(uint64_t)));
+    BSR_TRY(tg_hidx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(tg_hdist.ensure(nk * sizeof(float)));
+    BSR_TRY(tg_hgroup.ensure(nk * sizeof(uint32_t)));
+    BSR_TRY(tg_hcnt.ensure((size_t)nq * sizeof(uint32_t)));
+    if (!out_dev) {
+        BSR_TRY(tg_idx.ensure(nkm * sizeof(uint64_t)));
+        BSR_TRY(tg_dist.ensure(nkm * sizeof(float)));
+        BSR_TRY(tg_rows.ensure(nk * sizeof(uint32_t)));
+        BSR_TRY(tg_group.ensure(nk * sizeof(uint32_t)));
+        BSR_TRY(tg_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    }
+    // 1. The groups: the collapsed search, unchanged, into the index's own arrays (it checks
+    // row_group, runs the candidate search, walks, scans where the walk cannot certify, and waits).
+    BSR_TRY(group_search_device(queries, nq, k, fetch_k, 0, row_group, n_groups, allow, allow_words, n_masks,
+                                query_mask, mode, tg_hidx.as<uint64_t>(), tg_hdist.as<float>(),
+                                tg_hgroup.as<uint32_t>(), tg_hcnt.as<uint32_t>()));
+    stats.search_path = (stats.search_path & ~BSR_PATH_COLLAPSE) | BSR_PATH_GROUPS;
+    // 2. The inverted list of the caller's row_group, where the collapsed search left it on the device.
+    const uint32_t* const dgrp = is_device_ptr(row_group) ? row_group : col_grp.as<uint32_t>();
+    uint32_t* const info = tg_info.as<uint32_t>();
+    BSR_HIP(hipMemsetAsync(info, 0, 3 * sizeof(uint32_t), stream));
+    if (n) {
+        BSR_HIP(hipMemsetAsync(tg_gcnt.p, 0, (size_t)n_groups * sizeof(uint32_t), stream));
+        BSR_HIP(launch_groups_invert(dgrp, n, n_groups, tg_gcnt.as<uint32_t>(), tg_gpos.as<uint32_t>(), info,
+                                     tg_list.as<uint32_t>(), stream));
+    }
+    // 3. The fill, straight into the caller's arrays when they are all on the device.
+    GroupsFillArgs fa{};
+    fa.rows = rows.as<float>();
+    fa.ld = ld;
+    fa.dim = dim;
+    fa.offset = global_offset;
+    fa.na = na.as<float>();
+    fa.qf32 = qf32.as<float>();
+    fa.nb = nb.as<float>();
+    fa.dead = dead_bits();
+    // (the masks where the candidate search read them: the caller's device arrays or its copies)
+    fa.allow = !allow ? nullptr : is_device_ptr(allow) ? allow : mask_dev.as<uint64_t>();
+    fa.allow_words = allow_words;
+    fa.query_mask = !allow || !query_mask ? nullptr
+                    : is_device_ptr(query_mask) ? query_mask : grp_qmask.as<uint32_t>();
+    fa.gcnt = tg_gcnt.as<uint32_t>();
+    fa.gpos = tg_gpos.as<uint32_t>();
+    fa.glist = tg_list.as<uint32_t>();
+    fa.head_group = tg_hgroup.as<uint32_t>();
+    fa.head_cnt = tg_hcnt.as<uint32_t>();
+    fa.nq = nq;
+    fa.k = k;
+    fa.m = m;
+    fa.split_items = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, env_bytes("BSR_GROUPS_SPLIT_ITEMS", 64)),
+                                                  0xFFFFFFFFull);
+    fa.split = tg_split.as<uint32_t>();
+    fa.split_info = info + 1;
+    fa.out_idx = out_dev ? out_idx : tg_idx.as<uint64_t>();
+    fa.out_dist = out_dev ? out_dist : tg_dist.as<float>();
+    fa.out_rows = out_dev ? out_rows : tg_rows.as<uint32_t>();
+    fa.out_group = out_dev ? out_group : tg_group.as<uint32_t>();
+    fa.out_count = out_dev ? out_count : tg_cnt.as<uint32_t>();
+    BSR_HIP(launch_groups_fill(fa, stream));
+    uint32_t split[2] = {0, 0};  // the queries left to the split launches; their largest item count
+    BSR_HIP(hipMemcpyAsync(split, info + 1, sizeof split, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (split[0]) {
+        const size_t table = (size_t)split[0] * k * m * sizeof(uint64_t);  // (split[0] <= nq rows of tg_table)
+        fa.table = tg_table.as<uint64_t>();
+        BSR_HIP(hipMemsetAsync(tg_table.p, 0xff, table, stream));
+        const uint32_t parts = std::min<uint32_t>((split[1] + fa.split_items - 1) / fa.split_items, 1024u);
+        BSR_HIP(launch_groups_fill_split(fa, split[0], parts, stream));
+        BSR_HIP(launch_groups_finish(fa, split[0], stream));
+    }
+    if (!out_dev) {
+        BSR_HIP(hipMemcpyAsync(out_idx, fa.out_idx, nkm * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, fa.out_dist, nkm * sizeof(float), hipMemcpyDefault, stream));
+        if (out_rows) BSR_HIP(hipMemcpyAsync(out_rows, fa.out_rows, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        if (out_group) BSR_HIP(hipMemcpyAsync(out_group, fa.out_group, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, fa.out_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_groups_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t group_size,
+                              uint32_t fetch_k, const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                              const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                              const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                              uint32_t* out_group, uint32_t* out_rows, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (group_size == 0 || group_size > BSR_GROUPS_MAX_ROWS)
+        return set_error(BSR_E_INVALID, "group_size=%u outside 1 <= group_size <= %u", group_size, BSR_GROUPS_MAX_ROWS);
+    if ((uint64_t)k * group_size > BSR_GROUPS_MAX_SLOTS)
+        return set_error(BSR_E_INVALID, "k * group_size = %u * %u exceeds %u", k, group_size, BSR_GROUPS_MAX_SLOTS);
+    if (k == 0 || k > fetch_k || fetch_k > ix->cfg.max_k)
+        return set_error(BSR_E_INVALID, "k=%u, fetch_k=%u outside 1 <= k <= fetch_k <= max_k=%u", k, fetch_k,
+                         ix->cfg.max_k);
+    if (n_groups == 0) return set_error(BSR_E_INVALID, "n_groups = 0");
+    if (!allow && (n_masks != 0 || query_mask))
+        return set_error(BSR_E_INVALID, "n_masks = %u or a query_mask without allow masks", n_masks);
+    if (allow && n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 with allow masks");
+    if (allow && !query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (row_group_len != ix->n)
+        return set_error(BSR_E_INVALID, "row_group_len=%llu, the index holds %llu rows", (unsigned long long)row_group_len,
+                         (unsigned long long)ix->n);
+    if (ix->n && !row_group) return set_error(BSR_E_INVALID, "null row_group");
+    if (nq == 0) return BSR_OK;
+    BSR_TRY(ix->top_groups_device(queries, nq, k, group_size, fetch_k, row_group, n_groups, allow, allow_words, n_masks,
+                                  query_mask, mode, out_idx, out_dist, out_group, out_rows, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
 int bsr_index_collect_profile_impl(bsr_index* ix) {
     collect_profile(ix);
     return BSR_OK;

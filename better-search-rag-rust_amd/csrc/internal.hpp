@@ -307,6 +307,25 @@ struct bsr_index {
     bsr::DevBuf col_best;   // u64 [queries of a round][n_groups][entries per group]: the scan's tables
     bsr::DevBuf col_idx, col_dist, col_group, col_cnt;  // the result rows [nq][k], the counts [nq]
 
+    // Group search (bsr_local_top_groups): the collapsed search above into buffers of
+    // the index (the heads and their groups), the inverted list of row_group built for the call, the
+    // fill over the rows of every query's result groups, and for the queries with more items than
+    // BSR_GROUPS_SPLIT_ITEMS (read per call) the split fill into a global table and its finish.  All
+    // launched directly, never captured.  Every buffer, the split table at its largest ([nq][k][m])
+    // included, is sized before the candidate search: nothing can fail for want of memory once the
+    // fill has written to the caller's arrays.
+    int top_groups_device(const float* queries, uint32_t nq, uint32_t k, uint32_t group_size, uint32_t fetch_k,
+                          const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow, uint64_t allow_words,
+                          uint32_t n_masks, const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx,
+                          float* out_dist, uint32_t* out_group, uint32_t* out_rows, uint32_t* out_count);
+    bsr::DevBuf tg_gcnt, tg_gpos;  // u32 [n_groups]: the rows of a group; its range's end in tg_list
+    bsr::DevBuf tg_list;           // u32 [n]: the local rows, group by group
+    bsr::DevBuf tg_info;           // u32 [3]: the offsets' cursor; the split queries; their largest item count
+    bsr::DevBuf tg_split;          // u32 [nq]: the queries the split launches answer
+    bsr::DevBuf tg_table;          // u64 [split queries][k][m]: their tables (sized for nq of them)
+    bsr::DevBuf tg_hidx, tg_hdist, tg_hgroup, tg_hcnt;       // the collapsed search's result [nq][k], [nq]
+    bsr::DevBuf tg_idx, tg_dist, tg_rows, tg_group, tg_cnt;  // the result [nq][k][m], [nq][k], [nq]
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

@@ -1,5 +1,5 @@
 // kernels.hpp -- host-side launchers for the gfx950 kernels (k_prep.hip, k_filter.hip,
-// k_exact.hip).
+// k_exact.hip, k_groups.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -729,6 +729,63 @@ struct CapScanArgs {
     uint32_t m;
 };
 hipError_t launch_cap_scan(const CapScanArgs& a, uint32_t grid, hipStream_t s);
+
+// ---- group search (bsr_local_top_groups; k_groups.hip) --------------------------
+// The inverted list of row_group[0 .. n) (every entry < n_groups, launch_group_check), three launches:
+// the histogram gcnt[g] = the rows of group g (gcnt zero before it); the offsets -- every group gets a
+// range of gcnt[g] slots of glist, the ranges disjoint and covering [0, n), in no particular order
+// (a prefix sum inside each wave, one atomic add on *cursor, zero before, per wave), gpos[g] = its
+// first slot; the scatter -- row i takes slot gpos[g]++ of its group.  Afterwards the local rows of
+// group g are glist[gpos[g] - gcnt[g] .. gpos[g]), in any order.
+hipError_t launch_groups_invert(const uint32_t* row_group, uint64_t n, uint32_t n_groups, uint32_t* gcnt,
+                                uint32_t* gpos, uint32_t* cursor, uint32_t* glist, hipStream_t s);
+// The fill: for query q the result groups are head_group[q][0 .. head_cnt[q]) (the collapsed
+// search's out_group and out_count).  The concatenation of their row lists is cut into items of 64
+// positions, lane = row; a workgroup of four waves per query deals the items from an LDS counter, each
+// an exact walk of its rows against the query (the arithmetic of launch_score_ids).  A row that is
+// live (dead, nullable) and allowed (allow / query_mask as CollapseScanArgs has them) offers its key
+// to the m entries of its group; the m smallest of every group, ascending, are slots [g][0 .. m) of
+// row q of out_idx / out_dist [nq][k][m] as (offset + row, distance), then (~0, +inf); out_rows[q][g]
+// (nullable) their number, out_group[q][g] (nullable) the group or ~0u, out_count[q] = head_cnt[q].
+// 1 <= k <= 256, 1 <= m <= kGroupsMaxRows, k * m <= kGroupsMaxSlots.
+// A query with more than split_items items is not answered: it is appended to split[] (any order),
+// split_info[0] (zero before the launch) counts them and split_info[1] takes the largest item count.
+// launch_groups_fill_split answers those: workgroup (j, y) of grid (n_split, parts) takes the y-th
+// share of the items of query split[j] and offers into row j of table [n_split][k][m] (u64, all-ones
+// before the launch); launch_groups_finish then sorts row j of the table for every j < n_split and
+// writes the outputs of query split[j] as above.
+constexpr uint32_t kGroupsMaxRows = 64;     // BSR_GROUPS_MAX_ROWS
+constexpr uint32_t kGroupsMaxSlots = 4096;  // BSR_GROUPS_MAX_SLOTS
+struct GroupsFillArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t offset;            // the global id of row 0
+    const float* na;            // row magnitudes (read, never recomputed)
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const uint64_t* dead;       // the bitset of deleted rows (nullable)
+    const uint64_t* allow;      // [n_masks][allow_words] (nullable)
+    uint64_t allow_words;
+    const uint32_t* query_mask; // [nq] (nullable: mask 0)
+    const uint32_t* gcnt;       // [n_groups]: launch_groups_invert's
+    const uint32_t* gpos;       // [n_groups]
+    const uint32_t* glist;      // [n]
+    const uint32_t* head_group; // [nq][k]
+    const uint32_t* head_cnt;   // [nq]
+    uint32_t nq, k, m;
+    uint32_t split_items;
+    uint32_t* split;            // [nq]
+    uint32_t* split_info;       // [2]
+    uint64_t* table;            // [n_split][k][m], row j for query split[j] (the split launches)
+    uint64_t* out_idx;          // [nq][k][m]
+    float* out_dist;            // [nq][k][m]
+    uint32_t* out_rows;         // [nq][k], nullable
+    uint32_t* out_group;        // [nq][k], nullable
+    uint32_t* out_count;        // [nq]
+};
+hipError_t launch_groups_fill(const GroupsFillArgs& a, hipStream_t s);
+hipError_t launch_groups_fill_split(const GroupsFillArgs& a, uint32_t n_split, uint32_t parts, hipStream_t s);
+hipError_t launch_groups_finish(const GroupsFillArgs& a, uint32_t n_split, hipStream_t s);
 
 uint32_t scan_grid_for(uint64_t n);
 

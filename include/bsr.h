@@ -128,6 +128,7 @@ typedef struct {
 #define BSR_PATH_CAP       32768u  /* bsr_local_top_k_capped ran (with the candidate search's bits) */
 #define BSR_PATH_CAP_SCAN  65536u  /* ... and a query of the batch was answered by the capped group scan */
 #define BSR_PATH_SCORE   131072u   /* bsr_local_score_ids / bsr_local_rerank_ids ran */
+#define BSR_PATH_GROUPS  262144u   /* bsr_local_top_groups ran (with the candidate search's bits) */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -557,7 +558,8 @@ int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_qu
  * fetch_k) would replay.
  * A multi-rank capped search: this call on every rank with its own row_group (global group ids)
  * and out_group, bsr_allgather_bytes of the four outputs, bsr_global_top_k_capped.
- * Out of scope: "k groups with up to m rows each"; a per-query per_group; group ids stored on the
+ * "k groups with up to m rows each" is bsr_local_top_groups, below.
+ * Out of scope: a per-query per_group; group ids stored on the
  * index; a list-driven scan for sparse masks; counts per group in the output. */
 #define BSR_CAP_MAX_PER_GROUP 16u
 int bsr_local_top_k_capped(bsr_index* ix, const float* queries, uint32_t n_queries,
@@ -567,6 +569,63 @@ int bsr_local_top_k_capped(bsr_index* ix, const float* queries, uint32_t n_queri
                            const uint32_t* query_mask, uint32_t mode,
                            uint64_t* out_idx, float* out_dist, uint32_t* out_group /* nullable */,
                            uint32_t* out_count);
+
+/* ---- Group search: the k best groups with up to group_size rows of each ("ten documents, three
+ * passages of each"), exactly and in one call.  row_group, row_group_len, n_groups,
+ * the masks, mode and fetch_k are taken exactly as bsr_local_top_k_collapsed takes them: per call,
+ * host or device, never stored on the index.  For one query, over the rows that are live and
+ * allowed by its mask, with m = group_size:
+ *   1. order the rows by (reference distance asc, global index asc);
+ *   2. a group's head is its first row in that order, and the result groups are the k groups whose
+ *      heads come first -- bsr_local_top_k_collapsed's rule;
+ *   3. slot g of row q of out_idx / out_dist [n_queries][k][m] holds the first min(m, allowed live
+ *      rows of the group) rows of result group g in that order as (global index, the reference's f32
+ *      distance bits), then (~0, +inf); out_rows[q][g] (nullable) is that number and out_group[q][g]
+ *      (nullable) the group id; a group slot past the count holds (~0u, 0 rows, every slot padded);
+ *   4. out_count[q] = min(k, distinct groups among the allowed live rows).
+ * group_size = 1 is bsr_local_top_k_collapsed byte for byte; slot [g][0] is the collapsed head for
+ * every group_size; row_group[i] = i gives bsr_local_top_k(k) in the [g][0] slots with out_rows = 1;
+ * the result is the same for every legal fetch_k.
+ * The groups come from the collapsed search (its walk over the candidate list of length fetch_k, its
+ * group scan for the queries the walk cannot certify).  Their rows come from an inverted list of
+ * row_group that the call builds on the device (4 * (2 * n_groups + n) bytes, kept on the index,
+ * rebuilt by every call), so the cost of the rest follows the sizes of the k result groups, not the
+ * shard.  A query whose result groups hold more than 64 * BSR_GROUPS_SPLIT_ITEMS rows (read from the
+ * environment per call, 64 by default) is dealt over several workgroups through a table of 8 * k *
+ * group_size bytes per query.  The call's device footprint besides the candidate search's: the list
+ * above; 8 * n_queries * k * group_size bytes for that table, held for every query of the batch
+ * whether one splits or not (a second out_idx); the collapsed search's own buffers and 16 *
+ * n_queries * k bytes for the heads it returns; and, when an output is host memory, the five
+ * outputs once more.  All of it is kept on the index and
+ * grows with the largest call.  Every buffer is allocated before the candidate search, so nothing can
+ * fail for want of memory once a result is written; the first call of a shape allocates, and like
+ * the first update of its size that makes the plain search re-capture its graph once.
+ * 1 <= k <= fetch_k <= cfg.max_k; 1 <= group_size <= BSR_GROUPS_MAX_ROWS; k * group_size <=
+ * BSR_GROUPS_MAX_SLOTS; n_groups >= 1.  queries, row_group, the masks and the five outputs are,
+ * independently, host or device pointers.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; group_size = 0 or above
+ *      BSR_GROUPS_MAX_ROWS; k * group_size above BSR_GROUPS_MAX_SLOTS; then
+ *      bsr_local_top_k_collapsed's first check, word for word;
+ *   2. to 6.: bsr_local_top_k_collapsed's, word for word.
+ * An empty shard gives every count 0.
+ * bsr_search_stats: search_path carries the candidate search's bits plus BSR_PATH_GROUPS (never
+ * BSR_PATH_COLLAPSE), and BSR_PATH_COLLAPSE_SCAN when a query of the batch needed the group scan to
+ * find its groups; the other fields are the candidate search's, and graph_replay is 1 wherever
+ * bsr_local_top_k(n_queries, fetch_k) would replay.
+ * Out of scope: a multi-rank merge of group results; group ids or the inverted list stored on the
+ * index; a per-query group_size; group sizes beyond the returned rows. */
+#define BSR_GROUPS_MAX_ROWS   64u    /* group_size */
+#define BSR_GROUPS_MAX_SLOTS  4096u  /* k * group_size */
+int bsr_local_top_groups(bsr_index* ix, const float* queries, uint32_t n_queries,
+                         uint32_t k, uint32_t group_size, uint32_t fetch_k,
+                         const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                         const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                         const uint32_t* query_mask, uint32_t mode,
+                         uint64_t* out_idx, float* out_dist,   /* [n_queries][k][group_size] */
+                         uint32_t* out_group,                  /* [n_queries][k], nullable */
+                         uint32_t* out_rows,                   /* [n_queries][k], nullable */
+                         uint32_t* out_count);                 /* [n_queries] */
 
 /* ---- score given ids: the distances of rows the caller already has ("BM25 gave me these 300
  * chunk ids: how far is each from the query?", "re-check yesterday's answer", "rerank the list I
