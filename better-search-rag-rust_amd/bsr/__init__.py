@@ -67,6 +67,9 @@ BSR_PATH_CAP = 32768            # bsr_local_top_k_capped ran (with the bits of t
 BSR_PATH_CAP_SCAN = 65536       # ... and a query of the batch was answered by the capped group scan
 BSR_PATH_SCORE = 131072         # bsr_local_score_ids / bsr_local_rerank_ids ran
 BSR_PATH_GROUPS = 262144        # bsr_local_top_groups ran (with the bits of the candidate search)
+BSR_PATH_DEEP = 524288          # bsr_local_top_k_deep ran
+BSR_PATH_DEEP_SCAN = 1048576    # ... and a query of the batch was answered by the deep exact scan
+BSR_DEEP_MAX_K = 1024           # the largest k of bsr_local_top_k_deep (include/bsr.h)
 BSR_GROUPS_MAX_ROWS = 64        # the largest group_size of a group search (include/bsr.h)
 BSR_GROUPS_MAX_SLOTS = 4096     # ... and the largest k * group_size
 BSR_SCORE_MAX_IDS = 4096        # the longest id list bsr_local_rerank_ids orders (include/bsr.h)
@@ -167,6 +170,7 @@ def lib() -> ctypes.CDLL:
                                                 _P, _P, _P, _P]),
         "bsr_local_score_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P]),
         "bsr_local_rerank_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, u32, _P, _P, _P]),
+        "bsr_local_top_k_deep": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_global_top_k_capped": (ctypes.c_int, [_P, _P, _P, _P, u32, u32, u32, u32, u32, _P, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
@@ -193,7 +197,7 @@ def lib() -> ctypes.CDLL:
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
                 "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids",
-                "bsr_local_top_groups"}
+                "bsr_local_top_groups", "bsr_local_top_k_deep"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -580,6 +584,29 @@ class Index:
         nw = int(allow_words.numel()) if hasattr(allow_words, "numel") else int(allow_words.size)
         _check(lib().bsr_local_top_k_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), nw,
                                             _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_count)))
+
+    def deep_search(self, queries, k: int):
+        """Exact top-k for k up to BSR_DEEP_MAX_K (bsr_local_top_k_deep), not bounded by max_k ->
+        (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32), local_top_k's triple."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
+        nq, k = q.shape[0], int(k)
+        if k < 1 or k > BSR_DEEP_MAX_K:
+            raise BsrError(-1, f"k={k} outside [1, {BSR_DEEP_MAX_K}]")
+        oi = np.empty((nq, k), np.uint64)
+        od = np.empty((nq, k), np.float32)
+        oc = np.empty(nq, np.uint32)
+        _check(lib().bsr_local_top_k_deep(self._h, _ptr(q), nq, k, _ptr(oi), _ptr(od), _ptr(oc)))
+        return oi, od, oc
+
+    def deep_search_device(self, queries, nq: int, k: int, out_idx, out_dist, out_count):
+        """Zero-copy variant on caller buffers (torch tensors, numpy arrays or raw pointers, each
+        host or device): queries [nq][dim] f32, out_idx / out_dist [nq][k], out_count [nq]."""
+        _check(lib().bsr_local_top_k_deep(self._h, _ptr(queries), nq, k, _ptr(out_idx), _ptr(out_dist),
+                                          _ptr(out_count)))
 
     def range_search(self, queries, radius, max_results: int = 256, allow_mask=None, allow_ids=None,
                      allow_masks=None, query_mask=None, mask_mode="auto"):

@@ -2171,6 +2171,194 @@ int bsr_local_range_search_impl(bsr_index* ix, const float* queries, uint32_t nq
 }
 
 // ---------------------------------------------------------------------------------------
+// Deep search (bsr_local_top_k_deep)
+// ---------------------------------------------------------------------------------------
+// The deep exact scan of n_ids queries (device id list, rounds of kDeepScanQF ids every id_stride
+// entries, the last round padded with valid ids), run_range_scan's rounds: the scan into the
+// per-block lists, then their selection into the result rows of the round's queries.
+static_assert(kDeepMaxK == BSR_DEEP_MAX_K, "the deep kernels' limit is the ABI's");
+static int run_deep_scan(bsr_index* ix, const int32_t* ids, uint32_t id_stride, uint32_t n_ids, uint32_t k,
+                         uint64_t* out_idx, float* out_dist, uint32_t* out_count) {
+    const uint32_t grid = scan_grid_for(ix->n);
+    BSR_TRY(ix->deep_part.ensure((size_t)kDeepScanQF * grid * k * sizeof(uint64_t)));
+    DeepScanArgs sa{};
+    sa.rows = ix->rows.as<float>();
+    sa.ld = ix->ld;
+    sa.dim = ix->dim;
+    sa.n = ix->n;
+    sa.na = ix->na.as<float>();
+    sa.qf32 = ix->qf32.as<float>();
+    sa.nb = ix->nb.as<float>();
+    sa.dead = ix->dead_bits();
+    sa.k = k;
+    sa.part = ix->deep_part.as<uint64_t>();
+    DeepSelectArgs se{};
+    se.keys = sa.part;
+    se.stride = (uint64_t)grid * k;
+    se.n_keys = grid * k;
+    se.k = k;
+    se.offset = ix->global_offset;
+    se.out_idx = out_idx;
+    se.out_dist = out_dist;
+    se.out_count = out_count;
+    ev_begin(ix, ix->ev_scan, 1);
+    for (uint32_t g = 0; g * kDeepScanQF < n_ids; ++g) {
+        sa.qids = se.qids = ids + (size_t)g * id_stride;
+        sa.nqf = se.n_items = std::min(kDeepScanQF, n_ids - g * kDeepScanQF);
+        BSR_HIP(launch_deep_scan(sa, grid, ix->stream));
+        BSR_HIP(launch_deep_select(se, ix->stream));
+    }
+    ev_end(ix, ix->ev_scan);
+    return BSR_OK;
+}
+
+int bsr_index::deep_search_device(const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist,
+                                  uint32_t* out_count) {
+    bsr_index* ix = this;
+    BSR_TRY(check_batch(ix, 1));  // (loaded; k has its own bound, checked by the entry point)
+    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_DEEP));
+    if (nq == 0) return BSR_OK;
+
+    const uint32_t ks = deep_ks(k), cap = deep_cap(k);
+    const uint32_t qpad = qpad_for(nq);
+    const size_t nk = (size_t)nq * k;
+    BSR_TRY(query_buffers(ix, nq, qpad, 1));
+    BSR_TRY(deep_idx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(deep_dist.ensure(nk * sizeof(float)));
+    BSR_TRY(deep_ocnt.ensure((size_t)nq * sizeof(uint32_t)));
+    uint64_t* const di = deep_idx.as<uint64_t>();
+    float* const dd = deep_dist.as<float>();
+    uint32_t* const dc = deep_ocnt.as<uint32_t>();
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
+    // The filter rung needs an int8 operand worth a threshold (BSR_FLAG_EXACT_ONLY, sticky norm
+    // flags) and more live rows than one emitted list holds; else every query is scanned.
+    const uint64_t live = live_rows();
+    const bool use_filter = approx_ok && live > cap;
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, use_filter), stream));
+    if (use_filter) {
+        BSR_TRY(deep_keys.ensure((size_t)nq * cap * sizeof(uint64_t)));
+        BSR_TRY(deep_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+        BSR_TRY(deep_rad.ensure((size_t)nq * sizeof(float)));
+        // tau0 = the ks-th best sampled score, the emit pass over lists of cap keys (with the sample
+        // tiles' fix-up), then the reference distance of every emitted live row: a radius of +inf
+        BSR_TRY(sample_pass(ix, nq, qpad, k, nullptr, ks, cap));
+        BSR_TRY(emit_pass(ix, nq, qpad, k, cap));
+        BSR_HIP(hipMemsetAsync(deep_cnt.p, 0, (size_t)nq * sizeof(uint32_t), stream));
+        BSR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(deep_rad.p), 0x7f800000, nq, stream));
+        RangeArgs ra{};
+        ra.rows = rows.as<float>();
+        ra.ld = ld;
+        ra.dim = dim;
+        ra.n = n;
+        ra.na = na.as<float>();
+        ra.qf32 = qf32.as<float>();
+        ra.nb = nb.as<float>();
+        ra.radius = deep_rad.as<float>();
+        ra.dead = dead_bits();
+        ra.keys = deep_keys.as<uint64_t>();
+        ra.rcnt = deep_cnt.as<uint32_t>();
+        ra.cap = cap;
+        ra.nq = nq;
+        ra.cand = cand.as<uint64_t>();
+        ra.cnt = cnt.as<uint32_t>();
+        ra.scan_list = fail.as<uint32_t>();
+        ra.status = d_status;
+        ev_begin(ix, ev_rescore);
+        BSR_HIP(launch_range_rescore(ra, stream));
+        // (the rescore listed the overflowed queries; the selection lists every query it does not
+        // certify, those included: its list starts empty)
+        BSR_HIP(hipMemsetAsync(d_status + kStFail, 0, sizeof(uint32_t), stream));
+        DeepSelectArgs se{};
+        se.keys = ra.keys;
+        se.stride = cap;
+        se.kcnt = ra.rcnt;
+        se.n_keys = cap;
+        se.n_items = nq;
+        se.k = k;
+        se.offset = global_offset;
+        se.out_idx = di;
+        se.out_dist = dd;
+        se.out_count = dc;
+        se.tau = tau.as<float>();
+        se.ebound = ebound.as<float>();
+        se.nb = nb.as<float>();
+        se.emit_cnt = ra.cnt;
+        se.cap = cap;
+        se.fail = fail.as<uint32_t>();
+        se.status = d_status;
+        BSR_HIP(launch_deep_select(se, stream));
+        ev_end(ix, ev_rescore);
+    } else if (live > 0) {
+        stats.n_exact_direct = nq;
+        stats.search_path |= BSR_PATH_DEEP_SCAN;
+        BSR_TRY(run_deep_scan(ix, qids_id.as<int32_t>(), kDeepScanQF, nq, k, di, dd, dc));
+    } else {
+        // an empty shard, or one whose every row is deleted: no key, every row padding, every count 0
+        DeepSelectArgs se{};
+        se.keys = di;  // (never read: n_keys = 0)
+        se.n_items = nq;
+        se.k = k;
+        se.out_idx = di;
+        se.out_dist = dd;
+        se.out_count = dc;
+        BSR_HIP(launch_deep_select(se, stream));
+    }
+    stats.n_candidates = cap;
+    // The one status readback: the query flags and the number of queries left to the scan.
+    BSR_HIP(hipMemcpyAsync(h_res, d_status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BSR_HIP(stream_wait(stream));
+    BSR_TRY(check_queries(ix, nq));
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+    if (use_filter) {
+        stats.n_emitted = st[kStEmitted];
+        const uint32_t nscan = st[kStFail];
+        if (nscan) {
+            // queries the filter cannot serve (by design), and queries it left uncertified
+            stats.search_path |= BSR_PATH_DEEP_SCAN;
+            h_fail.resize(nscan);
+            h_qflags.resize(nq);
+            h_deep_eb.resize(nq);
+            BSR_HIP(hipMemcpy(h_fail.data(), fail.p, (size_t)nscan * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            BSR_HIP(hipMemcpy(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            BSR_HIP(hipMemcpy(h_deep_eb.data(), ebound.p, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+            std::sort(h_fail.begin(), h_fail.end());
+            for (uint32_t q : h_fail) {
+                if ((h_qflags[q] & kQueryNoApprox) || !(h_deep_eb[q] < 1.0f)) ++stats.n_exact_direct;
+                else ++stats.n_fallback;
+            }
+            const std::vector<int32_t> padded = padded_scan_ids(h_fail, nscan, kDeepScanQF);
+            BSR_TRY(qids.ensure(padded.size() * sizeof(int32_t)));
+            BSR_HIP(hipMemcpyAsync(qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   stream));
+            BSR_HIP(hipStreamSynchronize(stream));  // (padded is read by the copy)
+            BSR_TRY(run_deep_scan(ix, qids.as<int32_t>(), kScanQF, nscan, k, di, dd, dc));
+        }
+    }
+    ev_end(ix, ev_total);
+    // Every row was written to the index's own buffers -- the status is read before any of the
+    // caller's arrays, host or device, is written -- and goes out with one copy each.
+    BSR_HIP(hipMemcpyAsync(out_idx, di, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+    BSR_HIP(hipMemcpyAsync(out_dist, dd, nk * sizeof(float), hipMemcpyDefault, stream));
+    BSR_HIP(hipMemcpyAsync(out_count, dc, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_k_deep_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx,
+                              float* out_dist, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > BSR_DEEP_MAX_K) return set_error(BSR_E_INVALID, "k=%u outside [1, %u]", k, BSR_DEEP_MAX_K);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    BSR_TRY(ix->deep_search_device(queries, nq, k, out_idx, out_dist, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // Scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids)
 // ---------------------------------------------------------------------------------------
 int bsr_index::score_ids_device(const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m, uint32_t k,

@@ -258,6 +258,20 @@ struct bsr_index {
     bsr::DevBuf scr_cnt;    // u32 [nq]: the present slots (score) or the keys (rerank) of a query
     bsr::DevBuf scr_idx, scr_odist, scr_ocnt;  // the rerank's result rows [nq][k], the counts [nq]
 
+    // Deep search (bsr_local_top_k_deep): exact top-k for k up to BSR_DEEP_MAX_K -- the
+    // filter rung (a deep sample threshold, the emit pass, the rescore of every emitted row, the
+    // certified selection) and the deep exact scan for the queries it leaves.  Launched directly,
+    // never captured; every result row goes to buffers of the call's own first and to the caller's
+    // arrays, host or device, only once the status words are read.
+    int deep_search_device(const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist,
+                           uint32_t* out_count);
+    bsr::DevBuf deep_rad;   // f32 [nq]: the rescore's radii, +inf
+    bsr::DevBuf deep_keys;  // u64 [nq][deep_cap(k)]: the distance keys of the emitted live rows, any order
+    bsr::DevBuf deep_cnt;   // u32 [nq]: their counts
+    bsr::DevBuf deep_part;  // u64 [kDeepScanQF][grid][k]: a scan round's per-block lists
+    bsr::DevBuf deep_idx, deep_dist, deep_ocnt;  // the result rows [nq][k], the counts [nq]
+    std::vector<float> h_deep_eb;                // the error bounds of a batch with queries left to the scan
+
     // Masked range search (bsr_local_range_search_masked): the range search with an
     // allow mask per query group -- the grouped masked search's mask buffers (grp_*), the range
     // search's result buffers (rng_*), and the row lists in segments.

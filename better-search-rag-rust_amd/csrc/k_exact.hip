@@ -1951,6 +1951,216 @@ __global__ __launch_bounds__(256) void k_range_finish(const uint64_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------
+// Deep search (bsr_local_top_k_deep): exact top-k for k up to kDeepMaxK.  The
+// filter rung emits with a deep sample threshold and rescores every emitted row (k_range_rescore,
+// radius +inf); k_deep_select picks the k smallest of a query's unordered keys and certifies them
+// against the emission threshold; k_deep_scan is the exact scan that keeps up to kDeepMaxK rows a
+// query, whose per-block lists k_deep_select merges without a certification.
+// ------------------------------------------------------------------------------------
+// sk[0 .. n) (LDS, any n, uniform over the workgroup, every store to it behind a barrier) sorted
+// ascending in place: the bitonic network in its one-direction form -- the first step of a merge
+// of 2j-blocks pairs i with its mirror image in the block, the later steps with i ^ j, the smaller
+// key always to the lower index -- over the next power of two, the slots past n standing for
+// kKeyNone: a pair with its upper end past n never swaps, so those slots are never touched.
+// Thread t takes pairs, not slots: no thread idles through a step.  Ends behind a barrier.
+__device__ __forceinline__ void lds_sort_inplace(uint64_t* sk, uint32_t n, uint32_t t) {
+    uint32_t P = 2;
+    while (P < n) P <<= 1;
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t e = t; e < P / 2; e += blockDim.x) {
+                const uint32_t lo = e & (j - 1), i = ((e - lo) << 1) | lo;
+                const uint32_t p = j == k >> 1 ? i + ((j - lo) << 1) - 1 : i + j;
+                if (p < n) {
+                    const uint64_t x = sk[i], y = sk[p];
+                    if (x > y) { sk[i] = y; sk[p] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// One workgroup per item: the k smallest of the item's c unordered keys (kKeyNone: no key; the keys
+// are distinct), sorted, as the result row of its query.  More than kDeepSortKeys keys are not held
+// but streamed from global memory (L2-resident: at most a few MB per query), once per pass of a
+// most-significant-first radix select: a histogram of the next 11 bits (9 in the sixth pass) of the
+// keys in the live bucket -- 2048 LDS bins, a wave's increments aggregated by bin where lanes agree
+// with the wave's first -- a scan of the bins by 256 threads, and the bucket that holds the k-th
+// key becomes the live one.  As soon as the keys below the live bucket plus the bucket itself fit
+// the sort buffer, exactly the keys up to the bucket's end are compacted into LDS and sorted.
+// Distance keys of one query share a long prefix, so real lists take one or two passes; six passes
+// fix all 64 bits, and a bucket of one value holds one key.
+// a.tau (the filter rung): the row is written only when it is certified -- the emitted list did
+// not overflow, at least k keys, and the k-th distance strictly below exclusion_bound() of the
+// query's emission threshold -- else the query joins the fail list and nothing is written.
+__global__ __launch_bounds__(256) void k_deep_select(DeepSelectArgs a) {
+    constexpr uint32_t BINS = 2048, PER = BINS / 256;
+    __shared__ uint64_t sk[kDeepSortKeys];
+    __shared__ uint32_t hist[BINS];
+    __shared__ uint32_t s_scan[256];
+    __shared__ uint32_t s_n, s_bin, s_below, s_bucket;
+    const uint32_t item = blockIdx.x, t = threadIdx.x;
+    const int lane = t & 63;
+    const uint32_t q = a.qids ? (uint32_t)a.qids[item] : item;
+    const uint64_t* __restrict__ src = a.keys + (uint64_t)item * a.stride;
+    const uint32_t k = a.k;
+    auto fail = [&]() {
+        if (t == 0) a.fail[atomicAdd(a.status + kStFail, 1u)] = q;
+    };
+    if (a.tau && a.emit_cnt[q] > a.cap) return fail();  // (rows were dropped; uniform over the workgroup)
+    const uint32_t c = a.kcnt ? (a.kcnt[item] < a.n_keys ? a.kcnt[item] : a.n_keys) : a.n_keys;
+    const uint32_t c_up = (c + 255u) & ~255u;  // (every lane of a wave takes every trip: ballots)
+
+    uint64_t limit = kKeyNone;  // the compaction takes the keys <= limit
+    if (c > kDeepSortKeys) {
+        uint64_t prefix = 0;    // the live bucket: its `fixed` high bits
+        uint32_t fixed = 0, below = 0, valid = 0;
+        while (true) {
+            const uint32_t width = fixed + 11 <= 64 ? 11u : 64u - fixed, shift = 64u - fixed - width;
+            for (uint32_t i = t; i < BINS; i += 256) hist[i] = 0;
+            __syncthreads();
+            for (uint32_t i = t; i < c_up; i += 256) {
+                const uint64_t key = i < c ? src[i] : kKeyNone;
+                bool in = key != kKeyNone && (fixed == 0 || (key >> (64u - fixed)) == prefix);
+                const uint32_t bin = (uint32_t)(key >> shift) & ((1u << width) - 1u);
+                const uint64_t m0 = __ballot(in);
+                if (m0) {  // the lanes that agree with the first: one add
+                    const int first = __builtin_ctzll(m0);
+                    const uint32_t b0 = (uint32_t)__shfl((int)bin, first, kWave);
+                    const uint64_t same = __ballot(in && bin == b0);
+                    if (lane == first) atomicAdd(&hist[b0], (uint32_t)__popcll(same));
+                    in = in && bin != b0;
+                }
+                if (in) atomicAdd(&hist[bin], 1u);
+            }
+            __syncthreads();
+            uint32_t mine = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < PER; ++b) mine += hist[t * PER + b];
+            s_scan[t] = mine;
+            __syncthreads();
+            for (uint32_t s = 1; s < 256; s <<= 1) {  // (inclusive scan)
+                const uint32_t v = t >= s ? s_scan[t - s] : 0u;
+                __syncthreads();
+                s_scan[t] += v;
+                __syncthreads();
+            }
+            if (fixed == 0) valid = s_scan[255];  // (the first pass counts every key)
+            if (valid <= kDeepSortKeys) break;    // (mostly empty slots: every key is taken)
+            const uint32_t kk = k - below;        // the k-th key's rank in the live bucket, >= 1
+            const uint32_t incl = s_scan[t], excl = incl - mine;
+            if (excl < kk && kk <= incl) {        // (one thread: the scan is monotone)
+                uint32_t run = excl, b = 0;
+                while (run + hist[t * PER + b] < kk) run += hist[t * PER + b++];
+                s_bin = t * PER + b;
+                s_below = below + run;
+                s_bucket = hist[t * PER + b];
+            }
+            __syncthreads();
+            prefix = (prefix << width) | s_bin;
+            fixed += width;
+            below = s_below;
+            if (below + s_bucket <= kDeepSortKeys || fixed == 64) {
+                limit = fixed == 64 ? prefix : (prefix << (64u - fixed)) | ((1ull << (64u - fixed)) - 1ull);
+                break;
+            }
+        }
+    }
+    if (t == 0) s_n = 0;
+    __syncthreads();
+    for (uint32_t i = t; i < c_up; i += 256) {
+        const uint64_t key = i < c ? src[i] : kKeyNone;
+        const bool take = key != kKeyNone && key <= limit;
+        const uint32_t slot = wave_claim(take, &s_n, lane);
+        if (take && slot < kDeepSortKeys) sk[slot] = key;
+    }
+    __syncthreads();
+    const uint32_t m = s_n < kDeepSortKeys ? s_n : kDeepSortKeys;
+    lds_sort_inplace(sk, m, t);
+    if (a.tau) {
+        const bool ok = m >= k && key_dist(sk[k - 1]) < exclusion_bound(a.tau[q], a.ebound[q], a.nb[q]);
+        if (!ok) return fail();
+    }
+    const uint32_t cnt = m < k ? m : k;
+    for (uint32_t i = t; i < k; i += 256) {
+        const bool has = i < cnt;
+        a.out_idx[(uint64_t)q * k + i] = has ? a.offset + key_row(sk[i]) : ~0ull;
+        a.out_dist[(uint64_t)q * k + i] = has ? key_dist(sk[i]) : INFINITY;
+    }
+    if (t == 0) a.out_count[q] = cnt;
+}
+
+// The exact scan for k <= kDeepMaxK: scan_tiles, and per query of the launch an LDS buffer of
+// kDeepScanBuf = 2 kDeepMaxK + 256 keys with a running threshold (kKeyNone at first).  The live rows
+// of a tile whose key lies below the threshold claim slots of the buffer, a wave at a time; a
+// buffer with fewer than 256 free slots -- less than the next tile may claim -- is sorted in place,
+// cut to its k smallest, and the k-th becomes the threshold.  At the end every buffer is sorted once
+// more and its first k keys, kKeyNone behind them, are the workgroup's partial list
+// part[query slot][block][k].  Only the launch's first nqf queries count.
+// LDS: the tile stage (68 KB + the query chunks) + QF x 18 KB, 141 KB at QF = 4 of a CU's 160 KB:
+// one workgroup per CU, so the launch bounds name no second one (k_range_scan's do).
+// Compiled with the device feature packed-fp32-ops off, as k_groups.hip is: the
+// tile loop inlined here holds no v_pk_mul_f32 / v_pk_add_f32.  (The host pass does not know the
+// feature: the attribute is the device pass's alone.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BSR_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define BSR_NO_PK_F32
+#endif
+// Buffer j of a deep scan sorted and cut to its k smallest, the k-th the new threshold (uniform
+// over the workgroup; ends behind a barrier).
+__device__ __forceinline__ void deep_scan_compact(uint64_t* buf, uint32_t* cnt, uint64_t* thr, uint32_t k, uint32_t t) {
+    const uint32_t n = *cnt < kDeepScanBuf ? *cnt : kDeepScanBuf;
+    lds_sort_inplace(buf, n, t);
+    if (t == 0) {
+        *cnt = n < k ? n : k;
+        if (n >= k) *thr = buf[k - 1];
+    }
+    __syncthreads();
+}
+template <int QF>
+__global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan(DeepScanArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[256 * 68 + (QF > 1 ? QF * 64 : 0)];
+    __shared__ uint64_t buf[QF][kDeepScanBuf];
+    __shared__ uint64_t s_thr[QF];
+    __shared__ uint32_t s_cnt[QF];
+    const uint32_t t = threadIdx.x, k = a.k;
+    const int lane = t & 63;
+    const float* qp[QF];
+    float mag_b[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        const uint32_t id = (uint32_t)a.qids[j];
+        qp[j] = a.qf32 + (uint64_t)id * a.ld;
+        mag_b[j] = a.nb[id];
+    }
+    if (t < (uint32_t)QF) { s_thr[t] = kKeyNone; s_cnt[t] = 0; }
+    __syncthreads();
+    scan_tiles<QF>(lds, a.rows, a.ld, a.dim, a.n, a.na, qp,
+                   [&](uint64_t row, bool valid, float mag_a, const float (&acc)[QF], const float (&mx)[QF]) {
+        const bool live = row_live(a.dead, row, valid);
+#pragma unroll
+        for (int j = 0; j < QF; ++j) {
+            const uint64_t key = dist_key(finish_distance(acc[j], mx[j], mag_a, mag_b[j]), (uint32_t)row);
+            const bool hit = live && (uint32_t)j < a.nqf && key < s_thr[j];
+            const uint32_t slot = wave_claim(hit, &s_cnt[j], lane);
+            if (hit && slot < kDeepScanBuf) buf[j][slot] = key;  // (always: 256 slots were free)
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QF; ++j)
+            if (s_cnt[j] > kDeepScanBuf - 256u) deep_scan_compact(buf[j], &s_cnt[j], &s_thr[j], k, t);
+    });
+    __syncthreads();
+    for (int j = 0; j < QF && (uint32_t)j < a.nqf; ++j) {
+        deep_scan_compact(buf[j], &s_cnt[j], &s_thr[j], k, t);
+        const uint32_t n = s_cnt[j];
+        uint64_t* const dst = a.part + ((uint64_t)j * gridDim.x + blockIdx.x) * k;
+        for (uint32_t i = t; i < k; i += 256) dst[i] = i < n ? buf[j][i] : kKeyNone;
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids): the
 // reference's distance of every id of a per-query list, aligned with the list.
 // ------------------------------------------------------------------------------------
@@ -2751,6 +2961,25 @@ hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint3
     if (!nq || !capacity || capacity > kRangeMaxResults || cap < capacity) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_range_finish, dim3(nq), dim3(256), 0, s, keys, rcnt, cap, capacity, offset, out_idx,
                        out_dist, out_count);
+    return hipGetLastError();
+}
+
+// ---- deep search -------------------------------------------------------------------------------
+hipError_t launch_deep_select(const DeepSelectArgs& a, hipStream_t s) {
+    if (!a.n_items || !a.k || a.k > kDeepMaxK || !a.keys || !a.out_idx || !a.out_dist || !a.out_count ||
+        (a.tau && (!a.ebound || !a.nb || !a.emit_cnt || !a.fail || !a.status)))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_deep_select, dim3(a.n_items), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_deep_scan(const DeepScanArgs& a, uint32_t grid, hipStream_t s) {
+    if (!grid || !a.nqf || a.nqf > kDeepScanQF || !a.k || a.k > kDeepMaxK || a.ld == 0 || a.ld % 64 != 0 ||
+        a.dim > a.ld || a.n > 0xffffffffull)
+        return hipErrorInvalidValue;
+    if (a.nqf <= 1) hipLaunchKernelGGL(k_deep_scan<1>, dim3(grid), dim3(256), 0, s, a);
+    else if (a.nqf <= 2) hipLaunchKernelGGL(k_deep_scan<2>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_deep_scan<4>, dim3(grid), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -540,6 +540,65 @@ hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint3
                                uint32_t capacity, uint64_t offset, uint64_t* out_idx, float* out_dist,
                                uint32_t* out_count, hipStream_t s);
 
+// ---- deep search (bsr_local_top_k_deep; k_exact.hip) ----------------------------
+constexpr uint32_t kDeepMaxK = 1024;                      // BSR_DEEP_MAX_K
+constexpr uint32_t kDeepSortKeys = 2048;                  // k_deep_select sorts at most this many keys in LDS
+constexpr uint32_t kDeepScanQF = 4;                       // queries per deep scan launch (LDS: 18 KB of keys each)
+constexpr uint32_t kDeepScanBuf = 2u * kDeepMaxK + 256u;  // a deep scan's candidate keys per query
+// The sample depth and the list length of the filter rung: the plain search's floor, and k / 8
+// above it -- about 32 ks = 4 k rows reach the threshold; the list holds four times that.
+static inline uint32_t deep_ks(uint32_t k) {
+    const uint32_t a = ks_for(10), b = (k + 7u) / 8u;
+    return a > b ? a : b;
+}
+static inline uint32_t deep_cap(uint32_t k) { return 128u * deep_ks(k); }
+// One workgroup per item: the k smallest of item i's keys -- keys + i * stride, kcnt[i] of them
+// (kcnt null: n_keys; never more than n_keys), in any order, distinct, kKeyNone = an empty slot --
+// as the result row of query qids[i] (qids null: query i): (offset + row, distance) ascending in
+// out_idx / out_dist [.][k], (~0, +inf) behind the first out_count = min(k, keys).  1 <= k <=
+// kDeepMaxK; any number of keys (they are streamed, not held).
+// tau (nullable, with ebound / nb / emit_cnt / fail / status): the filter rung's certification --
+// the row of query q is written only when emit_cnt[q] <= cap (no emitted row was dropped), it has
+// at least k keys and its k-th distance lies strictly below exclusion_bound(tau[q], ebound[q],
+// nb[q]); else nothing is written and q is appended to fail with one atomic on status[kStFail].
+struct DeepSelectArgs {
+    const uint64_t* keys;
+    uint64_t stride;
+    const uint32_t* kcnt;
+    uint32_t n_keys, n_items;
+    const int32_t* qids;
+    uint32_t k;
+    uint64_t offset;
+    uint64_t* out_idx;
+    float* out_dist;
+    uint32_t* out_count;
+    const float* tau;
+    const float* ebound;
+    const float* nb;
+    const uint32_t* emit_cnt;
+    uint32_t cap;
+    uint32_t* fail;
+    uint32_t* status;
+};
+hipError_t launch_deep_select(const DeepSelectArgs& a, hipStream_t s);
+// The exact scan of the launch's nqf <= kDeepScanQF queries (ids in qids, device; entries up to the
+// template width -- 1, 2 or 4 -- must be valid ids, those past nqf count nothing): workgroup b
+// leaves the k smallest keys of the live rows of its tiles, ascending, kKeyNone behind them, in
+// part[(j * grid + b) * k ..] for query slot j -- grid * k keys per slot for launch_deep_select.
+struct DeepScanArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t n;
+    const float* na;            // row magnitudes (read, never recomputed)
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const uint64_t* dead;       // the bitset of deleted rows (nullable)
+    const int32_t* qids;
+    uint32_t nqf, k;
+    uint64_t* part;             // [nqf][grid][k]
+};
+hipError_t launch_deep_scan(const DeepScanArgs& a, uint32_t grid, hipStream_t s);
+
 // ---- scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids) -----
 // The longest list the rerank sorts (a list is sorted in LDS, as a range result is).
 constexpr uint32_t kScoreMaxIds = 4096;

@@ -129,6 +129,8 @@ typedef struct {
 #define BSR_PATH_CAP_SCAN  65536u  /* ... and a query of the batch was answered by the capped group scan */
 #define BSR_PATH_SCORE   131072u   /* bsr_local_score_ids / bsr_local_rerank_ids ran */
 #define BSR_PATH_GROUPS  262144u   /* bsr_local_top_groups ran (with the candidate search's bits) */
+#define BSR_PATH_DEEP      524288u   /* bsr_local_top_k_deep ran */
+#define BSR_PATH_DEEP_SCAN 1048576u  /* ... and a query of the batch was answered by the deep exact scan */
 
 /* Per-kernel timing (BSR_FLAG_PROFILE): cumulative device milliseconds and launch counts
  * since the last reset, measured with hipEvents on the index's stream. */
@@ -678,6 +680,39 @@ int bsr_local_score_ids(bsr_index* ix, const float* queries, uint32_t n_queries,
 int bsr_local_rerank_ids(bsr_index* ix, const float* queries, uint32_t n_queries,
                          const uint64_t* ids, uint32_t m, uint32_t k,
                          uint64_t* out_idx, float* out_dist,  /* [n_queries][k] */
+                         uint32_t* out_count /* [n_queries] */);
+
+/* ---- Deep search: the exact top-k for k up to BSR_DEEP_MAX_K, the list a caller
+ * hands to a reranker ("the 1000 nearest chunks").  bsr_local_top_k's contract with these
+ * differences: 1 <= k <= BSR_DEEP_MAX_K, and k is not bounded by cfg.max_k (the call owns its
+ * buffers, as bsr_local_rerank_ids does).  Row q of out_idx / out_dist ([n_queries][k]) holds
+ * out_count[q] = min(k, live rows) entries in (distance asc, global index asc) order with the
+ * reference's f32 distance bits, then (~0, +inf); deleted rows are never returned.  queries and the
+ * three outputs are host or device pointers, detected per call.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; k = 0 or k > BSR_DEEP_MAX_K; with
+ *      n_queries > 0 a null queries pointer or a null output;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. n_queries = 0: BSR_OK;
+ *   4. BSR_E_NONFINITE: a non-finite query, read from the batch's status words before any of the
+ *      caller's arrays, host or device, is written.
+ * An empty shard: every count 0.
+ * How: the int8 filter with a sample threshold max(8, ceil(k / 8)) deep and lists of 128 times that
+ * many keys, the reference distance of every emitted live row, a radix selection of the k smallest
+ * that is certified against the emission threshold, and for the queries it leaves (and every query
+ * of an index that cannot filter: BSR_FLAG_EXACT_ONLY, sticky norm flags, no more live rows than a
+ * list holds) an exact scan that keeps k rows per query.  Never graph-replayed; the plain search's
+ * graphs are left alone (the first call of a size allocates, as any call does).
+ * bsr_search_stats: search_path = BSR_PATH_DEEP, plus BSR_PATH_DEEP_SCAN when any query took the
+ * scan; n_emitted = the emitted keys of the batch; n_candidates = the list capacity;
+ * n_exact_direct = queries sent to the scan by design; n_fallback = queries whose filtered result
+ * could not be certified, an overflowed list included.  BSR_FLAG_PROFILE: the rescore and the
+ * selection in rescore_ms, the scan rounds in scan_ms, the call in search_ms.
+ * Out of scope: allow masks and groups with deep k; a multi-rank deep search (the per-rank lists
+ * merge with bsr_global_top_k on the host as they are). */
+#define BSR_DEEP_MAX_K 1024u
+int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                         uint64_t* out_idx, float* out_dist, /* [n_queries][k] */
                          uint32_t* out_count /* [n_queries] */);
 
 /* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists, on the host.  Layout and
