@@ -171,6 +171,7 @@ def lib() -> ctypes.CDLL:
         "bsr_local_score_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P]),
         "bsr_local_rerank_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_deep": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
+        "bsr_local_top_k_deep_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_global_top_k_capped": (ctypes.c_int, [_P, _P, _P, _P, u32, u32, u32, u32, u32, _P, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
@@ -197,7 +198,7 @@ def lib() -> ctypes.CDLL:
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
                 "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids",
-                "bsr_local_top_groups", "bsr_local_top_k_deep"}
+                "bsr_local_top_groups", "bsr_local_top_k_deep", "bsr_local_top_k_deep_masked"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -585,9 +586,19 @@ class Index:
         _check(lib().bsr_local_top_k_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), nw,
                                             _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist), _ptr(out_count)))
 
-    def deep_search(self, queries, k: int):
+    def deep_search(self, queries, k: int, allow_mask=None, allow_ids=None, allow_masks=None, query_mask=None,
+                    mask_mode="auto"):
         """Exact top-k for k up to BSR_DEEP_MAX_K (bsr_local_top_k_deep), not bounded by max_k ->
-        (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32), local_top_k's triple."""
+        (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32), local_top_k's triple.
+        Restricted to allowed rows (bsr_local_top_k_deep_masked): allow_mask / allow_ids give one mask
+        for the batch, allow_masks [G][n] with query_mask [Q] one mask per query group, and mask_mode
+        ("auto", "list", "filter" or a BSR_MASK_* value, per mask group): as range_search's.  The
+        counts are then min(k, allowed live rows of the query's mask)."""
+        one = allow_mask is not None or allow_ids is not None
+        if one and (allow_masks is not None or query_mask is not None):
+            raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
+        if (allow_masks is None) != (query_mask is None):
+            raise BsrError(-1, "allow_masks and query_mask go together")
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q.reshape(1, -1)
@@ -599,14 +610,40 @@ class Index:
         oi = np.empty((nq, k), np.uint64)
         od = np.empty((nq, k), np.float32)
         oc = np.empty(nq, np.uint32)
-        _check(lib().bsr_local_top_k_deep(self._h, _ptr(q), nq, k, _ptr(oi), _ptr(od), _ptr(oc)))
+        if not one and allow_masks is None:
+            _check(lib().bsr_local_top_k_deep(self._h, _ptr(q), nq, k, _ptr(oi), _ptr(od), _ptr(oc)))
+            return oi, od, oc
+        if one:
+            w, nw = self._allow_words(allow_mask, allow_ids)
+            n_masks, qm = 1, None
+        else:
+            w, n_masks, nw = self._allow_group_words(allow_masks)
+            qm = self._query_mask_ids(query_mask, nq)
+        # (an empty shard's masks have no words: a valid, non-null pointer all the same)
+        wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
+        _check(lib().bsr_local_top_k_deep_masked(self._h, _ptr(q), nq, k, wp, nw, n_masks, _ptr(qm),
+                                                 _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(oc)))
         return oi, od, oc
 
-    def deep_search_device(self, queries, nq: int, k: int, out_idx, out_dist, out_count):
+    def deep_search_device(self, queries, nq: int, k: int, out_idx, out_dist, out_count, allow_words=None,
+                           query_mask=None, mask_mode="auto"):
         """Zero-copy variant on caller buffers (torch tensors, numpy arrays or raw pointers, each
-        host or device): queries [nq][dim] f32, out_idx / out_dist [nq][k], out_count [nq]."""
-        _check(lib().bsr_local_top_k_deep(self._h, _ptr(queries), nq, k, _ptr(out_idx), _ptr(out_dist),
-                                          _ptr(out_count)))
+        host or device): queries [nq][dim] f32, out_idx / out_dist [nq][k], out_count [nq].
+        allow_words: the packed allow masks, [G][ceil(n / 64)] uint64 with query_mask [nq] 32-bit mask
+        ids, or [ceil(n / 64)] -- one mask, no query_mask."""
+        if allow_words is None:
+            if query_mask is not None:
+                raise BsrError(-1, "a query_mask needs allow_words")
+            _check(lib().bsr_local_top_k_deep(self._h, _ptr(queries), nq, k, _ptr(out_idx), _ptr(out_dist),
+                                              _ptr(out_count)))
+            return
+        shape = tuple(allow_words.shape)
+        if len(shape) not in (1, 2):
+            raise BsrError(-1, "packed allow masks have shape [G][words] or [words]")
+        n_masks = int(shape[0]) if len(shape) == 2 else 1
+        _check(lib().bsr_local_top_k_deep_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), int(shape[-1]),
+                                                 n_masks, _ptr(query_mask), _mask_mode(mask_mode), _ptr(out_idx),
+                                                 _ptr(out_dist), _ptr(out_count)))
 
     def range_search(self, queries, radius, max_results: int = 256, allow_mask=None, allow_ids=None,
                      allow_masks=None, query_mask=None, mask_mode="auto"):

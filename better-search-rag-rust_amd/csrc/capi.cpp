@@ -45,6 +45,10 @@ int bsr_local_range_search_masked_impl(bsr_index* ix, const float* queries, uint
                                        float* out_dist, uint32_t* out_count);
 int bsr_local_top_k_deep_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_idx,
                               float* out_dist, uint32_t* out_count);
+int bsr_local_top_k_deep_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k,
+                                     const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                     const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                     uint32_t* out_count);
 int bsr_local_score_ids_impl(bsr_index* ix, const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m,
                              float* out_dist, uint32_t* out_found);
 int bsr_local_rerank_ids_impl(bsr_index* ix, const float* queries, uint32_t nq, const uint64_t* ids, uint32_t m,
@@ -408,6 +412,14 @@ int bsr_local_range_search_masked(bsr_index* ix, const float* queries, uint32_t 
 int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint64_t* out_idx,
                          float* out_dist, uint32_t* out_count) {
     BSR_GUARD(bsr_local_top_k_deep_impl(ix, queries, n_queries, k, out_idx, out_dist, out_count));
+}
+
+int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                                const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                uint32_t* out_count) {
+    BSR_GUARD(bsr_local_top_k_deep_masked_impl(ix, queries, n_queries, k, allow, allow_words, n_masks, query_mask, mode,
+                                               out_idx, out_dist, out_count));
 }
 
 int bsr_local_score_ids(bsr_index* ix, const float* queries, uint32_t n_queries, const uint64_t* ids, uint32_t m,

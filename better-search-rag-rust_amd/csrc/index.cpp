@@ -1654,22 +1654,23 @@ static QueriesByMask queries_by_mask(const bsr_index* ix, uint32_t n_masks, cons
 struct GroupLaunch { uint32_t qf, groups, grid; size_t scan0, ids0; };
 template <class Desc>
 static std::vector<GroupLaunch> plan_query_groups(bsr_index* ix, const Desc* d, size_t n_d, const QueriesByMask& by,
-                                                  uint32_t max_groups, uint32_t k) {
+                                                  uint32_t max_groups, uint32_t k, uint32_t qf_max = kScanQF) {
+    // (qf_max: the widest group -- the deep list scan's is kDeepScanQF)
     std::vector<ScanGroupDesc>& scans = ix->h_grp_scan;
     std::vector<int32_t>& ids = ix->h_grp_ids;
     std::vector<GroupLaunch> launches;
-    for (uint32_t qf = kScanQF; qf >= 1; qf /= 2) {
+    for (uint32_t qf = qf_max; qf >= 1; qf /= 2) {
         const size_t scan0 = scans.size(), ids0 = ids.size();
         uint32_t longest = 0;
         for (size_t l = 0; l < n_d; ++l) {
-            const uint32_t q0 = by.start[d[l].mask], nqg = by.start[d[l].mask + 1] - q0, rest = nqg % kScanQF;
+            const uint32_t q0 = by.start[d[l].mask], nqg = by.start[d[l].mask + 1] - q0, rest = nqg % qf_max;
             auto group = [&](uint32_t first, uint32_t cnt) {
                 scans.push_back(ScanGroupDesc{d[l].off, d[l].n_list, cnt});
                 for (uint32_t j = 0; j < qf; ++j) ids.push_back((int32_t)by.order[first + (j < cnt ? j : 0)]);
                 longest = std::max(longest, d[l].n_list);
             };
-            if (qf == kScanQF)
-                for (uint32_t f = 0; f + kScanQF <= nqg; f += kScanQF) group(q0 + f, kScanQF);
+            if (qf == qf_max)
+                for (uint32_t f = 0; f + qf_max <= nqg; f += qf_max) group(q0 + f, qf_max);
             if (rest && rest <= qf && rest > qf / 2) group(q0 + nqg - rest, rest);
         }
         const size_t n_groups = scans.size() - scan0;
@@ -2759,6 +2760,328 @@ int bsr_local_range_search_masked_impl(bsr_index* ix, const float* queries, uint
         return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
     BSR_TRY(ix->range_search_device_masked(queries, nq, radius, capacity, allow, allow_words, n_masks, query_mask, mode,
                                            out_idx, out_dist, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Masked deep search (bsr_local_top_k_deep_masked)
+// ---------------------------------------------------------------------------------------
+// The filter rung's sample depth for a mask group: deep_ks(k) lowered by live / A, masked_ks' rule;
+// 0 where launch_select_tau cannot select that deep or the shard's live rows would fit one list.
+static uint32_t deep_masked_ks(uint32_t k, uint64_t live, uint64_t A) {
+    if (!A) return 0;
+    const uint64_t ks_m = ((uint64_t)deep_ks(k) * live + A - 1) / A;
+    return ks_m <= 128 && live > 128 * ks_m ? (uint32_t)ks_m : 0u;
+}
+
+// The deep exact scan over row lists for the queries `listed` (ascending ids), every one over the
+// list of its own mask: run_range_list_scan's segments and chunks with groups of at most
+// kDeepScanQF queries.  A launch scans one segment of a query's list at most; the selection behind
+// it merges the workgroups' lists with the query's carry -- deep_carry[q], its k best keys so far,
+// kKeyNone before the first segment -- and writes the carry again, so that after the last chunk
+// the carry of every listed query holds its k best keys over its whole list.
+static int run_deep_list_scan(bsr_index* ix, uint32_t k, const uint64_t* allow, uint64_t words, uint32_t n_masks,
+                              const std::vector<uint32_t>& listed) {
+    const std::vector<uint32_t>& A = ix->h_grp_out;
+    const QueriesByMask by = queries_by_mask(ix, n_masks, listed);
+    const std::vector<uint32_t>& start = by.start;
+    if (by.order.empty()) return BSR_OK;
+
+    struct Chunk { size_t seg0; uint32_t n_segs; std::vector<GroupLaunch> launches; };
+    std::vector<Chunk> chunks;
+    std::vector<MaskSegDesc>& segs = ix->h_rng_segs;
+    std::vector<ScanGroupDesc>& scans = ix->h_grp_scan;
+    std::vector<int32_t>& ids = ix->h_grp_ids;
+    segs.clear();
+    scans.clear();
+    ids.clear();
+    const uint64_t budget = mask_list_budget_ids();
+    uint64_t used = 0, list_ids = 0;
+    size_t part_bytes = 0;
+    Chunk cur{0, 0, {}};
+    auto close = [&]() {
+        if (!cur.n_segs) return;
+        cur.launches = plan_query_groups(ix, segs.data() + cur.seg0, cur.n_segs, by, 65535, k, kDeepScanQF);
+        for (const GroupLaunch& l : cur.launches)
+            part_bytes = std::max(part_bytes, (size_t)l.groups * l.qf * (l.grid + 1) * k * sizeof(uint64_t));
+        list_ids = std::max(list_ids, used);
+        chunks.push_back(std::move(cur));
+        cur = Chunk{segs.size(), 0, {}};
+        used = 0;
+    };
+    for (uint32_t g = 0; g < n_masks; ++g) {
+        if (start[g] == start[g + 1]) continue;
+        for (uint32_t pos = 0; pos < A[g];) {
+            if (used == budget) close();
+            const uint32_t take = (uint32_t)std::min<uint64_t>(A[g] - pos, budget - used);
+            segs.push_back(MaskSegDesc{used, g, pos, take, 0});
+            ++cur.n_segs;
+            used += take;
+            pos += take;
+        }
+    }
+    close();
+
+    BSR_TRY(ix->mask_list.ensure((size_t)list_ids * sizeof(uint32_t)));
+    BSR_TRY(ix->deep_part.ensure(part_bytes));
+    BSR_TRY(ix->rng_segs.ensure(segs.size() * sizeof(MaskSegDesc)));
+    BSR_TRY(ix->grp_scan.ensure(scans.size() * sizeof(ScanGroupDesc)));
+    BSR_TRY(ix->qids.ensure(ids.size() * sizeof(int32_t)));
+    BSR_HIP(hipMemcpyAsync(ix->rng_segs.p, segs.data(), segs.size() * sizeof(MaskSegDesc), hipMemcpyHostToDevice,
+                           ix->stream));
+    BSR_HIP(hipMemcpyAsync(ix->grp_scan.p, scans.data(), scans.size() * sizeof(ScanGroupDesc), hipMemcpyHostToDevice,
+                           ix->stream));
+    BSR_HIP(hipMemcpyAsync(ix->qids.p, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, ix->stream));
+    DeepListArgs la{};
+    la.rows = ix->rows.as<float>();
+    la.ld = ix->ld;
+    la.dim = ix->dim;
+    la.na = ix->na.as<float>();
+    la.qf32 = ix->qf32.as<float>();
+    la.nb = ix->nb.as<float>();
+    la.list = ix->mask_list.as<uint32_t>();
+    la.k = k;
+    la.part = ix->deep_part.as<uint64_t>();
+    la.carry = ix->deep_carry.as<uint64_t>();
+    DeepSelectArgs se{};
+    se.keys = la.part;
+    se.k = k;
+    se.out_keys = ix->deep_carry.as<uint64_t>();
+    ev_begin(ix, ix->ev_scan, 1);
+    for (const Chunk& c : chunks) {
+        // (the stream orders a chunk's scatter behind the scans of the chunk before it)
+        BSR_HIP(launch_mask_groups_scatter_seg(allow, words, ix->n, ix->dead_bits(), ix->grp_blk.as<uint32_t>(),
+                                               ix->rng_segs.as<MaskSegDesc>() + c.seg0, c.n_segs,
+                                               ix->mask_list.as<uint32_t>(), ix->stream));
+        for (const GroupLaunch& l : c.launches) {
+            la.grp = se.grp = ix->grp_scan.as<ScanGroupDesc>() + l.scan0;
+            la.qids = se.qids = ix->qids.as<int32_t>() + l.ids0;
+            la.groups = l.groups;
+            la.qf = se.qf = l.qf;
+            se.n_items = l.groups * l.qf;
+            se.stride = (uint64_t)(l.grid + 1) * k;
+            se.n_keys = (l.grid + 1) * k;
+            BSR_HIP(launch_deep_scan_list(la, l.grid, ix->stream));
+            BSR_HIP(launch_deep_select(se, ix->stream));
+        }
+    }
+    ev_end(ix, ix->ev_scan);
+    return BSR_OK;
+}
+
+int bsr_index::deep_search_device_masked(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                                         uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
+                                         uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_count) {
+    bsr_index* ix = this;
+    BSR_TRY(check_batch(ix, 1));  // (loaded; k has its own bound, checked by the entry point)
+    if (allow_words != (n + 63) / 64)
+        return set_error(BSR_E_INVALID, "allow_words=%llu, the index holds %llu rows (%llu words)",
+                         (unsigned long long)allow_words, (unsigned long long)n, (unsigned long long)((n + 63) / 64));
+    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_DEEP | (query_mask ? BSR_PATH_MASK_GROUPS : 0u)));
+    if (nq == 0) return BSR_OK;
+
+    const uint32_t qpad = qpad_for(nq);
+    const size_t nk = (size_t)nq * k;
+    BSR_TRY(query_buffers(ix, nq, qpad, 1));
+    BSR_TRY(mask_aux.ensure(((size_t)qpad + 1) * sizeof(uint32_t)));
+    BSR_TRY(deep_carry.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(deep_idx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(deep_dist.ensure(nk * sizeof(float)));
+    BSR_TRY(deep_ocnt.ensure((size_t)nq * sizeof(uint32_t)));
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
+    // The masks and the mask ids on the device; the ids on the host too (it forms the query groups).
+    const uint64_t* dallow = allow;
+    if (allow_words)
+        BSR_TRY(on_device(ix, mask_dev, allow, (size_t)n_masks * allow_words * sizeof(uint64_t), is_device_ptr(allow),
+                          &dallow));
+    const uint32_t* dqmask = query_mask;  // (nullptr: mask 0 for every query, n_masks == 1)
+    h_grp_qmask.assign(nq, 0);
+    if (query_mask && is_device_ptr(query_mask)) {
+        BSR_HIP(hipMemcpyAsync(h_grp_qmask.data(), query_mask, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               stream));
+    } else if (query_mask) {
+        memcpy(h_grp_qmask.data(), query_mask, (size_t)nq * sizeof(uint32_t));
+        BSR_TRY(grp_qmask.ensure((size_t)nq * sizeof(uint32_t)));
+        BSR_HIP(hipMemcpyAsync(grp_qmask.p, h_grp_qmask.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               stream));
+        dqmask = grp_qmask.as<uint32_t>();
+    }
+    // 1. Every A_g (over allow_g & ~dead) and the check of query_mask: one readback.
+    const uint32_t n_blk = mask_blocks(n);
+    BSR_TRY(grp_blk.ensure((size_t)n_masks * (n_blk + 1) * sizeof(uint32_t)));
+    BSR_TRY(grp_out.ensure(((size_t)n_masks + 1) * sizeof(uint32_t)));
+    h_grp_out.assign((size_t)n_masks + 1, 0);
+    BSR_HIP(launch_mask_groups_count(dallow, allow_words, n_masks, n, dead_bits(), dqmask, nq, grp_blk.as<uint32_t>(),
+                                     grp_out.as<uint32_t>(), stream));
+    BSR_HIP(hipMemcpyAsync(h_grp_out.data(), grp_out.p, ((size_t)n_masks + (dqmask ? 1 : 0)) * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    if (dqmask && h_grp_out[n_masks])
+        return set_error(BSR_E_INVALID, "%u entries of query_mask name no mask (n_masks = %u)", h_grp_out[n_masks],
+                         n_masks);
+
+    // 2. The path of every mask group, from its own A_g and query count: the filter rung where the
+    // threshold can be lowered to the group's depth, the list scan elsewhere.
+    const uint64_t live = live_rows();
+    std::vector<uint32_t> nq_g(n_masks, 0), ks_g(n_masks, 0);
+    for (uint32_t q = 0; q < nq; ++q) ++nq_g[h_grp_qmask[q]];
+    uint32_t ks_max = 0, n_list_q = 0;
+    for (uint32_t g = 0; g < n_masks; ++g) {
+        if (!nq_g[g] || !approx_ok || mode == BSR_MASK_LIST) continue;
+        const uint32_t ks_m = deep_masked_ks(k, live, h_grp_out[g]);
+        if (!ks_m || (mode == BSR_MASK_AUTO && auto_prefers_list(n, h_grp_out[g], nq_g[g], k))) continue;
+        ks_g[g] = ks_m;
+        ks_max = std::max(ks_max, ks_m);
+    }
+    const bool any_filter = ks_max != 0;
+    const uint32_t cap_m = 128u * ks_max;  // (one emission cap for the batch)
+    std::vector<uint8_t> on_list(nq, 0);
+    h_grp_ksq.assign(qpad, 0);
+    for (uint32_t q = 0; q < nq; ++q) {
+        h_grp_ksq[q] = ks_g[h_grp_qmask[q]];
+        on_list[q] = h_grp_ksq[q] == 0;
+        n_list_q += on_list[q];
+    }
+    stats.search_path |= (any_filter ? BSR_PATH_MASK_FILTER : 0u) | (n_list_q ? BSR_PATH_MASK_LIST : 0u);
+    stats.n_exact_direct = n_list_q;
+    if (any_filter) {
+        BSR_TRY(grp_ksq.ensure((size_t)qpad * sizeof(uint32_t)));
+        BSR_TRY(deep_keys.ensure((size_t)nq * cap_m * sizeof(uint64_t)));
+        BSR_TRY(deep_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+        BSR_TRY(deep_rad.ensure((size_t)nq * sizeof(float)));
+    }
+    // (a query that is neither certified nor scanned -- its mask allows no row -- keeps an empty carry)
+    BSR_HIP(hipMemsetAsync(deep_carry.p, 0xff, nk * sizeof(uint64_t), stream));
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, any_filter), stream));
+
+    if (any_filter) {
+        // 3. The filter rung, once over the batch: every query's threshold at its own depth (a
+        // list-group query's at +inf: it emits nothing), the lists cut by the query's own mask, the
+        // reference distance of every remaining row (a radius of +inf), and the certified selection
+        // into the carry.  The cut only removes keys: a row it leaves out was not emitted at tau or
+        // is not allowed, so the certification against tau stands.
+        BSR_HIP(hipMemcpyAsync(grp_ksq.p, h_grp_ksq.data(), (size_t)qpad * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        BSR_TRY(sample_pass(ix, nq, qpad, k, nullptr, ks_max, cap_m, grp_ksq.as<uint32_t>()));
+        BSR_TRY(emit_pass(ix, nq, qpad, k, cap_m));
+        uint32_t* raw_cnt = mask_aux.as<uint32_t>();
+        BSR_HIP(launch_mask_cut(cand.as<uint64_t>(), cnt.as<uint32_t>(), cap_m, nq, dallow, allow_words, dqmask,
+                                dead_bits(), n, raw_cnt, raw_cnt + qpad, stream));
+        BSR_HIP(hipMemsetAsync(deep_cnt.p, 0, (size_t)nq * sizeof(uint32_t), stream));
+        BSR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(deep_rad.p), 0x7f800000, nq, stream));
+        RangeArgs ra{};
+        ra.rows = rows.as<float>();
+        ra.ld = ld;
+        ra.dim = dim;
+        ra.n = n;
+        ra.na = na.as<float>();
+        ra.qf32 = qf32.as<float>();
+        ra.nb = nb.as<float>();
+        ra.radius = deep_rad.as<float>();
+        ra.dead = dead_bits();
+        ra.keys = deep_keys.as<uint64_t>();
+        ra.rcnt = deep_cnt.as<uint32_t>();
+        ra.cap = cap_m;
+        ra.nq = nq;
+        ra.cand = cand.as<uint64_t>();
+        ra.cnt = cnt.as<uint32_t>();
+        ra.scan_list = fail.as<uint32_t>();
+        ra.status = d_status;
+        ra.emit_cnt = raw_cnt;
+        ev_begin(ix, ev_rescore);
+        BSR_HIP(launch_range_rescore(ra, stream));
+        // (the rescore listed the overflowed queries; the selection lists every query it does not
+        // certify, those included: its list starts empty)
+        BSR_HIP(hipMemsetAsync(d_status + kStFail, 0, sizeof(uint32_t), stream));
+        DeepSelectArgs se{};
+        se.keys = ra.keys;
+        se.stride = cap_m;
+        se.kcnt = ra.rcnt;
+        se.n_keys = cap_m;
+        se.n_items = nq;
+        se.k = k;
+        se.out_keys = deep_carry.as<uint64_t>();
+        se.tau = tau.as<float>();
+        se.ebound = ebound.as<float>();
+        se.nb = nb.as<float>();
+        se.emit_cnt = raw_cnt;
+        se.cap = cap_m;
+        se.fail = fail.as<uint32_t>();
+        se.status = d_status;
+        BSR_HIP(launch_deep_select(se, stream));
+        ev_end(ix, ev_rescore);
+    }
+    stats.n_candidates = cap_m;
+    // 4. The one status readback: the query flags and the queries the rung did not certify.
+    BSR_HIP(hipMemcpyAsync(h_res, d_status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BSR_HIP(stream_wait(stream));
+    BSR_TRY(check_queries(ix, nq));
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+    if (any_filter) {
+        stats.n_emitted = st[kStEmitted];
+        const uint32_t nfail = st[kStFail];
+        if (nfail) {
+            // Uncertified queries and queries the filter cannot serve join the list scan of their own
+            // mask; the list-group queries among them (empty lists: never certified) are there already.
+            h_fail.resize(nfail);
+            h_qflags.resize(nq);
+            BSR_HIP(hipMemcpy(h_fail.data(), fail.p, (size_t)nfail * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            BSR_HIP(hipMemcpy(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (uint32_t q : h_fail) {
+                if (q >= nq || on_list[q]) continue;
+                on_list[q] = 1;
+                if (h_qflags[q] & kQueryNoApprox) ++stats.n_exact_direct;
+                else ++stats.n_fallback;
+                stats.search_path |= BSR_PATH_MASK_LIST;
+            }
+        }
+    }
+    // 5. The list scan of every query left, over the list of its own mask, in chunks with the carry.
+    std::vector<uint32_t> listed;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (on_list[q]) listed.push_back(q);
+    BSR_TRY(run_deep_list_scan(ix, k, dallow, allow_words, n_masks, listed));
+    // 6. Every query's carry holds its k best keys (or none): one selection writes the result rows.
+    DeepSelectArgs fe{};
+    fe.keys = deep_carry.as<uint64_t>();
+    fe.stride = k;
+    fe.n_keys = k;
+    fe.n_items = nq;
+    fe.k = k;
+    fe.offset = global_offset;
+    fe.out_idx = deep_idx.as<uint64_t>();
+    fe.out_dist = deep_dist.as<float>();
+    fe.out_count = deep_ocnt.as<uint32_t>();
+    BSR_HIP(launch_deep_select(fe, stream));
+    ev_end(ix, ev_total);
+    // Every row was written to the index's own buffers -- the status is read before any of the
+    // caller's arrays, host or device, is written -- and goes out with one copy each.
+    BSR_HIP(hipMemcpyAsync(out_idx, deep_idx.p, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+    BSR_HIP(hipMemcpyAsync(out_dist, deep_dist.p, nk * sizeof(float), hipMemcpyDefault, stream));
+    BSR_HIP(hipMemcpyAsync(out_count, deep_ocnt.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_k_deep_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k,
+                                     const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                     const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                     uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > BSR_DEEP_MAX_K) return set_error(BSR_E_INVALID, "k=%u outside [1, %u]", k, BSR_DEEP_MAX_K);
+    if (n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 (bsr_local_top_k_deep searches without a mask)");
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (nq && !allow) return set_error(BSR_E_INVALID, "null allow masks");
+    if (!query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    BSR_TRY(ix->deep_search_device_masked(queries, nq, k, allow, allow_words, n_masks, query_mask, mode, out_idx,
+                                          out_dist, out_count));
     collect_profile(ix);
     return BSR_OK;
 }

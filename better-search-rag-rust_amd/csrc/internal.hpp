@@ -284,6 +284,15 @@ struct bsr_index {
     std::vector<uint32_t> h_rng_route;
     std::vector<bsr::MaskSegDesc> h_rng_segs;
 
+    // Masked deep search (bsr_local_top_k_deep_masked): the deep search with an allow
+    // mask per query group -- the grouped masked search's mask buffers (grp_*), the list segments of
+    // the masked range search (rng_segs), the deep search's key and result buffers (deep_*), and the
+    // carry of a list scan in chunks.  Launched directly, never captured.
+    int deep_search_device_masked(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
+                                  uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
+                                  uint64_t* out_idx, float* out_dist, uint32_t* out_count);
+    bsr::DevBuf deep_carry;  // u64 [nq][k]: a listed query's k best keys of the segments scanned so far
+
     // MMR search (bsr_local_top_k_mmr): the candidate search with k = fetch_k (plain,
     // masked or grouped, by the mask arguments) run to completion, then the selection kernel over the
     // lists it left in d_idx / d_dist / d_cnt -- launched directly, never captured -- into the

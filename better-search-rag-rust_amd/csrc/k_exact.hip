@@ -1990,6 +1990,9 @@ __device__ __forceinline__ void lds_sort_inplace(uint64_t* sk, uint32_t n, uint3
 // the sort buffer, exactly the keys up to the bucket's end are compacted into LDS and sorted.
 // Distance keys of one query share a long prefix, so real lists take one or two passes; six passes
 // fix all 64 bits, and a bucket of one value holds one key.
+// a.out_keys (the masked deep search): the k keys go to out_keys[q][k], kKeyNone behind
+// them, instead of a result row (with a.tau: a certified query's only); a.grp with a.qf: item i is slot i % qf of query group i / qf and
+// counts only below the group's nq.  Both null: neither changes anything.
 // a.tau (the filter rung): the row is written only when it is certified -- the emitted list did
 // not overflow, at least k keys, and the k-th distance strictly below exclusion_bound() of the
 // query's emission threshold -- else the query joins the fail list and nothing is written.
@@ -2001,6 +2004,7 @@ __global__ __launch_bounds__(256) void k_deep_select(DeepSelectArgs a) {
     __shared__ uint32_t s_n, s_bin, s_below, s_bucket;
     const uint32_t item = blockIdx.x, t = threadIdx.x;
     const int lane = t & 63;
+    if (a.grp && item % a.qf >= a.grp[item / a.qf].nq) return;  // (a padding slot; uniform over the workgroup)
     const uint32_t q = a.qids ? (uint32_t)a.qids[item] : item;
     const uint64_t* __restrict__ src = a.keys + (uint64_t)item * a.stride;
     const uint32_t k = a.k;
@@ -2082,6 +2086,10 @@ __global__ __launch_bounds__(256) void k_deep_select(DeepSelectArgs a) {
         if (!ok) return fail();
     }
     const uint32_t cnt = m < k ? m : k;
+    if (a.out_keys) {  // (the carry of a list scan in chunks: the keys themselves, no result row yet)
+        for (uint32_t i = t; i < k; i += 256) a.out_keys[(uint64_t)q * k + i] = i < cnt ? sk[i] : kKeyNone;
+        return;
+    }
     for (uint32_t i = t; i < k; i += 256) {
         const bool has = i < cnt;
         a.out_idx[(uint64_t)q * k + i] = has ? a.offset + key_row(sk[i]) : ~0ull;
@@ -2157,6 +2165,137 @@ __global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan(DeepScanArgs a)
         const uint32_t n = s_cnt[j];
         uint64_t* const dst = a.part + ((uint64_t)j * gridDim.x + blockIdx.x) * k;
         for (uint32_t i = t; i < k; i += 256) dst[i] = i < n ? buf[j][i] : kKeyNone;
+    }
+}
+
+// The deep exact scan over row lists (bsr_local_top_k_deep_masked): k_deep_scan's
+// buffers and threshold over the list of a mask instead of every row of the shard.  Workgroup
+// (x, y) takes the tiles x, x + gridDim.x, ... of group y's list -- the grp[y].n_list ids at list +
+// grp[y].off, 256 positions per tile, lane = position, every id read once (the next tile's a tile
+// ahead) -- for the QF queries qids[y * QF ..], of which the first grp[y].nq count.  No mask and no
+// tombstone is read: the list holds the allowed live rows.
+// The gather is per wave, with no barrier inside a tile: a wave walks its own 64 rows through its
+// own LDS stage (64 x 68 floats), chunk by chunk -- load_cand_chunk, two chunks in flight in
+// registers -- and stages the same chunk of the QF queries beside it (lane l: float4 l & 15 of query
+// l >> 4; one float4 a lane at QF = 4), so that seq_chunk reads rows and queries from LDS.  Two
+// barriers a tile order the claims of the four waves against the compaction of a full buffer.
+// Workgroup x leaves slot j's k smallest keys ascending, kKeyNone behind them, at
+// part[((y * QF + j) * (gridDim.x + 1) + 1 + x) * k ..]; workgroup 0 copies the query's carry -- its
+// k best keys of the list segments scanned before, carry[id * k ..] -- to the front of the slot
+// (... + 0) * k, so that a slot is (gridDim.x + 1) * k keys for k_deep_select.
+// LDS: 4 x 17 KB of row stages + QF KB of query chunks + QF x 18 KB of keys: 144 KB at QF = 4, 107
+// KB at 2, 88 KB at 1 of a CU's 160 KB -- one workgroup per CU at every width.
+template <int QF>
+__device__ __forceinline__ void deep_list_walk(float* st, float* ldq, const float* __restrict__ rows, uint32_t ld,
+                                               uint32_t dim, uint32_t myrow, const float* const (&qp)[QF], int lane,
+                                               float (&acc)[QF], float (&mx)[QF]) {
+    const uint32_t nch = ld / 64;
+    uint32_t lrow[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) lrow[i] = (uint32_t)__shfl((int)myrow, (i * 64 + lane) >> 4, kWave);
+    const float* qsrc = nullptr;  // this lane's float4 of a query chunk
+#pragma unroll
+    for (int j = 0; j < QF; ++j)
+        if ((lane >> 4) == j) qsrc = qp[j] + (lane & 15) * 4;
+    float* const qdst = ldq + (lane >> 4) * 64 + (lane & 15) * 4;
+    const float* bq[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) bq[j] = ldq + j * 64;
+    const f32x4_t zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto step = [&](f32x4_t (&pre)[16], f32x4_t& qpre, uint32_t ch) {
+        wave_sync();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int L16 = i * 64 + lane;
+            *reinterpret_cast<f32x4_t*>(st + (L16 >> 4) * 68 + (L16 & 15) * 4) = pre[i];
+        }
+        if (qsrc) *reinterpret_cast<f32x4_t*>(qdst) = qpre;
+        wave_sync();
+        if (ch + 2 < nch) {
+            load_cand_chunk(pre, rows, ld, lrow, ch + 2, lane);
+            if (qsrc) qpre = *reinterpret_cast<const f32x4_t*>(qsrc + (ch + 2) * 64);
+        }
+        const uint32_t nvalid = dim - ch * 64 < 64 ? dim - ch * 64 : 64;
+        seq_chunk<QF>(st + lane * 68, bq, nvalid, acc, mx);
+    };
+    f32x4_t preA[16], preB[16], qA = zero, qB = zero;
+    load_cand_chunk(preA, rows, ld, lrow, 0, lane);
+    if (qsrc) qA = *reinterpret_cast<const f32x4_t*>(qsrc);
+    if (nch > 1) {
+        load_cand_chunk(preB, rows, ld, lrow, 1, lane);
+        if (qsrc) qB = *reinterpret_cast<const f32x4_t*>(qsrc + 64);
+    }
+    for (uint32_t ch = 0; ch < nch; ch += 2) {
+        step(preA, qA, ch);
+        if (ch + 1 < nch) step(preB, qB, ch + 1);
+    }
+}
+
+template <int QF>
+__global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan_list(DeepListArgs a) {
+    constexpr int STAGE = 64 * 68;
+    __shared__ __attribute__((aligned(16))) float lds[4 * STAGE + 4 * QF * 64];
+    __shared__ uint64_t buf[QF][kDeepScanBuf];
+    __shared__ uint64_t s_thr[QF];
+    __shared__ uint32_t s_cnt[QF];
+    const ScanGroupDesc me = a.grp[blockIdx.y];
+    const uint32_t* __restrict__ list = a.list + me.off;
+    const uint32_t n_list = me.n_list, k = a.k;
+    const uint32_t t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    float* const st = lds + w * STAGE;
+    float* const ldq = lds + 4 * STAGE + w * QF * 64;
+    const int32_t* qids = a.qids + (uint64_t)blockIdx.y * QF;
+    const float* qp[QF];
+    float mag_b[QF];
+    uint32_t id[QF];
+#pragma unroll
+    for (int j = 0; j < QF; ++j) {
+        id[j] = (uint32_t)qids[j];
+        qp[j] = a.qf32 + (uint64_t)id[j] * a.ld;
+        mag_b[j] = a.nb[id[j]];
+    }
+    if (t < (uint32_t)QF) { s_thr[t] = kKeyNone; s_cnt[t] = 0; }
+    __syncthreads();
+
+    const uint64_t n_tiles = ((uint64_t)n_list + 255) / 256;
+    // entry t of a tile (past the list: row 0, never walked by a wave without a listed row, never kept)
+    auto id_at = [&](uint64_t tl) -> uint32_t {
+        const uint64_t p = tl * 256 + t;
+        return p < n_list ? list[p] : 0u;
+    };
+    uint32_t idn = id_at(blockIdx.x);
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t myrow = idn;
+        const bool valid = tile * 256 + t < n_list;
+        idn = id_at(tile + gridDim.x);
+        const float mag_a = a.na[myrow];
+        float acc[QF], mx[QF];
+#pragma unroll
+        for (int j = 0; j < QF; ++j) { acc[j] = -0.0f; mx[j] = 0.0f; }
+        if (__ballot(valid)) deep_list_walk<QF>(st, ldq, a.rows, a.ld, a.dim, myrow, qp, lane, acc, mx);
+#pragma unroll
+        for (int j = 0; j < QF; ++j) {
+            const uint64_t key = dist_key(finish_distance(acc[j], mx[j], mag_a, mag_b[j]), myrow);
+            const bool hit = valid && (uint32_t)j < me.nq && key < s_thr[j];
+            const uint32_t slot = wave_claim(hit, &s_cnt[j], lane);
+            if (hit && slot < kDeepScanBuf) buf[j][slot] = key;  // (always: 256 slots were free)
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QF; ++j)
+            if (s_cnt[j] > kDeepScanBuf - 256u) deep_scan_compact(buf[j], &s_cnt[j], &s_thr[j], k, t);
+        __syncthreads();  // (no wave claims a slot of the next tile while another still reads the counts)
+    }
+    const uint64_t lists = (uint64_t)gridDim.x + 1;
+    for (int j = 0; j < QF && (uint32_t)j < me.nq; ++j) {
+        deep_scan_compact(buf[j], &s_cnt[j], &s_thr[j], k, t);
+        const uint32_t n = s_cnt[j];
+        uint64_t* const slot0 = a.part + ((uint64_t)blockIdx.y * QF + j) * lists * k;
+        uint64_t* const dst = slot0 + ((uint64_t)blockIdx.x + 1) * k;
+        for (uint32_t i = t; i < k; i += 256) dst[i] = i < n ? buf[j][i] : kKeyNone;
+        if (blockIdx.x == 0)
+            for (uint32_t i = t; i < k; i += 256) slot0[i] = a.carry[(uint64_t)id[j] * k + i];
     }
 }
 
@@ -2966,10 +3105,25 @@ hipError_t launch_range_finish(const uint64_t* keys, const uint32_t* rcnt, uint3
 
 // ---- deep search -------------------------------------------------------------------------------
 hipError_t launch_deep_select(const DeepSelectArgs& a, hipStream_t s) {
-    if (!a.n_items || !a.k || a.k > kDeepMaxK || !a.keys || !a.out_idx || !a.out_dist || !a.out_count ||
+    if (!a.n_items || !a.k || a.k > kDeepMaxK || !a.keys ||
+        (!a.out_keys && (!a.out_idx || !a.out_dist || !a.out_count)) || (a.grp && !a.qf) ||
         (a.tau && (!a.ebound || !a.nb || !a.emit_cnt || !a.fail || !a.status)))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_deep_select, dim3(a.n_items), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_deep_scan_list(const DeepListArgs& a, uint32_t grid, hipStream_t s) {
+    if (!grid || !a.groups || a.groups > 65535 || !a.k || a.k > kDeepMaxK || a.ld == 0 || a.ld % 64 != 0 ||
+        a.dim > a.ld || !a.list || !a.grp || !a.qids || !a.part || !a.carry)
+        return hipErrorInvalidValue;
+    const dim3 g(grid, a.groups);
+    switch (a.qf) {
+        case 1: hipLaunchKernelGGL(k_deep_scan_list<1>, g, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_deep_scan_list<2>, g, dim3(256), 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_deep_scan_list<4>, g, dim3(256), 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -579,6 +579,11 @@ struct DeepSelectArgs {
     uint32_t cap;
     uint32_t* fail;
     uint32_t* status;
+    // The masked deep search, both nullable:
+    uint64_t* out_keys;         // [.][k]: query q's k keys, kKeyNone behind them, instead of its result row
+                                //   (with tau: of a certified query only)
+    const ScanGroupDesc* grp;   // item i is slot i % qf of group i / qf: only the slots below the
+    uint32_t qf;                //   group's nq count, the others write nothing
 };
 hipError_t launch_deep_select(const DeepSelectArgs& a, hipStream_t s);
 // The exact scan of the launch's nqf <= kDeepScanQF queries (ids in qids, device; entries up to the
@@ -598,6 +603,31 @@ struct DeepScanArgs {
     uint64_t* part;             // [nqf][grid][k]
 };
 hipError_t launch_deep_scan(const DeepScanArgs& a, uint32_t grid, hipStream_t s);
+// The deep exact scan over row lists (bsr_local_top_k_deep_masked).  Group y
+// (blockIdx.y) walks the grp[y].n_list ids at list + grp[y].off (local row ids, each < n, allowed
+// live rows only -- no mask and no tombstone is read) for the qf queries qids[y * qf ..] (qf one of
+// 1, 2, 4; the first grp[y].nq count, the rest are padding ids of the same mask).  A slot (y, j) is
+// (grid + 1) * k keys of part, part[((y * qf + j) * (grid + 1) + l) * k ..]: list 0 is a copy of the
+// query's carry, carry[id * k ..] (its k best keys of the segments scanned before, kKeyNone for
+// none), list 1 + b the k smallest keys workgroup b found, ascending, kKeyNone behind them -- what
+// launch_deep_select takes with stride = n_keys = (grid + 1) * k, and with out_keys = carry leaves
+// as the next segment's carry.  A padding slot is not written.  A query is in at most one group of
+// a launch.  grid: scan_grid_for(the launch's longest list).
+struct DeepListArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    const float* na;            // row magnitudes (read, never recomputed)
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const uint32_t* list;       // the launch's row lists
+    const ScanGroupDesc* grp;   // [groups]
+    uint32_t groups, qf;
+    const int32_t* qids;        // [groups][qf]
+    uint32_t k;
+    uint64_t* part;             // [groups][qf][grid + 1][k]
+    const uint64_t* carry;      // [nq][k]
+};
+hipError_t launch_deep_scan_list(const DeepListArgs& a, uint32_t grid, hipStream_t s);
 
 // ---- scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids) -----
 // The longest list the rerank sorts (a list is sorted in LDS, as a range result is).

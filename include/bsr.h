@@ -708,12 +708,58 @@ int bsr_local_rerank_ids(bsr_index* ix, const float* queries, uint32_t n_queries
  * n_exact_direct = queries sent to the scan by design; n_fallback = queries whose filtered result
  * could not be certified, an overflowed list included.  BSR_FLAG_PROFILE: the rescore and the
  * selection in rescore_ms, the scan rounds in scan_ms, the call in search_ms.
- * Out of scope: allow masks and groups with deep k; a multi-rank deep search (the per-rank lists
- * merge with bsr_global_top_k on the host as they are). */
+ * Out of scope: row groups (collapsed, capped, group searches) with deep k; a multi-rank deep search
+ * (the per-rank lists merge with bsr_global_top_k on the host as they are).  Allow masks:
+ * bsr_local_top_k_deep_masked below. */
 #define BSR_DEEP_MAX_K 1024u
 int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
                          uint64_t* out_idx, float* out_dist, /* [n_queries][k] */
                          uint32_t* out_count /* [n_queries] */);
+
+/* ---- Masked deep search: bsr_local_top_k_deep under allow masks -- "the 1000
+ * nearest chunks of tenant T".  allow, allow_words, n_masks, query_mask and mode are
+ * bsr_local_range_search_masked's: allow is [n_masks][allow_words] bitsets with allow_words =
+ * ceil(n / 64) (bit i & 63 of word i >> 6 of mask g: local row i is allowed for the queries of mask g),
+ * query_mask[q] names query q's mask, a null query_mask is legal only with n_masks == 1, a mask no
+ * query names is legal.  Every array is, independently, a host or a device pointer.
+ * With A_g the rows mask g allows that are not deleted: row q of out_idx / out_dist ([n_queries][k])
+ * holds out_count[q] = min(k, A_g) entries in (distance asc, global index asc) order with the
+ * reference's f32 distance bits, then (~0, +inf).  A_g = 0 is not an error.  1 <= k <=
+ * BSR_DEEP_MAX_K, not bounded by cfg.max_k.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; k = 0 or k > BSR_DEEP_MAX_K;
+ *      n_masks = 0; an unknown mode; with n_queries > 0 a null queries pointer, a null output or a
+ *      null allow; a null query_mask with n_masks > 1;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. BSR_E_INVALID: allow_words != ceil(n / 64);
+ *   4. n_queries = 0: BSR_OK;
+ *   5. BSR_E_INVALID: an entry of query_mask >= n_masks, found on the device before any mask is
+ *      indexed with it;
+ *   6. BSR_E_NONFINITE: a non-finite query, read from the batch's status words before any of the
+ *      caller's arrays, host or device, is written.
+ * How, per mask group: the list scan -- the allowed live rows of the mask as a row list (in chunks of
+ * BSR_MASK_LIST_BUDGET bytes), scanned exactly by a kernel that keeps k keys a query, a query's k
+ * best keys carried from chunk to chunk -- or the filter rung: the deep search's, with the sample
+ * threshold lowered to depth ks_m = ceil(max(8, ceil(k / 8)) * live rows / A_g), lists of 128 ks_m
+ * keys cut by the query's mask, and the same certification.  The rung is possible where
+ * the index can filter, ks_m <= 128 and the shard has more than 128 ks_m live rows; a query it does
+ * not certify takes the list scan of its own mask.  mode: BSR_MASK_LIST always scans the list,
+ * BSR_MASK_FILTER filters wherever possible, BSR_MASK_AUTO filters where possible unless the
+ * masked search's cost rule prefers the list.  The full-shard scan never runs.  Never graph-replayed.
+ * bsr_search_stats: search_path = BSR_PATH_DEEP, plus BSR_PATH_MASK_FILTER and / or
+ * BSR_PATH_MASK_LIST, plus BSR_PATH_MASK_GROUPS when a query_mask was given; never
+ * BSR_PATH_DEEP_SCAN.  n_exact_direct = queries sent to the list scan by design; n_fallback =
+ * queries whose filtered result could not be certified; n_emitted = the emitted keys before the cut;
+ * n_candidates = the list capacity (0: no group filtered).  BSR_FLAG_PROFILE: the list scans in
+ * scan_ms, the rescore and the selection in rescore_ms.
+ * Out of scope: row groups with deep k; a multi-rank masked deep search (merge per-rank lists with
+ * bsr_global_top_k). */
+int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                                const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                const uint32_t* query_mask, /* [n_queries], nullable with one mask */
+                                uint32_t mode,              /* BSR_MASK_AUTO / _LIST / _FILTER */
+                                uint64_t* out_idx, float* out_dist, /* [n_queries][k] */
+                                uint32_t* out_count /* [n_queries] */);
 
 /* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists, on the host.  Layout and
  * null rules are bsr_global_top_k's, with group[(l*n_queries+q)*k_in ..] the group ids beside idx
