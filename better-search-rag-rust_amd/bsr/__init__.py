@@ -1318,6 +1318,30 @@ def merge_top_k_lists_capped(idx, dist, group, count, top_k: int, per_group: int
     return oi, od, og, oc
 
 
+def merge_top_k_lists_device(idx, dist, count, top_k: int, out_idx, out_dist, out_count):
+    """bsr_global_top_k on caller buffers, every one a torch device tensor: idx (64-bit) / dist (f32)
+    [L,Q,k_in], count (32-bit) [L,Q] -> out_idx / out_dist [Q,top_k], out_count [Q], merged on the GPU
+    (L <= 64, k_in <= 1024, top_k <= 1024), bit for bit what merge_top_k_lists returns."""
+    L, Q, k_in = (int(x) for x in idx.shape)
+    if tuple(dist.shape) != (L, Q, k_in) or tuple(count.shape) != (L, Q):
+        raise BsrError(-1, "idx and dist are [L,Q,k_in], count [L,Q]")
+    _check(lib().bsr_global_top_k(_ptr(idx), _ptr(dist), _ptr(count), L, Q, k_in, int(top_k), _ptr(out_idx),
+                                  _ptr(out_dist), _ptr(out_count)))
+
+
+def merge_top_k_lists_capped_device(idx, dist, group, count, top_k: int, per_group: int, out_idx, out_dist,
+                                    out_group, out_count):
+    """bsr_global_top_k_capped on caller buffers, every one a torch device tensor: merge_top_k_lists_device's
+    shapes with group (32-bit) [L,Q,k_in] and out_group [Q,top_k] (or None), bit for bit what
+    merge_top_k_lists_capped returns."""
+    L, Q, k_in = (int(x) for x in idx.shape)
+    if tuple(dist.shape) != (L, Q, k_in) or tuple(group.shape) != (L, Q, k_in) or tuple(count.shape) != (L, Q):
+        raise BsrError(-1, "idx, dist and group are [L,Q,k_in], count [L,Q]")
+    _check(lib().bsr_global_top_k_capped(_ptr(idx), _ptr(dist), _ptr(group), _ptr(count), L, Q, k_in, int(top_k),
+                                         int(per_group), _ptr(out_idx), _ptr(out_dist), _ptr(out_group),
+                                         _ptr(out_count)))
+
+
 def gather_top_k_results(world, rank: int, local_top_k: List[Tuple[int, float]]):
     """src/mpi_helpers/metrics.rs:56-138: rank-order concatenation at the root, through the
     C ABI's exchange (bsr_gather_top_k) over `world` (a Comm, a torch.distributed group or

@@ -475,6 +475,39 @@ static bool device_merge_fits(uint32_t P, uint32_t k_in, uint32_t k) {
     return P <= 64 && (uint64_t)P * k_in <= kMergeMaxEntries && k <= 256;
 }
 
+// The streaming device merge (k_merge_wide) on the current device's null stream: plain with
+// per_group == 0, capped otherwise.
+static int device_merge_wide(const uint64_t* idx, const float* dist, const uint32_t* group, const uint32_t* count,
+                             uint32_t n_lists, uint32_t n_queries, uint32_t k_in, uint32_t k, uint32_t per_group,
+                             uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_count) {
+    if (n_lists > kWideMaxLists || k_in > kWideMaxKIn || k > kDeepMaxK)
+        return set_error(BSR_E_INVALID, "device merge: n_lists <= %u, k_in <= %u, k <= %u", kWideMaxLists,
+                         kWideMaxKIn, kDeepMaxK);
+    DevBuf nan_word;
+    BSR_TRY(nan_word.ensure(sizeof(uint32_t)));
+    BSR_HIP(hipMemset(nan_word.p, 0xff, sizeof(uint32_t)));
+    MergeWideArgs a{};
+    a.idx = idx;
+    a.dist = dist;
+    a.group = group;
+    a.cnt = count;
+    a.P = n_lists;
+    a.nq = n_queries;
+    a.k_in = k_in;
+    a.k = k;
+    a.per_group = per_group;
+    a.out_idx = out_idx;
+    a.out_dist = out_dist;
+    a.out_group = out_group;
+    a.out_count = out_count;
+    a.first_nan = nan_word.as<uint32_t>();
+    BSR_HIP(launch_merge_wide(a, nullptr));
+    uint32_t bad = 0;
+    BSR_HIP(hipMemcpy(&bad, nan_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (bad != ~0u) return set_error(BSR_E_NONFINITE, "NaN distance in query %u (the reference panics)", bad);
+    return BSR_OK;
+}
+
 static int global_top_k_impl(const uint64_t* idx, const float* dist, const uint32_t* count, uint32_t n_lists,
                              uint32_t n_queries, uint32_t k_in, uint32_t k, uint64_t* out_idx, float* out_dist,
                              uint32_t* out_count) {
@@ -488,9 +521,10 @@ static int global_top_k_impl(const uint64_t* idx, const float* dist, const uint3
         if (!is_device_ptr(out_idx) || !is_device_ptr(out_dist) || !is_device_ptr(out_count) ||
             (n_lists && k_in && (!is_device_ptr(idx) || !is_device_ptr(dist))))
             return set_error(BSR_E_INVALID, "device lists need device outputs");
+        // (the shapes k_merge_lists holds in LDS stay with it; the others stream through k_merge_wide)
         if (!device_merge_fits(n_lists, k_in, k))
-            return set_error(BSR_E_INVALID, "device merge: n_lists <= 64, n_lists * k_in <= %u, k <= 256",
-                             kMergeMaxEntries);
+            return device_merge_wide(idx, dist, nullptr, count, n_lists, n_queries, k_in, k, 0, out_idx, out_dist,
+                                     nullptr, out_count);
         DevBuf nan_word;
         BSR_TRY(nan_word.ensure(sizeof(uint32_t)));
         BSR_HIP(hipMemset(nan_word.p, 0xff, sizeof(uint32_t)));
@@ -525,10 +559,19 @@ static int global_top_k_capped_impl(const uint64_t* idx, const float* dist, cons
         return set_error(BSR_E_INVALID, "null argument");
     if (k == 0) return set_error(BSR_E_INVALID, "k must be >= 1");
     if (per_group == 0) return set_error(BSR_E_INVALID, "per_group must be >= 1");
-    if (is_device_ptr(count) || is_device_ptr(out_idx) || is_device_ptr(out_dist) || is_device_ptr(out_count) ||
+    if (is_device_ptr(count)) {
+        // every array in device memory: the merge kernel in capped mode (the plain merge's rule)
+        if (!is_device_ptr(out_idx) || !is_device_ptr(out_dist) || !is_device_ptr(out_count) ||
+            (out_group && !is_device_ptr(out_group)) ||
+            (entries && (!is_device_ptr(idx) || !is_device_ptr(dist) || !is_device_ptr(group))))
+            return set_error(BSR_E_INVALID, "device lists need device outputs");
+        return device_merge_wide(idx, dist, group, count, n_lists, n_queries, k_in, k, per_group, out_idx, out_dist,
+                                 out_group, out_count);
+    }
+    if (is_device_ptr(out_idx) || is_device_ptr(out_dist) || is_device_ptr(out_count) ||
         (out_group && is_device_ptr(out_group)) ||
         (entries && (is_device_ptr(idx) || is_device_ptr(dist) || is_device_ptr(group))))
-        return set_error(BSR_E_INVALID, "the capped merge takes host arrays only (copy device lists to the host first)");
+        return set_error(BSR_E_INVALID, "host counts need host lists and outputs (or pass every array on the device)");
     return merge_top_k_lists_capped(ListsView{idx, dist, count, n_lists, n_queries, k_in}, group, n_queries, k,
                                     per_group, out_idx, out_dist, out_group, out_count);
 }

@@ -2300,6 +2300,318 @@ __global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan_list(DeepListAr
 }
 
 // ------------------------------------------------------------------------------------
+// Wide merge (bsr_global_top_k / bsr_global_top_k_capped on device arrays): gathered
+// lists [P][nq][k_in] (counts [P][nq]) into [nq][k], P <= 64, k_in <= 1024, k <= kDeepMaxK -- up to
+// 65 536 entries a query, streamed from global memory (L2) and never held whole.
+// ------------------------------------------------------------------------------------
+// The order key of the entry in slot f = l * k_in + i (the order of f among the counted slots is the
+// order of the concatenation), most significant first:
+//   plain:  ord_f32(d + 0.0f) | f            (64 bits, b = 0)   -- the stable sort by distance
+//   capped: ord_f32(d + 0.0f) | index | f    (128 bits, a | b)  -- the stable sort by (distance, index)
+// Keys are distinct.  d + 0.0f turns -0.0 into +0.0 (they compare equal on the host) and is the only
+// arithmetic on a distance; the result row carries the entry's own bits.
+// Both sorted ascending in place as pairs (a, b): lds_sort_inplace's network.
+__device__ __forceinline__ void lds_sort_pairs(uint64_t* sa, uint64_t* sb, uint32_t n, uint32_t t) {
+    uint32_t P = 2;
+    while (P < n) P <<= 1;
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t e = t; e < P / 2; e += blockDim.x) {
+                const uint32_t lo = e & (j - 1), i = ((e - lo) << 1) | lo;
+                const uint32_t p = j == k >> 1 ? i + ((j - lo) << 1) - 1 : i + j;
+                if (p < n) {
+                    const uint64_t xa = sa[i], ya = sa[p], xb = sb[i], yb = sb[p];
+                    if (xa > ya || (xa == ya && xb > yb)) { sa[i] = ya; sa[p] = xa; sb[i] = yb; sb[p] = xb; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// One workgroup per query.  Windows: a most-significant-first radix select over the keys above the
+// last window's limit (11-bit digits, 9 at the end of a 64-bit word; k_deep_select's histogram)
+// finds the largest prefix of bins that fits kDeepSortKeys entries; when it holds fewer than the rows
+// still wanted, the bin that overflows becomes the live bucket and the next digit splits it.  The
+// window (limit_prev, limit] is compacted into LDS, sorted, its rows loaded beside it, and wave 0
+// walks it in order, 64 entries at a time: a lane whose index is not among the kept ones (LDS hash)
+// and, capped, whose group holds fewer than per_group kept rows (LDS hash of group -> count) is a
+// candidate; the candidates are settled in order by broadcasts (a kept lane turns away the later
+// lanes of its index and counts against the later lanes of its group), the kept lanes store their
+// rows and join the hashes.  Only kept rows are remembered, as the host does, so the walk is the
+// host's loop over the sorted entries, cut into windows.
+// A NaN distance: out_count[q] = 0, (~0, +inf) in every slot, the lowest such q in *first_nan.
+template <bool CAP>
+__global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_merge_wide(MergeWideArgs a) {
+    constexpr uint32_t BINS = 2048, PER = BINS / 256, HS = 2 * kDeepMaxK, WIN = kDeepSortKeys;
+    __shared__ uint64_t ka[WIN];
+    __shared__ uint64_t kb[CAP ? WIN : 1];
+    __shared__ uint64_t w_idx[WIN];
+    __shared__ float w_dist[WIN];
+    __shared__ uint32_t w_grp[CAP ? WIN : 1];
+    __shared__ uint64_t h_idx[HS];            // kept indices (~0: empty; an index of ~0 is s_ones)
+    __shared__ uint64_t g_key[CAP ? HS : 1];  // kept groups (a u32 in a u64, ~0: empty) ...
+    __shared__ uint32_t g_cnt[CAP ? HS : 1];  // ... and their kept rows
+    __shared__ uint32_t hist[BINS];
+    __shared__ uint32_t s_scan[256];
+    __shared__ uint32_t s_cnt[kWave];
+    __shared__ uint32_t s_n, s_bin, s_taken, s_out, s_nan, s_ones, s_total;
+    const uint64_t* __restrict__ idx = a.idx;
+    const float* __restrict__ dist = a.dist;
+    const uint32_t* __restrict__ group = a.group;
+    const uint32_t P = a.P, nq = a.nq, k_in = a.k_in, k = a.k, per_group = a.per_group;
+    uint64_t* __restrict__ out_idx = a.out_idx;
+    float* __restrict__ out_dist = a.out_dist;
+    uint32_t* __restrict__ out_group = a.out_group;
+    uint32_t* __restrict__ out_count = a.out_count;
+    uint32_t* const first_nan = a.first_nan;
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    const int lane = t & 63;
+
+    if (t < (uint32_t)kWave) s_cnt[t] = t < P ? min(a.cnt[(uint64_t)t * nq + q], k_in) : 0u;
+    for (uint32_t i = t; i < HS; i += 256) {
+        h_idx[i] = ~0ull;
+        if (CAP) {
+            g_key[i] = ~0ull;
+            g_cnt[i] = 0;
+        }
+    }
+    if (t == 0) s_out = s_nan = s_ones = 0;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t sum = 0;
+        for (uint32_t l = 0; l < P; ++l) sum += s_cnt[l];
+        s_total = sum;
+    }
+    __syncthreads();
+    const uint32_t total = s_total;
+    const uint32_t slots = P * k_in, slots_up = (slots + 255u) & ~255u;  // (every lane takes every trip: ballots)
+
+    // slot f's key and distance; false for a slot past its list's count
+    auto load = [&](uint32_t f, uint64_t& xa, uint64_t& xb, float& d) __attribute__((always_inline)) -> bool {
+        xa = xb = 0;
+        d = 0.0f;
+        if (f >= slots) return false;
+        const uint32_t l = f / k_in, i = f - l * k_in;
+        if (i >= s_cnt[l]) return false;
+        const uint64_t e = ((uint64_t)l * nq + q) * k_in + i;
+        d = dist[e];
+        const uint64_t o = ord_f32(d + 0.0f);  // (-0.0 + 0.0 = +0.0)
+        if (CAP) {
+            const uint64_t x = idx[e];
+            xa = (o << 32) | (x >> 32);
+            xb = (x << 32) | f;
+        } else {
+            xa = (o << 32) | f;
+        }
+        return true;
+    };
+    auto hash_slot = [](uint64_t x) -> uint32_t { return (uint32_t)((x * 0x9E3779B97F4A7C15ull) >> 40) & (HS - 1u); };
+
+    uint64_t lo_a = 0, lo_b = 0;  // the last window's limit: the keys up to it are walked
+    uint32_t walked = 0;
+    while (true) {
+        const uint32_t out = s_out;
+        if (out >= k || walked >= total) break;
+        const uint32_t need = min(k - out, total - walked);  // (>= 1) rows still wanted, entries left
+        uint64_t pa = 0, pb = 0, ma = 0, mb = 0;  // the live bucket: its `fixed` high bits, and their mask
+        uint64_t la = ~0ull, lb = ~0ull;          // the window's limit
+        uint32_t fixed = 0, below = 0;
+        while (true) {
+            const uint32_t used = fixed & 63u, width = used + 11u <= 64u ? 11u : 64u - used, sh = 64u - used - width;
+            const bool hi_word = fixed < 64u;
+            for (uint32_t i = t; i < BINS; i += 256) hist[i] = 0;
+            __syncthreads();
+            for (uint32_t i = t; i < slots_up; i += 256) {
+                uint64_t xa, xb;
+                float d;
+                bool in = load(i, xa, xb, d);
+                if (walked == 0 && fixed == 0 && in && d != d) s_nan = 1;
+                in = in && (walked == 0 || xa > lo_a || (xa == lo_a && xb > lo_b)) && (xa & ma) == pa &&
+                     (xb & mb) == pb;
+                const uint32_t bin = (uint32_t)((hi_word ? xa : xb) >> sh) & ((1u << width) - 1u);
+                const uint64_t m0 = __ballot(in);
+                if (m0) {  // the lanes that agree with the first: one add
+                    const int first = __builtin_ctzll(m0);
+                    const uint32_t b0 = (uint32_t)__shfl((int)bin, first, kWave);
+                    const uint64_t same = __ballot(in && bin == b0);
+                    if (lane == first) atomicAdd(&hist[b0], (uint32_t)__popcll(same));
+                    in = in && bin != b0;
+                }
+                if (in) atomicAdd(&hist[bin], 1u);
+            }
+            __syncthreads();
+            if (walked == 0 && fixed == 0 && s_nan) {  // (uniform: read behind the barrier)
+                for (uint32_t i = t; i < k; i += 256) {
+                    out_idx[(uint64_t)q * k + i] = ~0ull;
+                    out_dist[(uint64_t)q * k + i] = INFINITY;
+                    if (CAP && out_group) out_group[(uint64_t)q * k + i] = ~0u;
+                }
+                if (t == 0) {
+                    out_count[q] = 0;
+                    atomicMin(first_nan, q);
+                }
+                return;
+            }
+            uint32_t mine = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < PER; ++b) mine += hist[t * PER + b];
+            s_scan[t] = mine;
+            __syncthreads();
+            for (uint32_t s = 1; s < 256; s <<= 1) {  // (inclusive scan)
+                const uint32_t v = t >= s ? s_scan[t - s] : 0u;
+                __syncthreads();
+                s_scan[t] += v;
+                __syncthreads();
+            }
+            if (below + s_scan[255] <= WIN || fixed == (CAP ? 128u : 64u)) {  // the whole bucket fits
+                la = pa | ~ma;
+                lb = pb | ~mb;
+                break;
+            }
+            const uint32_t incl = below + s_scan[t], excl = incl - mine;
+            if (excl <= WIN && incl > WIN) {  // (one thread: the scan is monotone) the bin that overflows
+                uint32_t run = excl, b = 0;
+                while (run + hist[t * PER + b] <= WIN) run += hist[t * PER + b++];
+                s_bin = t * PER + b;
+                s_taken = run;
+            }
+            __syncthreads();
+            const uint64_t ob = s_bin;
+            const uint32_t taken = s_taken;
+            if (taken >= need) {  // (ob >= 1: below < need) the bins before it are the window
+                const uint64_t end = ((ob - 1) << sh) | ((1ull << sh) - 1ull);
+                la = hi_word ? pa | end : pa;
+                lb = hi_word ? ~0ull : pb | end;
+                break;
+            }
+            if (hi_word) {
+                pa |= ob << sh;
+                ma |= ((1ull << width) - 1ull) << sh;
+            } else {
+                pb |= ob << sh;
+                mb |= ((1ull << width) - 1ull) << sh;
+            }
+            fixed += width;
+            below = taken;
+        }
+        if (t == 0) s_n = 0;
+        __syncthreads();
+        for (uint32_t i = t; i < slots_up; i += 256) {
+            uint64_t xa, xb;
+            float d;
+            bool in = load(i, xa, xb, d);
+            in = in && (walked == 0 || xa > lo_a || (xa == lo_a && xb > lo_b)) && (xa < la || (xa == la && xb <= lb));
+            const uint32_t slot = wave_claim(in, &s_n, lane);
+            if (in && slot < WIN) {
+                ka[slot] = xa;
+                if (CAP) kb[slot] = xb;
+            }
+        }
+        __syncthreads();
+        const uint32_t n = s_n < WIN ? s_n : WIN;
+        if (n == 0) break;
+        if (CAP) lds_sort_pairs(ka, kb, n, t);
+        else lds_sort_inplace(ka, n, t);
+        for (uint32_t j = t; j < n; j += 256) {  // the window's rows, in order
+            const uint32_t f = (uint32_t)(CAP ? kb[j] : ka[j]), l = f / k_in, i = f - l * k_in;
+            const uint64_t e = ((uint64_t)l * nq + q) * k_in + i;
+            w_idx[j] = idx[e];
+            w_dist[j] = dist[e];
+            if (CAP) w_grp[j] = group[e];
+        }
+        __syncthreads();
+        if (t < (uint32_t)kWave) {
+            volatile uint64_t* const vh = h_idx;
+            volatile uint64_t* const vg = g_key;
+            volatile uint32_t* const vc = g_cnt;
+            volatile uint32_t* const vones = &s_ones;
+            uint32_t o = out;
+            for (uint32_t base = 0; base < n && o < k; base += kWave) {
+                const uint32_t j = base + lane;
+                const bool have = j < n;
+                const uint64_t x = have ? w_idx[j] : 0ull;
+                const uint32_t g = CAP && have ? w_grp[j] : 0u;
+                bool cand = have;
+                if (cand) {
+                    if (x == ~0ull) {
+                        cand = *vones == 0;
+                    } else {
+                        for (uint32_t sl = hash_slot(x);; sl = (sl + 1) & (HS - 1u)) {
+                            const uint64_t v = vh[sl];
+                            if (v == x) cand = false;
+                            if (v == x || v == ~0ull) break;
+                        }
+                    }
+                }
+                uint32_t gc = 0;  // kept rows of the lane's group, the earlier lanes of the batch included
+                if (CAP && cand) {
+                    for (uint32_t sl = hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
+                        const uint64_t v = vg[sl];
+                        if (v == g) gc = vc[sl];
+                        if (v == g || v == ~0ull) break;
+                    }
+                    cand = gc < per_group;
+                }
+                uint64_t m = __ballot(cand);
+                uint32_t nb = 0;  // kept lanes of the batch before this one
+                bool keep = false;
+                while (m) {
+                    const int j0 = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const bool ok = cand && (!CAP || gc < per_group) && o + nb < k;
+                    if (!__shfl((int)ok, j0, kWave)) continue;  // (uniform)
+                    const uint64_t xj = shfl64(x, j0);
+                    const uint32_t gj = CAP ? (uint32_t)__shfl((int)g, j0, kWave) : 0u;
+                    if (lane == j0) keep = true;
+                    if (lane > j0) {
+                        ++nb;
+                        if (x == xj) cand = false;
+                        if (CAP && g == gj) ++gc;
+                    }
+                }
+                if (keep) {
+                    const uint64_t p = (uint64_t)q * k + o + nb;
+                    out_idx[p] = x;
+                    out_dist[p] = w_dist[j];
+                    if (CAP && out_group) out_group[p] = g;
+                    if (x == ~0ull) {
+                        *vones = 1;
+                    } else {
+                        for (uint32_t sl = hash_slot(x);; sl = (sl + 1) & (HS - 1u))
+                            if (atomicCAS(reinterpret_cast<unsigned long long*>(&h_idx[sl]), ~0ull,
+                                          (unsigned long long)x) == ~0ull)
+                                break;
+                    }
+                    if (CAP)
+                        for (uint32_t sl = hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
+                            const uint64_t prev = atomicCAS(reinterpret_cast<unsigned long long*>(&g_key[sl]), ~0ull,
+                                                            (unsigned long long)g);
+                            if (prev == ~0ull || prev == g) {
+                                atomicAdd(&g_cnt[sl], 1u);
+                                break;
+                            }
+                        }
+                }
+                o += (uint32_t)__popcll(__ballot(keep));
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (the next batch reads the hashes)
+            }
+            if (lane == 0) s_out = o;
+        }
+        __syncthreads();
+        lo_a = la;
+        lo_b = lb;
+        walked += n;
+    }
+    const uint32_t out = s_out;
+    for (uint32_t i = out + t; i < k; i += 256) {
+        out_idx[(uint64_t)q * k + i] = ~0ull;
+        out_dist[(uint64_t)q * k + i] = INFINITY;
+        if (CAP && out_group) out_group[(uint64_t)q * k + i] = ~0u;
+    }
+    if (t == 0) out_count[q] = out;
+}
+
+// ------------------------------------------------------------------------------------
 // Scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids): the
 // reference's distance of every id of a per-query list, aligned with the list.
 // ------------------------------------------------------------------------------------
@@ -3110,6 +3422,16 @@ hipError_t launch_deep_select(const DeepSelectArgs& a, hipStream_t s) {
         (a.tau && (!a.ebound || !a.nb || !a.emit_cnt || !a.fail || !a.status)))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_deep_select, dim3(a.n_items), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_wide(const MergeWideArgs& a, hipStream_t s) {
+    if (!a.nq || !a.k || a.k > kDeepMaxK || a.P > kWideMaxLists || a.k_in > kWideMaxKIn || !a.cnt || !a.out_idx ||
+        !a.out_dist || !a.out_count || !a.first_nan ||
+        (a.P && a.k_in && (!a.idx || !a.dist || (a.per_group && !a.group))))
+        return hipErrorInvalidValue;
+    if (a.per_group) hipLaunchKernelGGL(k_merge_wide<true>, dim3(a.nq), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_merge_wide<false>, dim3(a.nq), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -586,6 +586,31 @@ struct DeepSelectArgs {
     uint32_t qf;                //   group's nq count, the others write nothing
 };
 hipError_t launch_deep_select(const DeepSelectArgs& a, hipStream_t s);
+
+// ---- wide merge (bsr_global_top_k / bsr_global_top_k_capped on device arrays) ----
+// The merge of gathered lists [P][nq][k_in] (counts [P][nq], clamped to k_in) into [nq][k] beyond
+// launch_merge_lists' limits: P <= kWideMaxLists, k_in <= kWideMaxKIn, 1 <= k <= kDeepMaxK; the
+// lists may be unsorted and may overlap.  One workgroup per query streams the entries.
+// per_group == 0 (plain): merge_top_k_lists' result bit for bit -- rank-order concatenation, stable
+// sort by distance, first occurrence of an index, the first k.
+// per_group >= 1 (capped; group beside idx and dist, out_group nullable): merge_top_k_lists_capped's -- (distance,
+// index) order, deduplicated by index, a row kept while fewer than per_group kept rows hold its group.
+// (~0, +inf[, ~0u]) behind out_count[q].  *first_nan must hold ~0 before the launch; afterwards the
+// lowest query with a NaN distance (its row: count 0, every slot padded).
+constexpr uint32_t kWideMaxLists = 64, kWideMaxKIn = 1024;
+struct MergeWideArgs {
+    const uint64_t* idx;
+    const float* dist;
+    const uint32_t* group;
+    const uint32_t* cnt;
+    uint32_t P, nq, k_in, k, per_group;
+    uint64_t* out_idx;
+    float* out_dist;
+    uint32_t* out_group;
+    uint32_t* out_count;
+    uint32_t* first_nan;
+};
+hipError_t launch_merge_wide(const MergeWideArgs& a, hipStream_t s);
 // The exact scan of the launch's nqf <= kDeepScanQF queries (ids in qids, device; entries up to the
 // template width -- 1, 2 or 4 -- must be valid ids, those past nqf count nothing): workgroup b
 // leaves the k smallest keys of the live rows of its tiles, ascending, kKeyNone behind them, in

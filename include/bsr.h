@@ -511,7 +511,7 @@ int bsr_local_top_k_mmr(bsr_index* ix, const float* queries, uint32_t n_queries,
  * replay.
  * More than one row per group ("at most m per document") is bsr_local_top_k_capped, below; a
  * multi-rank collapsed search is this call on every rank with out_group, bsr_allgather_bytes and
- * bsr_global_top_k_capped with per_group = 1.
+ * bsr_global_top_k_capped with per_group = 1 (on the GPU when every array is in device memory).
  * Out of scope: group ids stored on the index; a parallel entry point that runs those collectives
  * itself; a list-driven scan for sparse masks; group sizes or counts in the output. */
 int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_queries,
@@ -559,7 +559,8 @@ int bsr_local_top_k_collapsed(bsr_index* ix, const float* queries, uint32_t n_qu
  * fields are the candidate search's, and graph_replay is 1 wherever bsr_local_top_k(n_queries,
  * fetch_k) would replay.
  * A multi-rank capped search: this call on every rank with its own row_group (global group ids)
- * and out_group, bsr_allgather_bytes of the four outputs, bsr_global_top_k_capped.
+ * and out_group, bsr_allgather_bytes of the four outputs, bsr_global_top_k_capped (host arrays on
+ * the host, device arrays on the GPU).
  * "k groups with up to m rows each" is bsr_local_top_groups, below.
  * Out of scope: a per-query per_group; group ids stored on the
  * index; a list-driven scan for sparse masks; counts per group in the output. */
@@ -708,8 +709,11 @@ int bsr_local_rerank_ids(bsr_index* ix, const float* queries, uint32_t n_queries
  * n_exact_direct = queries sent to the scan by design; n_fallback = queries whose filtered result
  * could not be certified, an overflowed list included.  BSR_FLAG_PROFILE: the rescore and the
  * selection in rescore_ms, the scan rounds in scan_ms, the call in search_ms.
- * Out of scope: row groups (collapsed, capped, group searches) with deep k; a multi-rank deep search
- * (the per-rank lists merge with bsr_global_top_k on the host as they are).  Allow masks:
+ * A multi-rank deep search: this call on every rank with device outputs, bsr_allgather_bytes of the
+ * three outputs on device buffers, bsr_global_top_k on the gathered device arrays (host arrays
+ * merge on the host).
+ * Out of scope: row groups (collapsed, capped, group searches) with deep k; a parallel entry point
+ * that runs those collectives itself.  Allow masks:
  * bsr_local_top_k_deep_masked below. */
 #define BSR_DEEP_MAX_K 1024u
 int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
@@ -752,8 +756,9 @@ int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries
  * queries whose filtered result could not be certified; n_emitted = the emitted keys before the cut;
  * n_candidates = the list capacity (0: no group filtered).  BSR_FLAG_PROFILE: the list scans in
  * scan_ms, the rescore and the selection in rescore_ms.
- * Out of scope: row groups with deep k; a multi-rank masked deep search (merge per-rank lists with
- * bsr_global_top_k). */
+ * A multi-rank masked deep search: as bsr_local_top_k_deep's (device lists merge on the GPU with
+ * bsr_global_top_k).
+ * Out of scope: row groups with deep k. */
 int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
                                 const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                                 const uint32_t* query_mask, /* [n_queries], nullable with one mask */
@@ -761,16 +766,21 @@ int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_
                                 uint64_t* out_idx, float* out_dist, /* [n_queries][k] */
                                 uint32_t* out_count /* [n_queries] */);
 
-/* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists, on the host.  Layout and
+/* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists.  Layout and
  * null rules are bsr_global_top_k's, with group[(l*n_queries+q)*k_in ..] the group ids beside idx
  * and dist (global group ids: a group may span ranks) and out_group [n_queries][k] (nullable).
  * Per query: the lists concatenated, ordered by (distance asc, index asc), deduplicated by index; a
  * row is kept while fewer than per_group kept rows hold its group; the first k kept rows.  Entries
  * past out_count[q] are (~0, +inf, ~0u).  Over per-rank results of bsr_local_top_k_capped(k,
  * per_group) (k_in = k) this is the capped search over the whole store.
+ * Host arrays: merged on the host.  Every array in device memory (a non-null out_group included;
+ * n_lists <= 64, k_in <= 1024, k <= BSR_DEEP_MAX_K): merged on the GPU by the streaming merge
+ * kernel, one workgroup per query, on the current device's null stream, with the host merge's
+ * result bit for bit.
  * BSR_E_INVALID: a null array (group included, when there are entries), k = 0, per_group = 0 (there
- * is no upper cap here), any array in device memory (a device merge is out of scope).
- * BSR_E_NONFINITE: a NaN distance. */
+ * is no upper cap here), host and device arrays mixed, device arrays beyond the limits above.
+ * BSR_E_NONFINITE: a NaN distance (device arrays: the lowest such query is named, its row is
+ * count 0 and padding). */
 int bsr_global_top_k_capped(const uint64_t* idx, const float* dist, const uint32_t* group, const uint32_t* count,
                             uint32_t n_lists, uint32_t n_queries, uint32_t k_in, uint32_t k, uint32_t per_group,
                             uint64_t* out_idx, float* out_dist, uint32_t* out_group /* nullable */,
@@ -779,9 +789,13 @@ int bsr_global_top_k_capped(const uint64_t* idx, const float* dist, const uint32
 /* ---- a-5: compute_global_top_k over n_lists per-rank lists, for n_queries queries.
  * Input list l of query q: idx[(l*n_queries+q)*k_in ..] with count[l*n_queries+q]
  * entries.  Rank-order concatenation + stable sort by distance + dedupe, keep k.
- * Host arrays: merged on the host (threads over queries).  Every array in device memory
- * (n_lists <= 64, n_lists * k_in <= 1024, k <= 256): merged on the GPU, one wave per query
- * (the RCCL path's root merge).  Rows past out_count[q] are (~0, +inf). -------------- */
+ * Host arrays: merged on the host (threads over queries).  Every array in device memory:
+ * merged on the GPU, on the current device's null stream -- n_lists <= 64, n_lists * k_in <=
+ * 1024 and k <= 256 with one wave per query (the RCCL path's root merge), every other shape
+ * within n_lists <= 64, k_in <= 1024, k <= BSR_DEEP_MAX_K with one workgroup per query that
+ * streams the entries (the lists of bsr_local_top_k_deep on every rank); beyond
+ * that, and for host and device arrays mixed, BSR_E_INVALID.  Either way the result is the host
+ * merge's bit for bit.  Rows past out_count[q] are (~0, +inf). -------------- */
 int bsr_global_top_k(const uint64_t* idx, const float* dist, const uint32_t* count,
                      uint32_t n_lists, uint32_t n_queries, uint32_t k_in, uint32_t k,
                      uint64_t* out_idx, float* out_dist, uint32_t* out_count);
