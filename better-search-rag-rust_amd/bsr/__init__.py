@@ -172,6 +172,7 @@ def lib() -> ctypes.CDLL:
         "bsr_local_rerank_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_deep": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_deep_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
+        "bsr_local_top_k_deep_capped": (ctypes.c_int, [_P, _P, u32, u32, u32, _P, u64, u32, _P, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_global_top_k_capped": (ctypes.c_int, [_P, _P, _P, _P, u32, u32, u32, u32, u32, _P, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
@@ -198,7 +199,8 @@ def lib() -> ctypes.CDLL:
                 "bsr_index_deleted_mask", "bsr_local_top_k_masked_groups", "bsr_index_update", "bsr_index_compact", "bsr_local_range_search",
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
                 "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids",
-                "bsr_local_top_groups", "bsr_local_top_k_deep", "bsr_local_top_k_deep_masked"}
+                "bsr_local_top_groups", "bsr_local_top_k_deep", "bsr_local_top_k_deep_masked",
+                "bsr_local_top_k_deep_capped"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -644,6 +646,43 @@ class Index:
         _check(lib().bsr_local_top_k_deep_masked(self._h, _ptr(queries), nq, k, _ptr(allow_words), int(shape[-1]),
                                                  n_masks, _ptr(query_mask), _mask_mode(mask_mode), _ptr(out_idx),
                                                  _ptr(out_dist), _ptr(out_count)))
+
+    def deep_capped_search(self, queries, k: int, row_group, per_group: int = 1, n_groups=None,
+                           return_groups: bool = False):
+        """capped_search for k up to BSR_DEEP_MAX_K (bsr_local_top_k_deep_capped), not bounded by
+        max_k -> (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32[, group [Q,k] u32]).  row_group and
+        n_groups: as capped_search's.  Row q holds the first k live rows in (distance asc, index asc)
+        order that have fewer than per_group rows of their group ahead of them; per_group = 1 (the
+        default) is the k nearest distinct groups.  No fetch_k and no masks."""
+        per_group = int(per_group)
+        if per_group < 1 or per_group > BSR_CAP_MAX_PER_GROUP:
+            raise BsrError(-1, f"per_group={per_group} outside 1 <= per_group <= {BSR_CAP_MAX_PER_GROUP}")
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
+        nq, k = q.shape[0], int(k)
+        if k < 1 or k > BSR_DEEP_MAX_K:
+            raise BsrError(-1, f"k={k} outside [1, {BSR_DEEP_MAX_K}]")
+        rg, n_rg, ng = self._row_groups(row_group, n_groups)
+        oi = np.empty((nq, k), np.uint64)
+        od = np.empty((nq, k), np.float32)
+        oc = np.empty(nq, np.uint32)
+        og = np.empty((nq, k), np.uint32) if return_groups else None
+        _check(lib().bsr_local_top_k_deep_capped(self._h, _ptr(q), nq, k, per_group, _ptr(rg), n_rg, ng, _ptr(oi),
+                                                 _ptr(od), _ptr(og), _ptr(oc)))
+        return (oi, od, oc, og) if return_groups else (oi, od, oc)
+
+    def deep_capped_search_device(self, queries, nq: int, k: int, per_group: int, row_group, n_groups: int, out_idx,
+                                  out_dist, out_count, out_group=None):
+        """Zero-copy variant of deep_capped_search on caller buffers (torch tensors, numpy arrays or
+        raw pointers, each host or device): queries [nq][dim] f32, row_group [n] 32-bit group ids,
+        out_idx / out_dist / out_group (optional) [nq][k], out_count [nq]."""
+        n_rg = int(row_group.numel()) if hasattr(row_group, "numel") else int(row_group.size)
+        _check(lib().bsr_local_top_k_deep_capped(self._h, _ptr(queries), nq, k, int(per_group), _ptr(row_group), n_rg,
+                                                 int(n_groups), _ptr(out_idx), _ptr(out_dist), _ptr(out_group),
+                                                 _ptr(out_count)))
 
     def range_search(self, queries, radius, max_results: int = 256, allow_mask=None, allow_ids=None,
                      allow_masks=None, query_mask=None, mask_mode="auto"):

@@ -3389,6 +3389,241 @@ int bsr_local_top_k_capped_impl(bsr_index* ix, const float* queries, uint32_t nq
 }
 
 // ---------------------------------------------------------------------------------------
+// Deep capped search (bsr_local_top_k_deep_capped): deep_search_device's filter rung
+// with the capped selection over the rescored keys in the place of the plain one, and
+// group_search_device's capped group scan (its tables, rounds and budget) for the queries the
+// selection leaves, the k <= 1024 smallest table keys taken by launch_deep_select.
+// ---------------------------------------------------------------------------------------
+int bsr_index::deep_capped_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t per_group,
+                                         const uint32_t* row_group, uint32_t n_groups, uint64_t* out_idx,
+                                         float* out_dist, uint32_t* out_group, uint32_t* out_count) {
+    bsr_index* ix = this;
+    BSR_TRY(check_batch(ix, 1));  // (loaded; k has its own bound, checked by the entry point)
+    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_DEEP | BSR_PATH_CAP));
+    if (nq == 0) return BSR_OK;
+
+    // (table entries per (query, group); m_eff * n_groups fits 32 bits, the entry point checked it)
+    const uint32_t m_eff = std::min(per_group, k);
+    const uint32_t n_entries = m_eff * n_groups;
+    const uint32_t ks = deep_ks(k), cap = deep_cap(k);
+    const uint32_t qpad = qpad_for(nq);
+    const size_t nk = (size_t)nq * k;
+    const uint64_t live = live_rows();
+    // The filter rung under deep_search_device's condition; else every query is scanned.
+    const bool use_filter = approx_ok && live > cap;
+    // Every buffer but the scan's tables first.
+    BSR_TRY(query_buffers(ix, nq, qpad, 1));
+    BSR_TRY(col_flag.ensure(2 * sizeof(uint32_t)));
+    BSR_TRY(col_qids.ensure((size_t)nq * kScanQF * sizeof(int32_t)));
+    BSR_TRY(col_keys.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(col_idx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(col_dist.ensure(nk * sizeof(float)));
+    BSR_TRY(col_group.ensure(nk * sizeof(uint32_t)));
+    BSR_TRY(col_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    if (use_filter) {
+        BSR_TRY(deep_keys.ensure((size_t)nq * cap * sizeof(uint64_t)));
+        BSR_TRY(deep_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+        BSR_TRY(deep_rad.ensure((size_t)nq * sizeof(float)));
+    }
+    uint64_t* const di = col_idx.as<uint64_t>();
+    float* const dd = col_dist.as<float>();
+    uint32_t* const dg = col_group.as<uint32_t>();
+    uint32_t* const dc = col_cnt.as<uint32_t>();
+    // The groups on the device and their check, before anything indexes a table or a hash with one.
+    uint32_t* const flag = col_flag.as<uint32_t>();
+    const uint32_t* dgrp = nullptr;
+    if (n) {
+        BSR_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(uint32_t), stream));
+        BSR_TRY(on_device(ix, col_grp, row_group, (size_t)n * sizeof(uint32_t), is_device_ptr(row_group), &dgrp));
+        BSR_HIP(launch_group_check(dgrp, n, n_groups, flag, stream));
+        uint32_t bad = 0;
+        BSR_HIP(hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, stream));
+        BSR_HIP(hipStreamSynchronize(stream));
+        if (bad) return set_error(BSR_E_INVALID, "a row_group entry is >= n_groups = %u", n_groups);
+    }
+
+    ev_begin(ix, ev_total);
+    const float* qsrc = nullptr;
+    BSR_TRY(stage_queries(ix, queries, nq, &qsrc));
+    BSR_HIP(launch_query_prep(query_prep_args(ix, qsrc, nq, qpad, use_filter), stream));
+    if (use_filter) {
+        // deep_search_device's sequence: tau0 = the ks-th best sampled score, the emit pass over lists
+        // of cap keys, the reference distance of every emitted live row (a radius of +inf) ...
+        BSR_TRY(sample_pass(ix, nq, qpad, k, nullptr, ks, cap));
+        BSR_TRY(emit_pass(ix, nq, qpad, k, cap));
+        BSR_HIP(hipMemsetAsync(deep_cnt.p, 0, (size_t)nq * sizeof(uint32_t), stream));
+        BSR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(deep_rad.p), 0x7f800000, nq, stream));
+        RangeArgs ra{};
+        ra.rows = rows.as<float>();
+        ra.ld = ld;
+        ra.dim = dim;
+        ra.n = n;
+        ra.na = na.as<float>();
+        ra.qf32 = qf32.as<float>();
+        ra.nb = nb.as<float>();
+        ra.radius = deep_rad.as<float>();
+        ra.dead = dead_bits();
+        ra.keys = deep_keys.as<uint64_t>();
+        ra.rcnt = deep_cnt.as<uint32_t>();
+        ra.cap = cap;
+        ra.nq = nq;
+        ra.cand = cand.as<uint64_t>();
+        ra.cnt = cnt.as<uint32_t>();
+        ra.scan_list = fail.as<uint32_t>();
+        ra.status = d_status;
+        ev_begin(ix, ev_rescore);
+        BSR_HIP(launch_range_rescore(ra, stream));
+        // ... and the capped walk of the keys below the exclusion bound (it lists every query it does
+        // not certify, the overflowed ones the rescore listed included: its list starts empty)
+        BSR_HIP(hipMemsetAsync(d_status + kStFail, 0, sizeof(uint32_t), stream));
+        DeepCapSelectArgs se{};
+        se.keys = ra.keys;
+        se.kcnt = ra.rcnt;
+        se.cap = cap;
+        se.nq = nq;
+        se.k = k;
+        se.per_group = m_eff;
+        se.offset = global_offset;
+        se.row_group = dgrp;
+        se.out_idx = di;
+        se.out_dist = dd;
+        se.out_group = dg;
+        se.out_count = dc;
+        se.tau = tau.as<float>();
+        se.ebound = ebound.as<float>();
+        se.nb = nb.as<float>();
+        se.emit_cnt = ra.cnt;
+        se.fail = fail.as<uint32_t>();
+        se.status = d_status;
+        BSR_HIP(launch_deep_cap_select(se, stream));
+        ev_end(ix, ev_rescore);
+    } else if (live == 0) {
+        // an empty shard, or one whose every row is deleted: no key, every row padding, every count 0
+        DeepSelectArgs se{};
+        se.keys = di;  // (never read: n_keys = 0)
+        se.n_items = nq;
+        se.k = k;
+        se.out_idx = di;
+        se.out_dist = dd;
+        se.out_count = dc;
+        BSR_HIP(launch_deep_select(se, stream));
+        BSR_HIP(hipMemsetAsync(dg, 0xff, nk * sizeof(uint32_t), stream));
+    }
+    stats.n_candidates = cap;
+    // The one status readback: the query flags and the number of queries left to the scan.
+    BSR_HIP(hipMemcpyAsync(h_res, d_status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    BSR_HIP(stream_wait(stream));
+    BSR_TRY(check_queries(ix, nq));
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(h_res);
+    uint32_t nscan = 0;
+    if (use_filter) {
+        stats.n_emitted = st[kStEmitted];
+        nscan = st[kStFail];
+        if (nscan) {
+            // queries the filter cannot serve (by design), and queries the walk left uncertified
+            h_fail.resize(nscan);
+            h_qflags.resize(nq);
+            h_deep_eb.resize(nq);
+            BSR_HIP(hipMemcpy(h_fail.data(), fail.p, (size_t)nscan * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            BSR_HIP(hipMemcpy(h_qflags.data(), qflags.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            BSR_HIP(hipMemcpy(h_deep_eb.data(), ebound.p, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
+            std::sort(h_fail.begin(), h_fail.end());
+            for (uint32_t q : h_fail) {
+                if ((h_qflags[q] & kQueryNoApprox) || !(h_deep_eb[q] < 1.0f)) ++stats.n_exact_direct;
+                else ++stats.n_fallback;
+            }
+        }
+    } else if (live > 0) {
+        nscan = nq;
+        stats.n_exact_direct = nq;
+        h_fail.resize(nq);
+        for (uint32_t q = 0; q < nq; ++q) h_fail[q] = q;
+    }
+    if (nscan) {
+        // The capped group scan in group_search_device's rounds: as many queries as the table budget
+        // holds, the k smallest of a table's m_eff * n_groups keys by the deep selection (it streams
+        // any number of keys and skips the empty entries), then the rows with their groups.
+        stats.search_path |= BSR_PATH_CAP_SCAN;
+        const uint64_t table = 8ull * n_entries;
+        const uint64_t budget = env_bytes("BSR_COLLAPSE_TABLE_BUDGET", 256ull << 20);
+        const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({kScanQF, budget / table, nscan}));
+        const uint32_t rounds = (nscan + per - 1) / per;
+        const std::vector<int32_t> padded = padded_scan_ids(h_fail, nscan, per);
+        BSR_TRY(col_best.ensure((size_t)per * table));
+        BSR_HIP(hipMemcpyAsync(col_qids.p, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                               stream));
+        BSR_HIP(hipStreamSynchronize(stream));  // (padded is read by the copy)
+        CollapseScanArgs sa{};
+        sa.rows = rows.as<float>();
+        sa.ld = ld;
+        sa.dim = dim;
+        sa.n = n;
+        sa.na = na.as<float>();
+        sa.qf32 = qf32.as<float>();
+        sa.nb = nb.as<float>();
+        sa.dead = dead_bits();
+        sa.row_group = dgrp;
+        sa.n_groups = n_groups;
+        sa.best = col_best.as<uint64_t>();
+        DeepSelectArgs se{};
+        se.keys = sa.best;
+        se.stride = n_entries;
+        se.n_keys = n_entries;
+        se.k = k;
+        se.out_keys = col_keys.as<uint64_t>();
+        const uint32_t grid = scan_grid_for(n);
+        ev_begin(ix, ev_scan, 1);
+        for (uint32_t r = 0; r < rounds; ++r) {
+            const uint32_t nr = std::min(per, nscan - r * per);
+            const int32_t* qid = col_qids.as<int32_t>() + (size_t)r * kScanQF;
+            sa.qids = se.qids = qid;
+            sa.nqf = se.n_items = nr;
+            BSR_HIP(hipMemsetAsync(col_best.p, 0xff, (size_t)nr * table, stream));
+            if (m_eff > 1) BSR_HIP(launch_cap_scan(CapScanArgs{sa, m_eff}, grid, stream));
+            else BSR_HIP(launch_collapse_scan(sa, grid, stream));
+            BSR_HIP(launch_deep_select(se, stream));
+            BSR_HIP(launch_deep_cap_finish(se.out_keys, qid, nr, k, global_offset, dgrp, di, dd, dg, dc, stream));
+        }
+        ev_end(ix, ev_scan);
+    }
+    ev_end(ix, ev_total);
+    // Every row was written to the index's own buffers -- the status is read before any of the
+    // caller's arrays, host or device, is written -- and goes out with one copy each.
+    BSR_HIP(hipMemcpyAsync(out_idx, di, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+    BSR_HIP(hipMemcpyAsync(out_dist, dd, nk * sizeof(float), hipMemcpyDefault, stream));
+    if (out_group) BSR_HIP(hipMemcpyAsync(out_group, dg, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+    BSR_HIP(hipMemcpyAsync(out_count, dc, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_k_deep_capped_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t per_group,
+                                     const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                                     uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > BSR_DEEP_MAX_K) return set_error(BSR_E_INVALID, "k=%u outside [1, %u]", k, BSR_DEEP_MAX_K);
+    if (per_group == 0 || per_group > BSR_CAP_MAX_PER_GROUP)
+        return set_error(BSR_E_INVALID, "per_group=%u outside 1 <= per_group <= %u", per_group, BSR_CAP_MAX_PER_GROUP);
+    if (n_groups == 0) return set_error(BSR_E_INVALID, "n_groups = 0");
+    // (the tables' entries per query go through the selection's 32-bit length)
+    if ((uint64_t)std::min(per_group, k) * n_groups > 0xFFFFFFFFull)
+        return set_error(BSR_E_INVALID, "min(per_group, k) * n_groups = %u * %u exceeds 2^32 - 1", std::min(per_group, k),
+                         n_groups);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (row_group_len != ix->n)
+        return set_error(BSR_E_INVALID, "row_group_len=%llu, the index holds %llu rows", (unsigned long long)row_group_len,
+                         (unsigned long long)ix->n);
+    if (ix->n && !row_group) return set_error(BSR_E_INVALID, "null row_group");
+    if (nq == 0) return BSR_OK;
+    BSR_TRY(ix->deep_capped_search_device(queries, nq, k, per_group, row_group, n_groups, out_idx, out_dist, out_group,
+                                          out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // Group search (bsr_local_top_groups): the collapsed search names every query's k
 // groups, the inverted list of row_group gives their rows, the fill keeps the m best of each.
 // ---------------------------------------------------------------------------------------

@@ -330,6 +330,15 @@ struct bsr_index {
     bsr::DevBuf col_best;   // u64 [queries of a round][n_groups][entries per group]: the scan's tables
     bsr::DevBuf col_idx, col_dist, col_group, col_cnt;  // the result rows [nq][k], the counts [nq]
 
+    // Deep capped search (bsr_local_top_k_deep_capped): the deep search's filter rung
+    // (deep_keys, deep_cnt, deep_rad) with the capped walk of the rescored keys, and the capped group
+    // scan above (col_*) for the queries the walk leaves, k up to BSR_DEEP_MAX_K.  No candidate search
+    // runs: launched directly, never captured; every result row goes to col_idx / col_dist /
+    // col_group / col_cnt first and to the caller's arrays only once the status words are read.
+    int deep_capped_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t per_group,
+                                  const uint32_t* row_group, uint32_t n_groups, uint64_t* out_idx, float* out_dist,
+                                  uint32_t* out_group, uint32_t* out_count);
+
     // Group search (bsr_local_top_groups): the collapsed search above into buffers of
     // the index (the heads and their groups), the inverted list of row_group built for the call, the
     // fill over the rows of every query's result groups, and for the queries with more items than

@@ -2612,6 +2612,223 @@ __global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_merge_wide(MergeWideArgs 
 }
 
 // ------------------------------------------------------------------------------------
+// Deep capped search (bsr_local_top_k_deep_capped): the first k rows of a query's
+// (distance, index) order of which fewer than m rows of their group precede them, k <= kDeepMaxK.
+// ------------------------------------------------------------------------------------
+// One workgroup per query over the distance keys the filter rung rescored (unordered, distinct).
+// Every live row whose distance lies strictly below B = exclusion_bound() of the query's emission
+// threshold was emitted, so the keys below B in ascending order are an exact prefix of the query's
+// order, however long: the kernel walks that prefix in windows, k_merge_wide's way.  A window is the
+// next <= kDeepSortKeys smallest keys above the last window's limit -- a most-significant-first
+// radix select (11-bit digits, 9 at the end, k_deep_select's histogram) takes the longest run of
+// bins that fits, and splits the bin that overflows while the run holds fewer than 1.5 x the rows
+// still wanted -- compacted into LDS, sorted, the group of every slot loaded beside it.  Wave 0
+// walks the window 64 slots at a time against an LDS hash of (group -> kept rows): a lane is kept
+// when the kept rows of its group plus the earlier lanes of its group in the step number fewer
+// than m (the rows of a group below the lane are exactly those: the prefix is exact), takes the
+// next result slot in lane order and joins the hash.  At most k <= 1024 groups are ever kept: 2048
+// hash slots.  The walk ends at k rows: the query is certified, its count is k.  A query whose keys
+// below B run out first, whose list overflowed or whose bound certifies nothing (B = -inf) joins
+// the fail list; the rows it wrote are the scan's to overwrite.
+__global__ __launch_bounds__(256) void k_deep_cap_select(DeepCapSelectArgs a) {
+    constexpr uint32_t BINS = 2048, PER = BINS / 256, HS = 2 * kDeepMaxK, WIN = kDeepSortKeys;
+    __shared__ uint64_t sk[WIN];
+    __shared__ uint32_t w_grp[WIN];
+    __shared__ uint32_t g_key[HS];  // kept groups (~0u: empty; a group id is below n_groups <= 2^32 - 1) ...
+    __shared__ uint32_t g_cnt[HS];  // ... and their kept rows
+    __shared__ uint32_t hist[BINS];
+    __shared__ uint32_t s_scan[256];
+    __shared__ uint32_t s_n, s_bin, s_taken, s_out;
+    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    const int lane = t & 63;
+    const uint32_t k = a.k, m = a.per_group;
+    auto fail = [&]() {
+        if (t == 0) a.fail[atomicAdd(a.status + kStFail, 1u)] = q;
+    };
+    if (a.emit_cnt[q] > a.cap) return fail();  // (rows were dropped; uniform over the workgroup)
+    const float B = exclusion_bound(a.tau[q], a.ebound[q], a.nb[q]);
+    if (!(B > 0.0f)) return fail();            // (no distance lies below it)
+    const uint64_t* __restrict__ src = a.keys + (uint64_t)q * a.cap;
+    const uint32_t c = a.kcnt[q] < a.cap ? a.kcnt[q] : a.cap;
+    const uint32_t c_up = (c + 255u) & ~255u;  // (every lane of a wave takes every trip: ballots)
+    for (uint32_t i = t; i < HS; i += 256) {
+        g_key[i] = ~0u;
+        g_cnt[i] = 0;
+    }
+    if (t == 0) s_out = 0;
+    __syncthreads();
+    auto hash_slot = [](uint32_t g) -> uint32_t { return (g * 0x9E3779B1u) >> 21; };  // (11 bits: HS slots)
+    static_assert(HS == 2048, "hash_slot keeps 11 bits");
+
+    uint64_t lo = 0;    // the last window's limit: the keys up to it are walked ...
+    bool first = true;  // ... none yet
+    bool last = false;  // the window holds every key left below B
+    while (!last) {
+        const uint32_t out = s_out;
+        if (out >= k) break;
+        const uint32_t need = k - out, target = need + need / 2;  // (<= 1536 < WIN)
+        // key i of the list when it is still to be walked
+        auto load = [&](uint32_t i, uint64_t& key) __attribute__((always_inline)) -> bool {
+            key = i < c ? src[i] : kKeyNone;
+            return key != kKeyNone && key_dist(key) < B && (first || key > lo);
+        };
+        uint64_t limit = kKeyNone;  // the window takes the keys <= limit
+        if (c <= WIN) {
+            last = true;
+        } else {
+            uint64_t prefix = 0, mask = 0;  // the live bucket: its `fixed` high bits
+            uint32_t fixed = 0, below = 0;
+            while (true) {
+                // (a pass with every bit fixed is never reached: the last digit's bins hold one key
+                // each -- the keys are distinct -- so its run is the whole bucket or WIN >= target keys)
+                const uint32_t width = fixed + 11u <= 64u ? 11u : 64u - fixed, sh = 64u - fixed - width;
+                for (uint32_t i = t; i < BINS; i += 256) hist[i] = 0;
+                __syncthreads();
+                for (uint32_t i = t; i < c_up; i += 256) {
+                    uint64_t key;
+                    bool in = load(i, key) && (key & mask) == prefix;
+                    const uint32_t bin = (uint32_t)(key >> sh) & ((1u << width) - 1u);
+                    const uint64_t m0 = __ballot(in);
+                    if (m0) {  // the lanes that agree with the first: one add
+                        const int f0 = __builtin_ctzll(m0);
+                        const uint32_t b0 = (uint32_t)__shfl((int)bin, f0, kWave);
+                        const uint64_t same = __ballot(in && bin == b0);
+                        if (lane == f0) atomicAdd(&hist[b0], (uint32_t)__popcll(same));
+                        in = in && bin != b0;
+                    }
+                    if (in) atomicAdd(&hist[bin], 1u);
+                }
+                __syncthreads();
+                uint32_t mine = 0;
+#pragma unroll
+                for (uint32_t b = 0; b < PER; ++b) mine += hist[t * PER + b];
+                s_scan[t] = mine;
+                __syncthreads();
+                for (uint32_t s = 1; s < 256; s <<= 1) {  // (inclusive scan)
+                    const uint32_t v = t >= s ? s_scan[t - s] : 0u;
+                    __syncthreads();
+                    s_scan[t] += v;
+                    __syncthreads();
+                }
+                if (below + s_scan[255] <= WIN) {  // the whole bucket fits
+                    limit = prefix | ~mask;
+                    last = fixed == 0;
+                    break;
+                }
+                const uint32_t incl = below + s_scan[t], excl = incl - mine;
+                if (excl <= WIN && incl > WIN) {  // (one thread: the scan is monotone) the bin that overflows
+                    uint32_t run = excl, b = 0;
+                    while (run + hist[t * PER + b] <= WIN) run += hist[t * PER + b++];
+                    s_bin = t * PER + b;
+                    s_taken = run;
+                }
+                __syncthreads();
+                const uint64_t ob = s_bin;
+                const uint32_t taken = s_taken;
+                if (taken >= target) {  // (ob >= 1: below < target) the bins before it are the window
+                    limit = prefix | ((ob - 1) << sh) | ((1ull << sh) - 1ull);
+                    break;
+                }
+                prefix |= ob << sh;
+                mask |= (uint64_t)((1u << width) - 1u) << sh;
+                fixed += width;
+                below = taken;
+            }
+        }
+        if (t == 0) s_n = 0;
+        __syncthreads();
+        for (uint32_t i = t; i < c_up; i += 256) {
+            uint64_t key;
+            const bool take = load(i, key) && key <= limit;
+            const uint32_t slot = wave_claim(take, &s_n, lane);
+            if (take && slot < WIN) sk[slot] = key;
+        }
+        __syncthreads();
+        const uint32_t n = s_n < WIN ? s_n : WIN;
+        if (n == 0) break;  // (uniform) nothing is left below B
+        lds_sort_inplace(sk, n, t);
+        for (uint32_t j = t; j < n; j += 256) w_grp[j] = a.row_group[key_row(sk[j])];
+        __syncthreads();
+        if (t < (uint32_t)kWave) {
+            volatile uint32_t* const vg = g_key;
+            volatile uint32_t* const vc = g_cnt;
+            uint32_t o = out;
+            for (uint32_t base = 0; base < n && o < k; base += kWave) {
+                const uint32_t j = base + lane;
+                const bool have = j < n;  // (the lanes without a slot are the step's last)
+                const uint64_t key = have ? sk[j] : 0ull;
+                const uint32_t g = have ? w_grp[j] : ~0u;
+                uint32_t gc = 0;  // kept rows of the lane's group in the steps before
+                if (have)
+                    for (uint32_t sl = hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
+                        const uint32_t v = vg[sl];
+                        if (v == g) gc = vc[sl];
+                        if (v == g || v == ~0u) break;
+                    }
+                uint32_t before = 0;  // earlier lanes of the step with the lane's group
+#pragma unroll
+                for (int l = 0; l < kWave - 1; ++l)
+                    before += (l < lane && (uint32_t)__builtin_amdgcn_readlane((int)g, l) == g) ? 1u : 0u;
+                const bool kept = have && gc + before < m;
+                const uint64_t mk = __ballot(kept);
+                const uint32_t slot =
+                    o + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                if (kept && slot < k) {
+                    const uint64_t p = (uint64_t)q * k + slot;
+                    a.out_idx[p] = a.offset + key_row(key);
+                    a.out_dist[p] = key_dist(key);
+                    a.out_group[p] = g;
+                    for (uint32_t sl = hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
+                        const uint32_t prev = atomicCAS(&g_key[sl], ~0u, g);
+                        if (prev == ~0u || prev == g) {
+                            atomicAdd(&g_cnt[sl], 1u);
+                            break;
+                        }
+                    }
+                }
+                o += (uint32_t)__popcll(mk);
+                o = o < k ? o : k;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (the next step reads the hash)
+            }
+            if (lane == 0) s_out = o;
+        }
+        __syncthreads();
+        lo = limit;
+        first = false;
+    }
+    if (s_out < k) return fail();  // (uniform: read behind a barrier, or 0 < k from the start)
+    if (t == 0) a.out_count[q] = k;
+}
+
+// One workgroup per scanned query of a round: its k smallest table keys [.][k] (ascending, kKeyNone
+// behind them) as result rows with their groups -- k_collapse_finish for k <= kDeepMaxK.
+__global__ __launch_bounds__(256) void k_deep_cap_finish(const uint64_t* __restrict__ keys,
+                                                         const int32_t* __restrict__ qids, uint32_t k,
+                                                         uint64_t offset, const uint32_t* __restrict__ row_group,
+                                                         uint64_t* __restrict__ out_idx, float* __restrict__ out_dist,
+                                                         uint32_t* __restrict__ out_group,
+                                                         uint32_t* __restrict__ out_count) {
+    __shared__ uint32_t s_c;
+    const uint32_t q = (uint32_t)qids[blockIdx.x], t = threadIdx.x;
+    if (t == 0) s_c = 0;
+    __syncthreads();
+    for (uint32_t e = t; e < ((k + 255u) & ~255u); e += 256) {  // (every lane takes every trip: ballots)
+        const uint64_t key = e < k ? keys[(uint64_t)q * k + e] : kKeyNone;
+        const bool has = key != kKeyNone;
+        const uint64_t mk = __ballot(has);
+        if (mk && lane_id() == 0) atomicAdd(&s_c, (uint32_t)__popcll(mk));
+        if (e < k) {
+            const uint64_t o = (uint64_t)q * k + e;
+            out_idx[o] = has ? offset + key_row(key) : ~0ull;
+            out_dist[o] = has ? key_dist(key) : INFINITY;
+            out_group[o] = has ? row_group[key_row(key)] : ~0u;
+        }
+    }
+    __syncthreads();
+    if (t == 0) out_count[q] = s_c;
+}
+
+// ------------------------------------------------------------------------------------
 // Scoring caller-chosen rows (bsr_local_score_ids / bsr_local_rerank_ids): the
 // reference's distance of every id of a per-query list, aligned with the list.
 // ------------------------------------------------------------------------------------
@@ -3562,6 +3779,25 @@ hipError_t launch_cap_scan(const CapScanArgs& c, uint32_t grid, hipStream_t s) {
     else if (a.nqf <= 2) hipLaunchKernelGGL(k_cap_scan<2>, dim3(grid), dim3(256), 0, s, c);
     else if (a.nqf <= 4) hipLaunchKernelGGL(k_cap_scan<4>, dim3(grid), dim3(256), 0, s, c);
     else hipLaunchKernelGGL(k_cap_scan<8>, dim3(grid), dim3(256), 0, s, c);
+    return hipGetLastError();
+}
+
+// ---- deep capped search ----------------------------------------------------------------------
+hipError_t launch_deep_cap_select(const DeepCapSelectArgs& a, hipStream_t s) {
+    if (!a.nq || !a.k || a.k > kDeepMaxK || !a.per_group || !a.cap || !a.keys || !a.kcnt || !a.row_group ||
+        !a.out_idx || !a.out_dist || !a.out_group || !a.out_count || !a.tau || !a.ebound || !a.nb || !a.emit_cnt ||
+        !a.fail || !a.status)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_deep_cap_select, dim3(a.nq), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_deep_cap_finish(const uint64_t* keys, const int32_t* qids, uint32_t nqf, uint32_t k, uint64_t offset,
+                                  const uint32_t* row_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                  uint32_t* out_count, hipStream_t s) {
+    if (!nqf || !k || k > kDeepMaxK || !out_group) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_deep_cap_finish, dim3(nqf), dim3(256), 0, s, keys, qids, k, offset, row_group, out_idx,
+                       out_dist, out_group, out_count);
     return hipGetLastError();
 }
 

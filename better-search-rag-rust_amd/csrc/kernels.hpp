@@ -844,6 +844,40 @@ struct CapScanArgs {
 };
 hipError_t launch_cap_scan(const CapScanArgs& a, uint32_t grid, hipStream_t s);
 
+// ---- deep capped search (bsr_local_top_k_deep_capped; k_exact.hip) --------------
+// One workgroup per query over the filter rung's rescored keys (launch_range_rescore with a radius
+// of +inf: keys + q * cap, min(kcnt[q], cap) of them, any order, distinct).  The keys whose distance
+// lies strictly below exclusion_bound(tau[q], ebound[q], nb[q]) are, in ascending order, an exact
+// prefix of the query's (distance, row) order; along it a row is kept while fewer than per_group
+// rows of its group (row_group[row], every entry checked by launch_group_check) precede it.  A
+// query that keeps k rows that way is certified: row q of out_idx / out_dist / out_group [nq][k]
+// holds them as (offset + row, distance, group) and out_count[q] = k.  Every other query -- its
+// emitted list overflowed (emit_cnt[q] > cap), its bound certifies nothing, or its keys below the
+// bound ran out first -- is appended to fail with one atomic on status[kStFail]; what it wrote to
+// its result row means nothing and its count is not written.  1 <= k <= kDeepMaxK, per_group >= 1.
+struct DeepCapSelectArgs {
+    const uint64_t* keys;       // [nq][cap]
+    const uint32_t* kcnt;       // [nq]
+    uint32_t cap, nq, k, per_group;
+    uint64_t offset;            // the global id of row 0
+    const uint32_t* row_group;  // [n]
+    uint64_t* out_idx;          // [nq][k]
+    float* out_dist;            // [nq][k]
+    uint32_t* out_group;        // [nq][k]
+    uint32_t* out_count;        // [nq]
+    const float* tau;
+    const float* ebound;
+    const float* nb;
+    const uint32_t* emit_cnt;
+    uint32_t* fail;
+    uint32_t* status;
+};
+hipError_t launch_deep_cap_select(const DeepCapSelectArgs& a, hipStream_t s);
+// launch_collapse_finish for k <= kDeepMaxK (out_group is not nullable here).
+hipError_t launch_deep_cap_finish(const uint64_t* keys, const int32_t* qids, uint32_t nqf, uint32_t k, uint64_t offset,
+                                  const uint32_t* row_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                  uint32_t* out_count, hipStream_t s);
+
 // ---- group search (bsr_local_top_groups; k_groups.hip) --------------------------
 // The inverted list of row_group[0 .. n) (every entry < n_groups, launch_group_check), three launches:
 // the histogram gcnt[g] = the rows of group g (gcnt zero before it); the offsets -- every group gets a

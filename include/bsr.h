@@ -712,9 +712,9 @@ int bsr_local_rerank_ids(bsr_index* ix, const float* queries, uint32_t n_queries
  * A multi-rank deep search: this call on every rank with device outputs, bsr_allgather_bytes of the
  * three outputs on device buffers, bsr_global_top_k on the gathered device arrays (host arrays
  * merge on the host).
- * Out of scope: row groups (collapsed, capped, group searches) with deep k; a parallel entry point
- * that runs those collectives itself.  Allow masks:
- * bsr_local_top_k_deep_masked below. */
+ * Out of scope: the group search (bsr_local_top_groups) with deep k; a parallel entry point
+ * that runs those collectives itself.  Allow masks: bsr_local_top_k_deep_masked below.  At most m
+ * rows per group, or one row per group: bsr_local_top_k_deep_capped below. */
 #define BSR_DEEP_MAX_K 1024u
 int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
                          uint64_t* out_idx, float* out_dist, /* [n_queries][k] */
@@ -758,12 +758,63 @@ int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries
  * scan_ms, the rescore and the selection in rescore_ms.
  * A multi-rank masked deep search: as bsr_local_top_k_deep's (device lists merge on the GPU with
  * bsr_global_top_k).
- * Out of scope: row groups with deep k. */
+ * Out of scope: row groups with deep k under a mask (bsr_local_top_k_deep_capped takes no mask). */
 int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
                                 const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                                 const uint32_t* query_mask, /* [n_queries], nullable with one mask */
                                 uint32_t mode,              /* BSR_MASK_AUTO / _LIST / _FILTER */
                                 uint64_t* out_idx, float* out_dist, /* [n_queries][k] */
+                                uint32_t* out_count /* [n_queries] */);
+
+/* ---- Deep capped search: bsr_local_top_k_capped for k up to BSR_DEEP_MAX_K --
+ * "1000 chunks, at most 3 per document", and with per_group = 1 "the 1000 nearest distinct
+ * documents" (the deep collapsed search).  row_group, row_group_len and n_groups are taken exactly as
+ * bsr_local_top_k_collapsed takes them: per call, host or device memory (detected per call), never
+ * stored; a host array is copied into the index's buffer.  There is no fetch_k and there are no masks.
+ * The result is rules 1 to 5 of bsr_local_top_k_capped over the live rows, with m = per_group: the
+ * first k kept rows as (global index, the reference's f32 distance bits, group id in out_group,
+ * nullable), then (~0, +inf, ~0u); out_count[q] = min(k, sum over the groups of min(m, the group's
+ * live rows)).  row_group[i] = i is bsr_local_top_k_deep(k) bit for bit; for k <= 256 the result is
+ * bsr_local_top_k_capped(k, fetch_k = 256, per_group)'s byte for byte; the result at k is a prefix
+ * of the result at any larger k.  An empty shard, or one with every row deleted: every count 0.
+ * 1 <= k <= BSR_DEEP_MAX_K, not bounded by cfg.max_k; 1 <= per_group <= BSR_CAP_MAX_PER_GROUP;
+ * n_groups >= 1.  Every array is, independently, a host or a device pointer.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; k = 0 or k > BSR_DEEP_MAX_K;
+ *      per_group = 0 or above BSR_CAP_MAX_PER_GROUP; n_groups = 0; min(per_group, k) * n_groups >
+ *      2^32 - 1; with n_queries > 0 a null queries pointer or a null out_idx / out_dist / out_count;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. BSR_E_INVALID: row_group_len != n, or a null row_group with rows;
+ *   4. n_queries = 0: BSR_OK;
+ *   5. BSR_E_INVALID: a row_group entry >= n_groups, found on the device before any table or hash is
+ *      indexed with it;
+ *   6. BSR_E_NONFINITE: a non-finite query, read from the batch's status words before any of the
+ *      caller's arrays, host or device, is written.
+ * How: the deep search's filter rung, unchanged up to the rescore -- about 4 k emitted rows a query,
+ * each with its reference distance.  Every live row whose distance lies strictly below the exclusion
+ * bound of the query's emission threshold was emitted, so those keys in ascending order are an exact
+ * prefix of the query's order, much longer than k; one kernel walks it in sorted windows of 2048
+ * keys and counts groups along it until k rows are kept.  A query whose prefix runs out first (and
+ * every query of an index that cannot filter: BSR_FLAG_EXACT_ONLY, sticky norm flags, no more live
+ * rows than a list holds) takes the capped search's group scan -- tables of 8 * min(m, k) * n_groups
+ * bytes, rounds of up to 8 queries under BSR_COLLAPSE_TABLE_BUDGET -- and a selection of the k
+ * smallest table keys.  Never graph-replayed; the plain search's graphs are left alone.
+ * bsr_search_stats: search_path = BSR_PATH_DEEP | BSR_PATH_CAP, plus BSR_PATH_CAP_SCAN when a query
+ * took the group scan; never BSR_PATH_DEEP_SCAN or BSR_PATH_COLLAPSE.  n_emitted, n_candidates,
+ * n_exact_direct and n_fallback are bsr_local_top_k_deep's.  BSR_FLAG_PROFILE: the rescore and the
+ * walk in rescore_ms, the scan rounds in scan_ms, the call in search_ms.
+ * A multi-rank deep capped search: this call on every rank with its own row_group (global group
+ * ids) and device outputs, out_group included; bsr_allgather_bytes of the four outputs on device
+ * buffers; bsr_global_top_k_capped(k_in = k, per_group) on the gathered device arrays, which merges
+ * lists of this depth on the GPU.
+ * Out of scope: allow masks (the follow-up: the masked deep search's list scan with groups); the
+ * group search (bsr_local_top_groups) at deep k; a per-query per_group; raising
+ * BSR_CAP_MAX_PER_GROUP; a collective entry point. */
+int bsr_local_top_k_deep_capped(bsr_index* ix, const float* queries, uint32_t n_queries,
+                                uint32_t k, uint32_t per_group,
+                                const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                                uint64_t* out_idx, float* out_dist,    /* [n_queries][k] */
+                                uint32_t* out_group /* [n_queries][k], nullable */,
                                 uint32_t* out_count /* [n_queries] */);
 
 /* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists.  Layout and
