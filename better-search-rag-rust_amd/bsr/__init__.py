@@ -70,6 +70,7 @@ BSR_PATH_GROUPS = 262144        # bsr_local_top_groups ran (with the bits of the
 BSR_PATH_DEEP = 524288          # bsr_local_top_k_deep ran
 BSR_PATH_DEEP_SCAN = 1048576    # ... and a query of the batch was answered by the deep exact scan
 BSR_DEEP_MAX_K = 1024           # the largest k of bsr_local_top_k_deep (include/bsr.h)
+BSR_DEEP_MMR_MAX_PICKS = 256    # the largest k of bsr_local_top_k_deep_mmr (include/bsr.h)
 BSR_GROUPS_MAX_ROWS = 64        # the largest group_size of a group search (include/bsr.h)
 BSR_GROUPS_MAX_SLOTS = 4096     # ... and the largest k * group_size
 BSR_SCORE_MAX_IDS = 4096        # the longest id list bsr_local_rerank_ids orders (include/bsr.h)
@@ -162,6 +163,9 @@ def lib() -> ctypes.CDLL:
         "bsr_local_range_search_masked": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_local_top_k_mmr": (ctypes.c_int, [_P, _P, u32, u32, u32, ctypes.c_float, _P, u64, u32, _P, u32, _P, _P,
                                                _P, _P]),
+        "bsr_local_top_k_deep_mmr": (ctypes.c_int, [_P, _P, u32, u32, u32, ctypes.c_float, _P, u64, u32, _P, u32, _P,
+                                                    _P, _P, _P]),
+        "bsr_index_last_mmr_pairs": (ctypes.c_int, [_P, ctypes.POINTER(u64)]),
         "bsr_local_top_k_collapsed": (ctypes.c_int, [_P, _P, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P, _P,
                                                      _P, _P]),
         "bsr_local_top_k_capped": (ctypes.c_int, [_P, _P, u32, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P,
@@ -200,7 +204,7 @@ def lib() -> ctypes.CDLL:
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
                 "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids",
                 "bsr_local_top_groups", "bsr_local_top_k_deep", "bsr_local_top_k_deep_masked",
-                "bsr_local_top_k_deep_capped"}
+                "bsr_local_top_k_deep_capped", "bsr_local_top_k_deep_mmr", "bsr_index_last_mmr_pairs"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -855,6 +859,13 @@ class Index:
         the global index, dist the distance to the query, rank the position in the candidate list.
         lambda_mult = 1 is local_top_k(k); 0 is farthest-first after the top-1.
         allow_mask / allow_ids, or allow_masks with query_mask, and mask_mode: as range_search's."""
+        return self._mmr("bsr_local_top_k_mmr", queries, k, fetch_k, self.max_k, self.max_k, lambda_mult, allow_mask,
+                         allow_ids, allow_masks, query_mask, mask_mode, return_rank)
+
+    def _mmr(self, call, queries, k, fetch_k, max_k, max_fetch, lambda_mult, allow_mask, allow_ids, allow_masks,
+             query_mask, mask_mode, return_rank):
+        """mmr_search and deep_mmr_search: the library call `call` with 1 <= k <= min(fetch_k, max_k)
+        and fetch_k <= max_fetch (by default min(max_fetch, max(20, 4 k)))."""
         one = allow_mask is not None or allow_ids is not None
         if one and (allow_masks is not None or query_mask is not None):
             raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
@@ -867,9 +878,9 @@ class Index:
             raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
         nq = q.shape[0]
         k = int(k)
-        fk = min(self.max_k, max(20, 4 * k)) if fetch_k is None else int(fetch_k)
-        if k < 1 or k > fk or fk > self.max_k:
-            raise BsrError(-1, f"k={k}, fetch_k={fk} outside 1 <= k <= fetch_k <= max_k={self.max_k}")
+        fk = min(max_fetch, max(20, 4 * k)) if fetch_k is None else int(fetch_k)
+        if k < 1 or k > fk or k > max_k or fk > max_fetch:
+            raise BsrError(-1, f"k={k}, fetch_k={fk} outside 1 <= k <= min(fetch_k, {max_k}), fetch_k <= {max_fetch}")
         lam = float(lambda_mult)
         if not 0.0 <= lam <= 1.0:  # (a NaN fails both comparisons)
             raise BsrError(-1, f"lambda_mult={lam} outside [0, 1]")
@@ -888,8 +899,8 @@ class Index:
                 qm = self._query_mask_ids(query_mask, nq)
             # (an empty shard's masks have no words: a valid, non-null pointer all the same)
             wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
-        _check(lib().bsr_local_top_k_mmr(self._h, _ptr(q), nq, k, fk, lam, wp, nw, n_masks, _ptr(qm),
-                                         _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(orank), _ptr(oc)))
+        _check(getattr(lib(), call)(self._h, _ptr(q), nq, k, fk, lam, wp, nw, n_masks, _ptr(qm),
+                                    _mask_mode(mask_mode), _ptr(oi), _ptr(od), _ptr(orank), _ptr(oc)))
         return (oi, od, oc, orank) if return_rank else (oi, od, oc)
 
     def mmr_search_device(self, queries, nq: int, k: int, fetch_k: int, lambda_mult: float, out_idx, out_dist,
@@ -898,6 +909,11 @@ class Index:
         pointers, each host or device): queries [nq][dim] f32, out_idx / out_dist / out_rank
         (optional) [nq][k], out_count [nq].  allow_words: the packed allow masks, [G][ceil(n / 64)]
         uint64 with query_mask [nq] 32-bit mask ids, or [ceil(n / 64)] -- one mask, no query_mask."""
+        self._mmr_device("bsr_local_top_k_mmr", queries, nq, k, fetch_k, lambda_mult, out_idx, out_dist, out_count,
+                         out_rank, allow_words, query_mask, mask_mode)
+
+    def _mmr_device(self, call, queries, nq, k, fetch_k, lambda_mult, out_idx, out_dist, out_count, out_rank,
+                    allow_words, query_mask, mask_mode):
         if allow_words is None:
             if query_mask is not None:
                 raise BsrError(-1, "a query_mask needs allow_words")
@@ -907,9 +923,32 @@ class Index:
             if len(shape) not in (1, 2):
                 raise BsrError(-1, "packed allow masks have shape [G][words] or [words]")
             wp, nw, n_masks = _ptr(allow_words), int(shape[-1]), int(shape[0]) if len(shape) == 2 else 1
-        _check(lib().bsr_local_top_k_mmr(self._h, _ptr(queries), nq, k, fetch_k, float(lambda_mult), wp, nw, n_masks,
-                                         _ptr(query_mask), _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist),
-                                         _ptr(out_rank), _ptr(out_count)))
+        _check(getattr(lib(), call)(self._h, _ptr(queries), nq, k, fetch_k, float(lambda_mult), wp, nw, n_masks,
+                                    _ptr(query_mask), _mask_mode(mask_mode), _ptr(out_idx), _ptr(out_dist),
+                                    _ptr(out_rank), _ptr(out_count)))
+
+    def deep_mmr_search(self, queries, k: int, fetch_k=None, lambda_mult: float = 0.5, allow_mask=None,
+                        allow_ids=None, allow_masks=None, query_mask=None, mask_mode="auto",
+                        return_rank: bool = False):
+        """mmr_search over up to BSR_DEEP_MAX_K exact candidates (bsr_local_top_k_deep_mmr): the
+        candidates are deep_search(fetch_k)'s, 1 <= k <= min(fetch_k, BSR_DEEP_MMR_MAX_PICKS), neither
+        bounded by max_k; fetch_k defaults to min(1024, max(20, 4 k)).  The same rule and outputs as
+        mmr_search, bit for bit; the pair distances are computed lazily (last_mmr_pairs)."""
+        return self._mmr("bsr_local_top_k_deep_mmr", queries, k, fetch_k, BSR_DEEP_MMR_MAX_PICKS, BSR_DEEP_MAX_K,
+                         lambda_mult, allow_mask, allow_ids, allow_masks, query_mask, mask_mode, return_rank)
+
+    def deep_mmr_search_device(self, queries, nq: int, k: int, fetch_k: int, lambda_mult: float, out_idx, out_dist,
+                               out_count, out_rank=None, allow_words=None, query_mask=None, mask_mode="auto"):
+        """Zero-copy variant of deep_mmr_search on caller buffers: mmr_search_device's arguments."""
+        self._mmr_device("bsr_local_top_k_deep_mmr", queries, nq, k, fetch_k, lambda_mult, out_idx, out_dist,
+                         out_count, out_rank, allow_words, query_mask, mask_mode)
+
+    def last_mmr_pairs(self) -> int:
+        """The pair distances the last deep_mmr_search computed, summed over its queries (a full
+        column per pick would be the sum of (picks - 1) * candidates); 0 before any such call."""
+        out = ctypes.c_uint64(0)
+        _check(lib().bsr_index_last_mmr_pairs(self._h, ctypes.byref(out)))
+        return int(out.value)
 
     def collapsed_search(self, queries, k: int, row_group, n_groups=None, fetch_k=None, allow_mask=None,
                          allow_ids=None, allow_masks=None, query_mask=None, mask_mode="auto",

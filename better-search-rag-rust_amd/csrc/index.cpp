@@ -3169,6 +3169,99 @@ int bsr_local_top_k_mmr_impl(bsr_index* ix, const float* queries, uint32_t nq, u
 }
 
 // ---------------------------------------------------------------------------------------
+// Deep MMR search (bsr_local_top_k_deep_mmr)
+// ---------------------------------------------------------------------------------------
+int bsr_index::deep_mmr_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k, float lambda,
+                                      const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                      const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                      uint32_t* out_rank, uint32_t* out_count) {
+    BSR_HIP(hipSetDevice(device));
+    // The call's own buffers first: the candidate lists the deep search writes, and the picks.
+    const size_t nf = (size_t)nq * fetch_k, nk = (size_t)nq * k;
+    BSR_TRY(dmmr_idx.ensure(nf * sizeof(uint64_t)));
+    BSR_TRY(dmmr_dist.ensure(nf * sizeof(float)));
+    BSR_TRY(dmmr_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    BSR_TRY(dmmr_pairs.ensure(sizeof(uint64_t)));
+    BSR_TRY(mmr_idx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(mmr_dist.ensure(nk * sizeof(float)));
+    BSR_TRY(mmr_rank.ensure(nk * sizeof(uint32_t)));
+    BSR_TRY(mmr_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    // The candidates: the deep search with k = fetch_k, run to completion into those lists (its
+    // errors return here, before any of the caller's arrays is written).
+    if (!allow) BSR_TRY(deep_search_device(queries, nq, fetch_k, dmmr_idx.as<uint64_t>(), dmmr_dist.as<float>(),
+                                           dmmr_cnt.as<uint32_t>()));
+    else BSR_TRY(deep_search_device_masked(queries, nq, fetch_k, allow, allow_words, n_masks, query_mask, mode,
+                                           dmmr_idx.as<uint64_t>(), dmmr_dist.as<float>(), dmmr_cnt.as<uint32_t>()));
+    stats.search_path |= BSR_PATH_MMR;
+    // The selection: straight into the caller's arrays when they are all on the device, else into
+    // the index's own and copied out (mmr_search_device).
+    const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count) &&
+                         (!out_rank || is_device_ptr(out_rank));
+    BSR_HIP(hipMemsetAsync(dmmr_pairs.p, 0, sizeof(uint64_t), stream));
+    MmrDeepArgs ma{};
+    ma.rows = rows.as<float>();
+    ma.ld = ld;
+    ma.dim = dim;
+    ma.n = n;
+    ma.offset = global_offset;
+    ma.na = na.as<float>();
+    ma.cand_idx = dmmr_idx.as<uint64_t>();
+    ma.cand_dist = dmmr_dist.as<float>();
+    ma.cand_cnt = dmmr_cnt.as<uint32_t>();
+    ma.nq = nq;
+    ma.fetch_k = fetch_k;
+    ma.k = k;
+    ma.lambda = lambda;
+    ma.out_idx = out_dev ? out_idx : mmr_idx.as<uint64_t>();
+    ma.out_dist = out_dev ? out_dist : mmr_dist.as<float>();
+    ma.out_rank = out_dev ? out_rank : mmr_rank.as<uint32_t>();
+    ma.out_count = out_dev ? out_count : mmr_cnt.as<uint32_t>();
+    ma.pairs = dmmr_pairs.as<unsigned long long>();
+    BSR_HIP(launch_mmr_deep_select(ma, stream));
+    if (!out_dev) {
+        BSR_HIP(hipMemcpyAsync(out_idx, ma.out_idx, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, ma.out_dist, nk * sizeof(float), hipMemcpyDefault, stream));
+        if (out_rank) BSR_HIP(hipMemcpyAsync(out_rank, ma.out_rank, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, ma.out_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    BSR_HIP(hipMemcpyAsync(&last_mmr_pairs, dmmr_pairs.p, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_k_deep_mmr_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k,
+                                  float lambda, const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                  const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                  uint32_t* out_rank, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > fetch_k || k > BSR_DEEP_MMR_MAX_PICKS || fetch_k > BSR_DEEP_MAX_K)
+        return set_error(BSR_E_INVALID, "k=%u, fetch_k=%u outside 1 <= k <= min(fetch_k, %u), fetch_k <= %u", k, fetch_k,
+                         BSR_DEEP_MMR_MAX_PICKS, BSR_DEEP_MAX_K);
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return set_error(BSR_E_INVALID, "lambda=%g outside [0, 1]", (double)lambda);
+    if (!allow && (n_masks != 0 || query_mask))
+        return set_error(BSR_E_INVALID, "n_masks = %u or a query_mask without allow masks", n_masks);
+    if (allow && n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 with allow masks");
+    if (allow && !query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (nq == 0) return BSR_OK;
+    BSR_TRY(ix->deep_mmr_search_device(queries, nq, k, fetch_k, lambda, allow, allow_words, n_masks, query_mask, mode,
+                                       out_idx, out_dist, out_rank, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+int bsr_index_last_mmr_pairs_impl(const bsr_index* ix, uint64_t* out_pairs) {
+    if (!ix || !out_pairs) return set_error(BSR_E_INVALID, "null index or output");
+    *out_pairs = ix->last_mmr_pairs;
+    return BSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // Collapsed search (bsr_local_top_k_collapsed) and capped search
 // (bsr_local_top_k_capped): one host sequence.  per_group = 0 is the collapsed search
 // with its own walk and scan kernels; per_group >= 1 the capped search, whose walk counts up to

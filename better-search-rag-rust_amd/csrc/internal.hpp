@@ -302,6 +302,18 @@ struct bsr_index {
                           uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_rank, uint32_t* out_count);
     bsr::DevBuf mmr_idx, mmr_dist, mmr_rank, mmr_cnt;  // the picks [nq][k], their counts [nq]
 
+    // Deep MMR search (bsr_local_top_k_deep_mmr): the deep search with k = fetch_k
+    // (masked by the mask arguments) run to completion into the call's own candidate lists, then the
+    // lazy selection kernel over them into the caller's arrays, host or device (out_rank nullable;
+    // the picks' buffers are the MMR search's).  Launched directly, never captured.
+    int deep_mmr_search_device(const float* queries, uint32_t nq, uint32_t k, uint32_t fetch_k, float lambda,
+                               const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                               const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                               uint32_t* out_rank, uint32_t* out_count);
+    bsr::DevBuf dmmr_idx, dmmr_dist, dmmr_cnt;  // the candidate lists [nq][fetch_k], their counts [nq]
+    bsr::DevBuf dmmr_pairs;                     // u64: the pair distances the selection computed
+    uint64_t last_mmr_pairs = 0;                // ... of the last deep MMR call
+
     // Collapsed search (bsr_local_top_k_collapsed): the group check, the candidate
     // search with k = fetch_k run to completion, the walk over its lists, and for the queries the
     // walk could not certify the group scan in rounds -- table memset, scan, selection, merge, finish.

@@ -756,6 +756,34 @@ struct MmrArgs {
 };
 hipError_t launch_mmr_select(const MmrArgs& a, hipStream_t s);
 
+// ---- deep MMR selection (bsr_local_top_k_deep_mmr; k_mmr.hip) --------------------
+// launch_mmr_select's contract and outputs, bit for bit, for lists of up to kMmrDeepMaxFetch
+// candidates and up to kMmrDeepMaxPicks picks.  The pair distances are computed lazily: a
+// candidate's score is brought up to date only while its last score could still beat the best
+// up-to-date one (scores only fall as picks are added).  *pairs (nullable; the caller zeroes it)
+// receives the number of pair distances the launch computed and folded into a mind: every workgroup
+// adds its count once.  fetch_k <= kMmrDeepMaxFetch, 1 <= k <= min(fetch_k, kMmrDeepMaxPicks),
+// lambda in [0, 1].
+constexpr uint32_t kMmrDeepMaxFetch = 1024;
+constexpr uint32_t kMmrDeepMaxPicks = 256;
+struct MmrDeepArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t n, offset;         // rows of the shard; the global id of row 0
+    const float* na;            // row magnitudes (read, never recomputed)
+    const uint64_t* cand_idx;   // [nq][fetch_k]
+    const float* cand_dist;     // [nq][fetch_k]
+    const uint32_t* cand_cnt;   // [nq]
+    uint32_t nq, fetch_k, k;
+    float lambda;
+    uint64_t* out_idx;          // [nq][k]
+    float* out_dist;            // [nq][k]
+    uint32_t* out_rank;         // [nq][k], nullable
+    uint32_t* out_count;        // [nq]
+    unsigned long long* pairs;  // [1], nullable
+};
+hipError_t launch_mmr_deep_select(const MmrDeepArgs& a, hipStream_t s);
+
 // ---- collapsed search (bsr_local_top_k_collapsed; k_exact.hip) ------------------
 // The group check: *flag |= 1 when an entry of row_group[0 .. n) is >= n_groups (zero before the
 // launch; 4 n bytes read, no pass over the rows).

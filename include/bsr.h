@@ -455,7 +455,8 @@ int bsr_local_range_search_masked(bsr_index* ix, const float* queries, uint32_t 
  * fields are the candidate search's.
  * Out of scope: multi-rank MMR (the pair distances need rows of other ranks: run the parallel
  * search for ids, then MMR on the rank that holds the rows); a per-query lambda; another diversity
- * measure; returning D. */
+ * measure; returning D.  More candidates than cfg.max_k: bsr_local_top_k_deep_mmr (fetch_k up to
+ * BSR_DEEP_MAX_K, the pair distances computed lazily). */
 int bsr_local_top_k_mmr(bsr_index* ix, const float* queries, uint32_t n_queries,
                         uint32_t k, uint32_t fetch_k, float lambda,
                         const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
@@ -816,6 +817,40 @@ int bsr_local_top_k_deep_capped(bsr_index* ix, const float* queries, uint32_t n_
                                 uint64_t* out_idx, float* out_dist,    /* [n_queries][k] */
                                 uint32_t* out_group /* [n_queries][k], nullable */,
                                 uint32_t* out_count /* [n_queries] */);
+
+/* ---- Deep MMR search: bsr_local_top_k_mmr over up to BSR_DEEP_MAX_K exact
+ * candidates -- "k different passages out of the 1000 nearest", without document ids and without
+ * reading the candidates' rows back.  Rules 1-6 of bsr_local_top_k_mmr, word for word, with one
+ * change to rule 1: the candidates are exactly what bsr_local_top_k_deep returns for k = fetch_k
+ * (with allow masks: bsr_local_top_k_deep_masked with the same mask arguments): m = min(fetch_k,
+ * allowed live rows) positions in (distance asc, global index asc) order, each with its dq bits.
+ * 1 <= k <= min(fetch_k, BSR_DEEP_MMR_MAX_PICKS), fetch_k <= BSR_DEEP_MAX_K, neither bounded by
+ * cfg.max_k (the call owns its buffers, as the deep searches do); lambda finite and within [0, 1].
+ * lambda = 1 returns bsr_local_top_k_deep(k) bit for bit; pick 0 is always the top-1; where fetch_k
+ * <= cfg.max_k the result is bsr_local_top_k_mmr's byte for byte, out_rank included.
+ * The selection computes pair distances lazily -- a candidate's score is brought up to date only
+ * while its last score could still beat the best up-to-date one; scores only fall as picks are
+ * added, so the result is the greedy rule's, bit for bit.
+ * queries, the masks and the four outputs are, independently, host or device pointers, detected per
+ * call.  The checks and their order are bsr_local_top_k_mmr's, with the limits above in step 1; the
+ * caller's arrays are untouched on every error (the candidate search's errors included).
+ * bsr_search_stats: search_path carries the candidate search's bits (BSR_PATH_DEEP, the mask bits,
+ * BSR_PATH_DEEP_SCAN) plus BSR_PATH_MMR; the other fields are the candidate search's.  The call is
+ * never graph-replayed and leaves the plain search's graphs alone.
+ * Out of scope: a per-query lambda; k above BSR_DEEP_MMR_MAX_PICKS; another diversity measure;
+ * returning D; a collective entry point (the pair distances need rows of other ranks: run the
+ * parallel deep search for ids, then score on the rank that holds the rows). */
+#define BSR_DEEP_MMR_MAX_PICKS 256u
+int bsr_local_top_k_deep_mmr(bsr_index* ix, const float* queries, uint32_t n_queries,
+                             uint32_t k, uint32_t fetch_k, float lambda,
+                             const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                             const uint32_t* query_mask, uint32_t mode,
+                             uint64_t* out_idx, float* out_dist, uint32_t* out_rank /* nullable */,
+                             uint32_t* out_count);
+/* The number of pair distances D(i, p) the last bsr_local_top_k_deep_mmr call computed, summed over
+ * its queries (0 before any such call).  Computing a full column per pick, as bsr_local_top_k_mmr
+ * does, would take the sum over the queries of (picks - 1) * m. */
+int bsr_index_last_mmr_pairs(const bsr_index* ix, uint64_t* out_pairs);
 
 /* ---- The merge of per-rank capped (or collapsed: per_group = 1) lists.  Layout and
  * null rules are bsr_global_top_k's, with group[(l*n_queries+q)*k_in ..] the group ids beside idx
