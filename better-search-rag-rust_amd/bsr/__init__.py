@@ -177,6 +177,8 @@ def lib() -> ctypes.CDLL:
         "bsr_local_top_k_deep": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_deep_masked": (ctypes.c_int, [_P, _P, u32, u32, _P, u64, u32, _P, u32, _P, _P, _P]),
         "bsr_local_top_k_deep_capped": (ctypes.c_int, [_P, _P, u32, u32, u32, _P, u64, u32, _P, _P, _P, _P]),
+        "bsr_local_top_k_deep_capped_masked": (ctypes.c_int, [_P, _P, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32,
+                                                              _P, _P, _P, _P]),
         "bsr_global_top_k": (ctypes.c_int, [_P, _P, _P, u32, u32, u32, u32, _P, _P, _P]),
         "bsr_global_top_k_capped": (ctypes.c_int, [_P, _P, _P, _P, u32, u32, u32, u32, u32, _P, _P, _P, _P]),
         "bsr_comm_unique_id": (ctypes.c_int, [_P]),
@@ -204,7 +206,7 @@ def lib() -> ctypes.CDLL:
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
                 "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids",
                 "bsr_local_top_groups", "bsr_local_top_k_deep", "bsr_local_top_k_deep_masked",
-                "bsr_local_top_k_deep_capped", "bsr_local_top_k_deep_mmr", "bsr_index_last_mmr_pairs"}
+                "bsr_local_top_k_deep_capped", "bsr_local_top_k_deep_capped_masked", "bsr_local_top_k_deep_mmr", "bsr_index_last_mmr_pairs"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -652,12 +654,21 @@ class Index:
                                                  _ptr(out_dist), _ptr(out_count)))
 
     def deep_capped_search(self, queries, k: int, row_group, per_group: int = 1, n_groups=None,
-                           return_groups: bool = False):
+                           return_groups: bool = False, allow_mask=None, allow_ids=None, allow_masks=None,
+                           query_mask=None, mask_mode="auto"):
         """capped_search for k up to BSR_DEEP_MAX_K (bsr_local_top_k_deep_capped), not bounded by
         max_k -> (idx [Q,k] u64, dist [Q,k] f32, count [Q] u32[, group [Q,k] u32]).  row_group and
         n_groups: as capped_search's.  Row q holds the first k live rows in (distance asc, index asc)
         order that have fewer than per_group rows of their group ahead of them; per_group = 1 (the
-        default) is the k nearest distinct groups.  No fetch_k and no masks."""
+        default) is the k nearest distinct groups.  No fetch_k.
+        Restricted to allowed rows (bsr_local_top_k_deep_capped_masked): allow_mask / allow_ids,
+        allow_masks with query_mask and mask_mode as deep_search's; the rule then runs over the
+        live rows the query's mask allows."""
+        one = allow_mask is not None or allow_ids is not None
+        if one and (allow_masks is not None or query_mask is not None):
+            raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
+        if (allow_masks is None) != (query_mask is None):
+            raise BsrError(-1, "allow_masks and query_mask go together")
         per_group = int(per_group)
         if per_group < 1 or per_group > BSR_CAP_MAX_PER_GROUP:
             raise BsrError(-1, f"per_group={per_group} outside 1 <= per_group <= {BSR_CAP_MAX_PER_GROUP}")
@@ -674,19 +685,46 @@ class Index:
         od = np.empty((nq, k), np.float32)
         oc = np.empty(nq, np.uint32)
         og = np.empty((nq, k), np.uint32) if return_groups else None
-        _check(lib().bsr_local_top_k_deep_capped(self._h, _ptr(q), nq, k, per_group, _ptr(rg), n_rg, ng, _ptr(oi),
-                                                 _ptr(od), _ptr(og), _ptr(oc)))
+        if not one and allow_masks is None:
+            _check(lib().bsr_local_top_k_deep_capped(self._h, _ptr(q), nq, k, per_group, _ptr(rg), n_rg, ng, _ptr(oi),
+                                                     _ptr(od), _ptr(og), _ptr(oc)))
+            return (oi, od, oc, og) if return_groups else (oi, od, oc)
+        if one:
+            w, nw = self._allow_words(allow_mask, allow_ids)
+            n_masks, qm = 1, None
+        else:
+            w, n_masks, nw = self._allow_group_words(allow_masks)
+            qm = self._query_mask_ids(query_mask, nq)
+        # (an empty shard's masks have no words: a valid, non-null pointer all the same)
+        wp = _ptr(w) if nw and n_masks else _ptr(np.zeros(1, np.uint64))
+        _check(lib().bsr_local_top_k_deep_capped_masked(self._h, _ptr(q), nq, k, per_group, _ptr(rg), n_rg, ng, wp, nw,
+                                                        n_masks, _ptr(qm), _mask_mode(mask_mode), _ptr(oi), _ptr(od),
+                                                        _ptr(og), _ptr(oc)))
         return (oi, od, oc, og) if return_groups else (oi, od, oc)
 
     def deep_capped_search_device(self, queries, nq: int, k: int, per_group: int, row_group, n_groups: int, out_idx,
-                                  out_dist, out_count, out_group=None):
+                                  out_dist, out_count, out_group=None, allow_words=None, query_mask=None,
+                                  mask_mode="auto"):
         """Zero-copy variant of deep_capped_search on caller buffers (torch tensors, numpy arrays or
         raw pointers, each host or device): queries [nq][dim] f32, row_group [n] 32-bit group ids,
-        out_idx / out_dist / out_group (optional) [nq][k], out_count [nq]."""
+        out_idx / out_dist / out_group (optional) [nq][k], out_count [nq].  allow_words and
+        query_mask: as deep_search_device's."""
         n_rg = int(row_group.numel()) if hasattr(row_group, "numel") else int(row_group.size)
-        _check(lib().bsr_local_top_k_deep_capped(self._h, _ptr(queries), nq, k, int(per_group), _ptr(row_group), n_rg,
-                                                 int(n_groups), _ptr(out_idx), _ptr(out_dist), _ptr(out_group),
-                                                 _ptr(out_count)))
+        if allow_words is None:
+            if query_mask is not None:
+                raise BsrError(-1, "a query_mask needs allow_words")
+            _check(lib().bsr_local_top_k_deep_capped(self._h, _ptr(queries), nq, k, int(per_group), _ptr(row_group),
+                                                     n_rg, int(n_groups), _ptr(out_idx), _ptr(out_dist),
+                                                     _ptr(out_group), _ptr(out_count)))
+            return
+        shape = tuple(allow_words.shape)
+        if len(shape) not in (1, 2):
+            raise BsrError(-1, "packed allow masks have shape [G][words] or [words]")
+        n_masks = int(shape[0]) if len(shape) == 2 else 1
+        _check(lib().bsr_local_top_k_deep_capped_masked(self._h, _ptr(queries), nq, k, int(per_group), _ptr(row_group),
+                                                        n_rg, int(n_groups), _ptr(allow_words), int(shape[-1]), n_masks,
+                                                        _ptr(query_mask), _mask_mode(mask_mode), _ptr(out_idx),
+                                                        _ptr(out_dist), _ptr(out_group), _ptr(out_count)))
 
     def range_search(self, queries, radius, max_results: int = 256, allow_mask=None, allow_ids=None,
                      allow_masks=None, query_mask=None, mask_mode="auto"):

@@ -75,6 +75,12 @@ int bsr_local_top_k_capped_impl(bsr_index* ix, const float* queries, uint32_t nq
 int bsr_local_top_k_deep_capped_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t per_group,
                                      const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
                                      uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_count);
+int bsr_local_top_k_deep_capped_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k,
+                                            uint32_t per_group, const uint32_t* row_group, uint64_t row_group_len,
+                                            uint32_t n_groups, const uint64_t* allow, uint64_t allow_words,
+                                            uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
+                                            uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                            uint32_t* out_count);
 int bsr_local_top_groups_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t group_size,
                               uint32_t fetch_k, const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
                               const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
@@ -486,6 +492,16 @@ int bsr_local_top_k_deep_capped(bsr_index* ix, const float* queries, uint32_t n_
                                 uint32_t* out_count) {
     BSR_GUARD(bsr_local_top_k_deep_capped_impl(ix, queries, n_queries, k, per_group, row_group, row_group_len, n_groups,
                                                out_idx, out_dist, out_group, out_count));
+}
+
+int bsr_local_top_k_deep_capped_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                                       uint32_t per_group, const uint32_t* row_group, uint64_t row_group_len,
+                                       uint32_t n_groups, const uint64_t* allow, uint64_t allow_words,
+                                       uint32_t n_masks, const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx,
+                                       float* out_dist, uint32_t* out_group, uint32_t* out_count) {
+    BSR_GUARD(bsr_local_top_k_deep_capped_masked_impl(ix, queries, n_queries, k, per_group, row_group, row_group_len,
+                                                      n_groups, allow, allow_words, n_masks, query_mask, mode, out_idx,
+                                                      out_dist, out_group, out_count));
 }
 
 int bsr_local_top_groups(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k, uint32_t group_size,

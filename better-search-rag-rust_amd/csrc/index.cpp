@@ -2781,8 +2781,12 @@ static uint32_t deep_masked_ks(uint32_t k, uint64_t live, uint64_t A) {
 // it merges the workgroups' lists with the query's carry -- deep_carry[q], its k best keys so far,
 // kKeyNone before the first segment -- and writes the carry again, so that after the last chunk
 // the carry of every listed query holds its k best keys over its whole list.
+// With groups (dgrp non-null): the capped list scan in groups of at most
+// kDeepCapScanQF queries and the capped selection without a bound behind it -- the carry holds the
+// first k kept keys, at most m_eff of a group.
 static int run_deep_list_scan(bsr_index* ix, uint32_t k, const uint64_t* allow, uint64_t words, uint32_t n_masks,
-                              const std::vector<uint32_t>& listed) {
+                              const std::vector<uint32_t>& listed, const uint32_t* dgrp = nullptr,
+                              uint32_t m_eff = 0) {
     const std::vector<uint32_t>& A = ix->h_grp_out;
     const QueriesByMask by = queries_by_mask(ix, n_masks, listed);
     const std::vector<uint32_t>& start = by.start;
@@ -2802,7 +2806,8 @@ static int run_deep_list_scan(bsr_index* ix, uint32_t k, const uint64_t* allow, 
     Chunk cur{0, 0, {}};
     auto close = [&]() {
         if (!cur.n_segs) return;
-        cur.launches = plan_query_groups(ix, segs.data() + cur.seg0, cur.n_segs, by, 65535, k, kDeepScanQF);
+        cur.launches = plan_query_groups(ix, segs.data() + cur.seg0, cur.n_segs, by, 65535, k,
+                                         dgrp ? kDeepCapScanQF : kDeepScanQF);
         for (const GroupLaunch& l : cur.launches)
             part_bytes = std::max(part_bytes, (size_t)l.groups * l.qf * (l.grid + 1) * k * sizeof(uint64_t));
         list_ids = std::max(list_ids, used);
@@ -2848,6 +2853,12 @@ static int run_deep_list_scan(bsr_index* ix, uint32_t k, const uint64_t* allow, 
     se.keys = la.part;
     se.k = k;
     se.out_keys = ix->deep_carry.as<uint64_t>();
+    DeepCapSelectArgs ce{};
+    ce.keys = la.part;
+    ce.k = k;
+    ce.per_group = m_eff;
+    ce.row_group = dgrp;
+    ce.out_keys = se.out_keys;
     ev_begin(ix, ix->ev_scan, 1);
     for (const Chunk& c : chunks) {
         // (the stream orders a chunk's scatter behind the scans of the chunk before it)
@@ -2862,6 +2873,16 @@ static int run_deep_list_scan(bsr_index* ix, uint32_t k, const uint64_t* allow, 
             se.n_items = l.groups * l.qf;
             se.stride = (uint64_t)(l.grid + 1) * k;
             se.n_keys = (l.grid + 1) * k;
+            if (dgrp) {
+                ce.grp = la.grp;
+                ce.qids = la.qids;
+                ce.qf = l.qf;
+                ce.nq = se.n_items;
+                ce.cap = se.n_keys;
+                BSR_HIP(launch_deep_cap_scan_list(DeepCapListArgs{la, dgrp, m_eff}, l.grid, ix->stream));
+                BSR_HIP(launch_deep_cap_select(ce, ix->stream));
+                continue;
+            }
             BSR_HIP(launch_deep_scan_list(la, l.grid, ix->stream));
             BSR_HIP(launch_deep_select(se, ix->stream));
         }
@@ -2872,18 +2893,25 @@ static int run_deep_list_scan(bsr_index* ix, uint32_t k, const uint64_t* allow, 
 
 int bsr_index::deep_search_device_masked(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
                                          uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
-                                         uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_count) {
+                                         uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_count,
+                                         const DeepCap* cap) {
     bsr_index* ix = this;
     BSR_TRY(check_batch(ix, 1));  // (loaded; k has its own bound, checked by the entry point)
     if (allow_words != (n + 63) / 64)
         return set_error(BSR_E_INVALID, "allow_words=%llu, the index holds %llu rows (%llu words)",
                          (unsigned long long)allow_words, (unsigned long long)n, (unsigned long long)((n + 63) / 64));
-    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_DEEP | (query_mask ? BSR_PATH_MASK_GROUPS : 0u)));
+    BSR_TRY(begin_batch(ix, nq, 1, BSR_PATH_DEEP | (cap ? BSR_PATH_CAP : 0u) | (query_mask ? BSR_PATH_MASK_GROUPS : 0u)));
     if (nq == 0) return BSR_OK;
 
     const uint32_t qpad = qpad_for(nq);
     const size_t nk = (size_t)nq * k;
+    const uint32_t m_eff = cap ? std::min(cap->per_group, k) : 0u;
     BSR_TRY(query_buffers(ix, nq, qpad, 1));
+    if (cap) {
+        BSR_TRY(col_flag.ensure(2 * sizeof(uint32_t)));
+        BSR_TRY(col_qids.ensure((size_t)nq * sizeof(int32_t)));
+        BSR_TRY(col_group.ensure(nk * sizeof(uint32_t)));
+    }
     BSR_TRY(mask_aux.ensure(((size_t)qpad + 1) * sizeof(uint32_t)));
     BSR_TRY(deep_carry.ensure(nk * sizeof(uint64_t)));
     BSR_TRY(deep_idx.ensure(nk * sizeof(uint64_t)));
@@ -2923,6 +2951,19 @@ int bsr_index::deep_search_device_masked(const float* queries, uint32_t nq, uint
     if (dqmask && h_grp_out[n_masks])
         return set_error(BSR_E_INVALID, "%u entries of query_mask name no mask (n_masks = %u)", h_grp_out[n_masks],
                          n_masks);
+    // (capped) The groups on the device and their check, before anything indexes a hash with one.
+    const uint32_t* dgrp = nullptr;
+    if (cap && n) {
+        uint32_t* const flag = col_flag.as<uint32_t>();
+        BSR_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(uint32_t), stream));
+        BSR_TRY(on_device(ix, col_grp, cap->row_group, (size_t)n * sizeof(uint32_t), is_device_ptr(cap->row_group),
+                          &dgrp));
+        BSR_HIP(launch_group_check(dgrp, n, cap->n_groups, flag, stream));
+        uint32_t bad = 0;
+        BSR_HIP(hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, stream));
+        BSR_HIP(hipStreamSynchronize(stream));
+        if (bad) return set_error(BSR_E_INVALID, "a row_group entry is >= n_groups = %u", cap->n_groups);
+    }
 
     // 2. The path of every mask group, from its own A_g and query count: the filter rung where the
     // threshold can be lowered to the group's depth, the list scan elsewhere.
@@ -3011,7 +3052,28 @@ int bsr_index::deep_search_device_masked(const float* queries, uint32_t nq, uint
         se.cap = cap_m;
         se.fail = fail.as<uint32_t>();
         se.status = d_status;
-        BSR_HIP(launch_deep_select(se, stream));
+        if (cap) {
+            // (capped) the capped walk of the keys below the exclusion bound: the cut left an exact
+            // prefix of the query's order over its mask, and k kept rows along it certify the query
+            DeepCapSelectArgs ce{};
+            ce.keys = ra.keys;
+            ce.kcnt = ra.rcnt;
+            ce.cap = cap_m;
+            ce.nq = nq;
+            ce.k = k;
+            ce.per_group = m_eff;
+            ce.row_group = dgrp;
+            ce.out_keys = se.out_keys;
+            ce.tau = se.tau;
+            ce.ebound = se.ebound;
+            ce.nb = se.nb;
+            ce.emit_cnt = raw_cnt;
+            ce.fail = se.fail;
+            ce.status = d_status;
+            BSR_HIP(launch_deep_cap_select(ce, stream));
+        } else {
+            BSR_HIP(launch_deep_select(se, stream));
+        }
         ev_end(ix, ev_rescore);
     }
     stats.n_candidates = cap_m;
@@ -3043,7 +3105,26 @@ int bsr_index::deep_search_device_masked(const float* queries, uint32_t nq, uint
     std::vector<uint32_t> listed;
     for (uint32_t q = 0; q < nq; ++q)
         if (on_list[q]) listed.push_back(q);
-    BSR_TRY(run_deep_list_scan(ix, k, dallow, allow_words, n_masks, listed));
+    BSR_TRY(run_deep_list_scan(ix, k, dallow, allow_words, n_masks, listed, dgrp, m_eff));
+    if (cap) {
+        // 6. (capped) Every query's carry holds its first k kept keys, ascending (or none): the rows
+        // with their groups and counts, then one copy per output as below.
+        std::vector<int32_t> all(nq);
+        for (uint32_t q = 0; q < nq; ++q) all[q] = (int32_t)q;
+        BSR_HIP(hipMemcpyAsync(col_qids.p, all.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        BSR_HIP(hipStreamSynchronize(stream));  // (all is read by the copy)
+        BSR_HIP(launch_deep_cap_finish(deep_carry.as<uint64_t>(), col_qids.as<int32_t>(), nq, k, global_offset, dgrp,
+                                       deep_idx.as<uint64_t>(), deep_dist.as<float>(), col_group.as<uint32_t>(),
+                                       deep_ocnt.as<uint32_t>(), stream));
+        ev_end(ix, ev_total);
+        BSR_HIP(hipMemcpyAsync(out_idx, deep_idx.p, nk * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, deep_dist.p, nk * sizeof(float), hipMemcpyDefault, stream));
+        if (cap->out_group)
+            BSR_HIP(hipMemcpyAsync(cap->out_group, col_group.p, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, deep_ocnt.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipStreamSynchronize(stream));
+        return BSR_OK;
+    }
     // 6. Every query's carry holds its k best keys (or none): one selection writes the result rows.
     DeepSelectArgs fe{};
     fe.keys = deep_carry.as<uint64_t>();
@@ -3712,6 +3793,49 @@ int bsr_local_top_k_deep_capped_impl(bsr_index* ix, const float* queries, uint32
     if (nq == 0) return BSR_OK;
     BSR_TRY(ix->deep_capped_search_device(queries, nq, k, per_group, row_group, n_groups, out_idx, out_dist, out_group,
                                           out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
+// Masked deep capped search (bsr_local_top_k_deep_capped_masked): the masked deep
+// search's ladder with a cap (deep_search_device_masked above).  The checks are the union of the
+// two parents', in their order.
+int bsr_local_top_k_deep_capped_masked_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k,
+                                            uint32_t per_group, const uint32_t* row_group, uint64_t row_group_len,
+                                            uint32_t n_groups, const uint64_t* allow, uint64_t allow_words,
+                                            uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
+                                            uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                            uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (k == 0 || k > BSR_DEEP_MAX_K) return set_error(BSR_E_INVALID, "k=%u outside [1, %u]", k, BSR_DEEP_MAX_K);
+    if (per_group == 0 || per_group > BSR_CAP_MAX_PER_GROUP)
+        return set_error(BSR_E_INVALID, "per_group=%u outside 1 <= per_group <= %u", per_group, BSR_CAP_MAX_PER_GROUP);
+    if (n_groups == 0) return set_error(BSR_E_INVALID, "n_groups = 0");
+    if ((uint64_t)std::min(per_group, k) * n_groups > 0xFFFFFFFFull)
+        return set_error(BSR_E_INVALID, "min(per_group, k) * n_groups = %u * %u exceeds 2^32 - 1", std::min(per_group, k),
+                         n_groups);
+    if (n_masks == 0)
+        return set_error(BSR_E_INVALID, "n_masks = 0 (bsr_local_top_k_deep_capped searches without a mask)");
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (!query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (nq && !allow) return set_error(BSR_E_INVALID, "null allow masks");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (allow_words != (ix->n + 63) / 64)
+        return set_error(BSR_E_INVALID, "allow_words=%llu, the index holds %llu rows (%llu words)",
+                         (unsigned long long)allow_words, (unsigned long long)ix->n,
+                         (unsigned long long)((ix->n + 63) / 64));
+    if (row_group_len != ix->n)
+        return set_error(BSR_E_INVALID, "row_group_len=%llu, the index holds %llu rows", (unsigned long long)row_group_len,
+                         (unsigned long long)ix->n);
+    if (ix->n && !row_group) return set_error(BSR_E_INVALID, "null row_group");
+    if (nq == 0) return BSR_OK;
+    const bsr_index::DeepCap cap{per_group, row_group, n_groups, out_group};
+    BSR_TRY(ix->deep_search_device_masked(queries, nq, k, allow, allow_words, n_masks, query_mask, mode, out_idx,
+                                          out_dist, out_count, &cap));
     collect_profile(ix);
     return BSR_OK;
 }

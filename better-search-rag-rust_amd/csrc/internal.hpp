@@ -288,10 +288,21 @@ struct bsr_index {
     // mask per query group -- the grouped masked search's mask buffers (grp_*), the list segments of
     // the masked range search (rng_segs), the deep search's key and result buffers (deep_*), and the
     // carry of a list scan in chunks.  Launched directly, never captured.
+    // With a cap (bsr_local_top_k_deep_capped_masked; null: none) the same ladder keeps
+    // "the first k kept keys" wherever it kept "the k smallest": the capped selection behind the
+    // rescore, the capped list scan and its capped merge into the carry, and the finish that adds the
+    // groups (col_grp, col_flag, col_qids, col_group are the capped search's).
+    struct DeepCap {
+        uint32_t per_group;
+        const uint32_t* row_group;  // [n], host or device
+        uint32_t n_groups;
+        uint32_t* out_group;        // [nq][k], nullable
+    };
     int deep_search_device_masked(const float* queries, uint32_t nq, uint32_t k, const uint64_t* allow,
                                   uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
-                                  uint64_t* out_idx, float* out_dist, uint32_t* out_count);
-    bsr::DevBuf deep_carry;  // u64 [nq][k]: a listed query's k best keys of the segments scanned so far
+                                  uint64_t* out_idx, float* out_dist, uint32_t* out_count,
+                                  const DeepCap* cap = nullptr);
+    bsr::DevBuf deep_carry;  // u64 [nq][k]: a listed query's k best (capped: first k kept) keys of the segments so far
 
     // MMR search (bsr_local_top_k_mmr): the candidate search with k = fetch_k (plain,
     // masked or grouped, by the mask arguments) run to completion, then the selection kernel over the

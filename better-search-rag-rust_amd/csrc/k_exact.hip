@@ -2231,13 +2231,65 @@ __device__ __forceinline__ void deep_list_walk(float* st, float* ldq, const floa
     }
 }
 
-template <int QF>
-__global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan_list(DeepListArgs a) {
+// The capped walk of k_deep_cap_select and k_deep_cap_scan_list, one wave: sk[0 .. n) ascending with w_grp[j] the group of sk[j], the hash (g_key:
+// ~0u = empty, g_cnt: kCapHash slots for at most kDeepMaxK kept groups) holding the kept rows of the
+// windows before, o the rows kept so far.  A kept
+// lane calls emit(result slot, key, group); emit may store to sk below the step's first slot + its
+// lane (every lane has read its key by then).  Returns the rows kept, at most k.
+constexpr uint32_t kCapHash = 2 * kDeepMaxK;
+static_assert(kCapHash == 2048, "cap_hash_slot keeps 11 bits");
+__device__ __forceinline__ uint32_t cap_hash_slot(uint32_t g) { return (g * 0x9E3779B1u) >> 21; }
+template <class Emit>
+__device__ __forceinline__ uint32_t cap_walk(const uint64_t* sk, const uint32_t* w_grp, uint32_t n, uint32_t* g_key,
+                                             uint32_t* g_cnt, uint32_t m, uint32_t k, uint32_t o, int lane, Emit emit) {
+    constexpr uint32_t HS = kCapHash;
+    // (the hash is read with relaxed atomic loads, never cached in registers over a step; a volatile
+    // access through a pointer parameter would hide the LDS address space from the compiler)
+    auto peek = [](const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+    for (uint32_t base = 0; base < n && o < k; base += kWave) {
+        const uint32_t j = base + lane;
+        const bool have = j < n;  // (the lanes without a slot are the step's last)
+        const uint64_t key = have ? sk[j] : 0ull;
+        const uint32_t g = have ? w_grp[j] : ~0u;
+        uint32_t gc = 0;  // kept rows of the lane's group in the steps before
+        if (have)
+            for (uint32_t sl = cap_hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
+                const uint32_t v = peek(&g_key[sl]);
+                if (v == g) gc = peek(&g_cnt[sl]);
+                if (v == g || v == ~0u) break;
+            }
+        uint32_t before = 0;  // earlier lanes of the step with the lane's group
+#pragma unroll
+        for (int l = 0; l < kWave - 1; ++l)
+            before += (l < lane && (uint32_t)__builtin_amdgcn_readlane((int)g, l) == g) ? 1u : 0u;
+        const bool kept = have && gc + before < m;
+        const uint64_t mk = __ballot(kept);
+        const uint32_t slot =
+            o + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        if (kept && slot < k) {
+            emit(slot, key, g);
+            for (uint32_t sl = cap_hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
+                const uint32_t prev = atomicCAS(&g_key[sl], ~0u, g);
+                if (prev == ~0u || prev == g) {
+                    atomicAdd(&g_cnt[sl], 1u);
+                    break;
+                }
+            }
+        }
+        o += (uint32_t)__popcll(mk);
+        o = o < k ? o : k;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (the next step reads the hash)
+    }
+    return o;
+}
+
+// The body of a deep list scan: the tile loop, the claims, the final lists.  compact(j) cuts buffer j
+// (k_deep_scan_list: to its k smallest keys; k_deep_cap_scan_list: to its first k kept keys), sets
+// s_cnt[j] and s_thr[j], and ends behind a barrier.  lds: 4 row stages + 4 x QF query chunks.
+template <int QF, class Compact>
+__device__ __forceinline__ void deep_list_scan(const DeepListArgs& a, float* lds, uint64_t (*buf)[kDeepScanBuf],
+                                               uint64_t* s_thr, uint32_t* s_cnt, Compact compact) {
     constexpr int STAGE = 64 * 68;
-    __shared__ __attribute__((aligned(16))) float lds[4 * STAGE + 4 * QF * 64];
-    __shared__ uint64_t buf[QF][kDeepScanBuf];
-    __shared__ uint64_t s_thr[QF];
-    __shared__ uint32_t s_cnt[QF];
     const ScanGroupDesc me = a.grp[blockIdx.y];
     const uint32_t* __restrict__ list = a.list + me.off;
     const uint32_t n_list = me.n_list, k = a.k;
@@ -2284,12 +2336,12 @@ __global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan_list(DeepListAr
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < QF; ++j)
-            if (s_cnt[j] > kDeepScanBuf - 256u) deep_scan_compact(buf[j], &s_cnt[j], &s_thr[j], k, t);
+            if (s_cnt[j] > kDeepScanBuf - 256u) compact(j);
         __syncthreads();  // (no wave claims a slot of the next tile while another still reads the counts)
     }
     const uint64_t lists = (uint64_t)gridDim.x + 1;
     for (int j = 0; j < QF && (uint32_t)j < me.nq; ++j) {
-        deep_scan_compact(buf[j], &s_cnt[j], &s_thr[j], k, t);
+        compact(j);
         const uint32_t n = s_cnt[j];
         uint64_t* const slot0 = a.part + ((uint64_t)blockIdx.y * QF + j) * lists * k;
         uint64_t* const dst = slot0 + ((uint64_t)blockIdx.x + 1) * k;
@@ -2297,6 +2349,67 @@ __global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan_list(DeepListAr
         if (blockIdx.x == 0)
             for (uint32_t i = t; i < k; i += 256) slot0[i] = a.carry[(uint64_t)id[j] * k + i];
     }
+}
+
+template <int QF>
+__global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_scan_list(DeepListArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[4 * 64 * 68 + 4 * QF * 64];
+    __shared__ uint64_t buf[QF][kDeepScanBuf];
+    __shared__ uint64_t s_thr[QF];
+    __shared__ uint32_t s_cnt[QF];
+    deep_list_scan<QF>(a, lds, buf, s_thr, s_cnt,
+                       [&](int j) { deep_scan_compact(buf[j], &s_cnt[j], &s_thr[j], a.k, threadIdx.x); });
+}
+
+// The deep capped list scan (bsr_local_top_k_deep_capped_masked): k_deep_scan_list
+// with "the first k kept keys" in the place of "the k smallest".  A key of the list is kept when
+// fewer than m = min(per_group, k) keys of its group precede it in the list's (distance, row) order.
+// A full buffer is sorted, the group of every slot loaded beside it (row_group[row]: only keys are
+// ever held), and wave 0 walks it with cap_walk against an LDS hash that starts empty -- the buffer
+// holds every key of the rows seen so far that can still be kept, so the walk of the buffer alone
+// decides -- moving the kept keys to the front; with k kept, the k-th is the threshold.  Exact
+// because (§29): a row above the k-th kept key of any subset is never among the first k kept; a
+// dropped row stays dropped when rows are added; a row among the first k kept of the whole list is
+// among the first k kept of every subset that holds it.  The workgroup's list is its kept keys, the
+// union of the lists and the carry goes through launch_deep_cap_select without a bound.
+// One hash and one array of slot groups serve the group's queries, whose compactions run one after
+// the other.  LDS: 68 KB of row stages + QF KB of query chunks + QF x 18 KB of keys + 16 KB of hash +
+// 9 KB of slot groups: 131 KB at QF = 2, 112 KB at 1 (QF = 4 would take 169 KB of a CU's 160).
+__device__ __forceinline__ void deep_cap_compact(uint64_t* buf, uint32_t* cnt, uint64_t* thr, uint32_t* w_grp,
+                                                 uint32_t* g_key, uint32_t* g_cnt,
+                                                 const uint32_t* __restrict__ row_group, uint32_t k, uint32_t m,
+                                                 uint32_t t) {
+    const uint32_t n = *cnt < kDeepScanBuf ? *cnt : kDeepScanBuf;
+    lds_sort_inplace(buf, n, t);
+    for (uint32_t j = t; j < n; j += 256) w_grp[j] = row_group[key_row(buf[j])];
+    for (uint32_t i = t; i < kCapHash; i += 256) {
+        g_key[i] = ~0u;
+        g_cnt[i] = 0;
+    }
+    __syncthreads();
+    if (t < (uint32_t)kWave) {
+        const uint32_t o = cap_walk(buf, w_grp, n, g_key, g_cnt, m, k, 0u, (int)t,
+                                    [&](uint32_t slot, uint64_t key, uint32_t) { buf[slot] = key; });
+        if (t == 0) {
+            *cnt = o;
+            if (o >= k) *thr = buf[k - 1];
+        }
+    }
+    __syncthreads();
+}
+template <int QF>
+__global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_deep_cap_scan_list(DeepCapListArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[4 * 64 * 68 + 4 * QF * 64];
+    __shared__ uint64_t buf[QF][kDeepScanBuf];
+    __shared__ uint32_t w_grp[kDeepScanBuf];
+    __shared__ uint32_t g_key[kCapHash];
+    __shared__ uint32_t g_cnt[kCapHash];
+    __shared__ uint64_t s_thr[QF];
+    __shared__ uint32_t s_cnt[QF];
+    deep_list_scan<QF>(a.l, lds, buf, s_thr, s_cnt, [&](int j) {
+        deep_cap_compact(buf[j], &s_cnt[j], &s_thr[j], w_grp, g_key, g_cnt, a.row_group, a.l.k, a.per_group,
+                         threadIdx.x);
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -2630,6 +2743,12 @@ __global__ __launch_bounds__(256) BSR_NO_PK_F32 void k_merge_wide(MergeWideArgs 
 // hash slots.  The walk ends at k rows: the query is certified, its count is k.  A query whose keys
 // below B run out first, whose list overflowed or whose bound certifies nothing (B = -inf) joins
 // the fail list; the rows it wrote are the scan's to overwrite.
+// With a.tau null there is no bound: every key is a candidate, the walk ends at k kept keys or at
+// the last key, and nothing fails -- the merge of a deep capped list scan's kept lists.  With
+// a.out_keys the kept keys are written, not the row: q's carry, kKeyNone behind them (a failed
+// query's carry is cleared).  a.qids / a.grp / a.qf are DeepSelectArgs'.
+//
+// The walk itself is cap_walk, above.
 __global__ __launch_bounds__(256) void k_deep_cap_select(DeepCapSelectArgs a) {
     constexpr uint32_t BINS = 2048, PER = BINS / 256, HS = 2 * kDeepMaxK, WIN = kDeepSortKeys;
     __shared__ uint64_t sk[WIN];
@@ -2639,17 +2758,22 @@ __global__ __launch_bounds__(256) void k_deep_cap_select(DeepCapSelectArgs a) {
     __shared__ uint32_t hist[BINS];
     __shared__ uint32_t s_scan[256];
     __shared__ uint32_t s_n, s_bin, s_taken, s_out;
-    const uint32_t q = blockIdx.x, t = threadIdx.x;
+    const uint32_t item = blockIdx.x, t = threadIdx.x;
+    if (a.grp && item % a.qf >= a.grp[item / a.qf].nq) return;  // (a padding slot of a query group)
+    const uint32_t q = a.qids ? (uint32_t)a.qids[item] : item;
     const int lane = t & 63;
     const uint32_t k = a.k, m = a.per_group;
+    const bool bounded = a.tau != nullptr;
     auto fail = [&]() {
+        if (a.out_keys)  // (the keys it wrote are not its carry: the list scan starts from none)
+            for (uint32_t i = t; i < k; i += 256) a.out_keys[(uint64_t)q * k + i] = kKeyNone;
         if (t == 0) a.fail[atomicAdd(a.status + kStFail, 1u)] = q;
     };
-    if (a.emit_cnt[q] > a.cap) return fail();  // (rows were dropped; uniform over the workgroup)
-    const float B = exclusion_bound(a.tau[q], a.ebound[q], a.nb[q]);
+    if (bounded && a.emit_cnt[q] > a.cap) return fail();  // (rows were dropped; uniform over the workgroup)
+    const float B = bounded ? exclusion_bound(a.tau[q], a.ebound[q], a.nb[q]) : INFINITY;
     if (!(B > 0.0f)) return fail();            // (no distance lies below it)
-    const uint64_t* __restrict__ src = a.keys + (uint64_t)q * a.cap;
-    const uint32_t c = a.kcnt[q] < a.cap ? a.kcnt[q] : a.cap;
+    const uint64_t* __restrict__ src = a.keys + (uint64_t)item * a.cap;
+    const uint32_t c = a.kcnt && a.kcnt[q] < a.cap ? a.kcnt[q] : a.cap;
     const uint32_t c_up = (c + 255u) & ~255u;  // (every lane of a wave takes every trip: ballots)
     for (uint32_t i = t; i < HS; i += 256) {
         g_key[i] = ~0u;
@@ -2657,8 +2781,7 @@ __global__ __launch_bounds__(256) void k_deep_cap_select(DeepCapSelectArgs a) {
     }
     if (t == 0) s_out = 0;
     __syncthreads();
-    auto hash_slot = [](uint32_t g) -> uint32_t { return (g * 0x9E3779B1u) >> 21; };  // (11 bits: HS slots)
-    static_assert(HS == 2048, "hash_slot keeps 11 bits");
+    static_assert(HS == kCapHash, "cap_walk's hash");
 
     uint64_t lo = 0;    // the last window's limit: the keys up to it are walked ...
     bool first = true;  // ... none yet
@@ -2670,7 +2793,7 @@ __global__ __launch_bounds__(256) void k_deep_cap_select(DeepCapSelectArgs a) {
         // key i of the list when it is still to be walked
         auto load = [&](uint32_t i, uint64_t& key) __attribute__((always_inline)) -> bool {
             key = i < c ? src[i] : kKeyNone;
-            return key != kKeyNone && key_dist(key) < B && (first || key > lo);
+            return key != kKeyNone && (!bounded || key_dist(key) < B) && (first || key > lo);
         };
         uint64_t limit = kKeyNone;  // the window takes the keys <= limit
         if (c <= WIN) {
@@ -2750,54 +2873,30 @@ __global__ __launch_bounds__(256) void k_deep_cap_select(DeepCapSelectArgs a) {
         for (uint32_t j = t; j < n; j += 256) w_grp[j] = a.row_group[key_row(sk[j])];
         __syncthreads();
         if (t < (uint32_t)kWave) {
-            volatile uint32_t* const vg = g_key;
-            volatile uint32_t* const vc = g_cnt;
-            uint32_t o = out;
-            for (uint32_t base = 0; base < n && o < k; base += kWave) {
-                const uint32_t j = base + lane;
-                const bool have = j < n;  // (the lanes without a slot are the step's last)
-                const uint64_t key = have ? sk[j] : 0ull;
-                const uint32_t g = have ? w_grp[j] : ~0u;
-                uint32_t gc = 0;  // kept rows of the lane's group in the steps before
-                if (have)
-                    for (uint32_t sl = hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
-                        const uint32_t v = vg[sl];
-                        if (v == g) gc = vc[sl];
-                        if (v == g || v == ~0u) break;
-                    }
-                uint32_t before = 0;  // earlier lanes of the step with the lane's group
-#pragma unroll
-                for (int l = 0; l < kWave - 1; ++l)
-                    before += (l < lane && (uint32_t)__builtin_amdgcn_readlane((int)g, l) == g) ? 1u : 0u;
-                const bool kept = have && gc + before < m;
-                const uint64_t mk = __ballot(kept);
-                const uint32_t slot =
-                    o + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                if (kept && slot < k) {
-                    const uint64_t p = (uint64_t)q * k + slot;
-                    a.out_idx[p] = a.offset + key_row(key);
-                    a.out_dist[p] = key_dist(key);
-                    a.out_group[p] = g;
-                    for (uint32_t sl = hash_slot(g);; sl = (sl + 1) & (HS - 1u)) {
-                        const uint32_t prev = atomicCAS(&g_key[sl], ~0u, g);
-                        if (prev == ~0u || prev == g) {
-                            atomicAdd(&g_cnt[sl], 1u);
-                            break;
-                        }
-                    }
+            const uint32_t o = cap_walk(sk, w_grp, n, g_key, g_cnt, m, k, out, lane,
+                                        [&](uint32_t slot, uint64_t key, uint32_t g) {
+                const uint64_t p = (uint64_t)q * k + slot;
+                if (a.out_keys) {  // (a merge of kept lists, or the masked filter rung: keys, no row yet)
+                    a.out_keys[p] = key;
+                    return;
                 }
-                o += (uint32_t)__popcll(mk);
-                o = o < k ? o : k;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (the next step reads the hash)
-            }
+                a.out_idx[p] = a.offset + key_row(key);
+                a.out_dist[p] = key_dist(key);
+                a.out_group[p] = g;
+            });
             if (lane == 0) s_out = o;
         }
         __syncthreads();
         lo = limit;
         first = false;
     }
-    if (s_out < k) return fail();  // (uniform: read behind a barrier, or 0 < k from the start)
-    if (t == 0) a.out_count[q] = k;
+    const uint32_t out = s_out;  // (uniform: read behind a barrier, or 0 < k from the start)
+    if (!bounded) {  // every key was a candidate: the kept keys are the whole answer, however few
+        for (uint32_t i = out + t; i < k; i += 256) a.out_keys[(uint64_t)q * k + i] = kKeyNone;
+        return;
+    }
+    if (out < k) return fail();
+    if (t == 0 && a.out_count) a.out_count[q] = k;
 }
 
 // One workgroup per scanned query of a round: its k smallest table keys [.][k] (ascending, kKeyNone
@@ -3666,6 +3765,20 @@ hipError_t launch_deep_scan_list(const DeepListArgs& a, uint32_t grid, hipStream
     return hipGetLastError();
 }
 
+hipError_t launch_deep_cap_scan_list(const DeepCapListArgs& a, uint32_t grid, hipStream_t s) {
+    const DeepListArgs& l = a.l;
+    if (!grid || !l.groups || l.groups > 65535 || !l.k || l.k > kDeepMaxK || l.ld == 0 || l.ld % 64 != 0 ||
+        l.dim > l.ld || !l.list || !l.grp || !l.qids || !l.part || !l.carry || !a.row_group || !a.per_group)
+        return hipErrorInvalidValue;
+    const dim3 g(grid, l.groups);
+    switch (l.qf) {
+        case 1: hipLaunchKernelGGL(k_deep_cap_scan_list<1>, g, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_deep_cap_scan_list<2>, g, dim3(256), 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_deep_scan(const DeepScanArgs& a, uint32_t grid, hipStream_t s) {
     if (!grid || !a.nqf || a.nqf > kDeepScanQF || !a.k || a.k > kDeepMaxK || a.ld == 0 || a.ld % 64 != 0 ||
         a.dim > a.ld || a.n > 0xffffffffull)
@@ -3784,10 +3897,11 @@ hipError_t launch_cap_scan(const CapScanArgs& c, uint32_t grid, hipStream_t s) {
 
 // ---- deep capped search ----------------------------------------------------------------------
 hipError_t launch_deep_cap_select(const DeepCapSelectArgs& a, hipStream_t s) {
-    if (!a.nq || !a.k || a.k > kDeepMaxK || !a.per_group || !a.cap || !a.keys || !a.kcnt || !a.row_group ||
-        !a.out_idx || !a.out_dist || !a.out_group || !a.out_count || !a.tau || !a.ebound || !a.nb || !a.emit_cnt ||
-        !a.fail || !a.status)
+    if (!a.nq || !a.k || a.k > kDeepMaxK || !a.per_group || !a.cap || !a.keys || !a.row_group) return hipErrorInvalidValue;
+    if (!a.out_keys && (!a.out_idx || !a.out_dist || !a.out_group || !a.out_count)) return hipErrorInvalidValue;
+    if (a.tau ? !a.kcnt || !a.ebound || !a.nb || !a.emit_cnt || !a.fail || !a.status : !a.out_keys)
         return hipErrorInvalidValue;
+    if (a.grp && !a.qf) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_deep_cap_select, dim3(a.nq), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -899,8 +899,31 @@ struct DeepCapSelectArgs {
     const uint32_t* emit_cnt;
     uint32_t* fail;
     uint32_t* status;
+    // The masked deep capped search, all nullable; all null leaves the above.
+    uint64_t* out_keys;         // [.][k]: query q's kept keys ascending, kKeyNone behind them, instead of its
+                                //   result row and count (with tau: of a certified query; a failed one's are
+                                //   all kKeyNone)
+    const int32_t* qids;        // item i (workgroup i, keys + i * cap) is query qids[i] (null: query i)
+    const ScanGroupDesc* grp;   // item i is slot i % qf of group i / qf: only the slots below the
+    uint32_t qf;                //   group's nq count, the others write nothing
+    // tau == nullptr (out_keys required; ebound / nb / emit_cnt / fail / status unused, kcnt nullable:
+    // cap keys an item, kKeyNone = none): no bound -- every key is a candidate, the walk ends at k kept
+    // keys or behind the last key, no query fails.  The capped merge of a list scan's kept lists.
 };
 hipError_t launch_deep_cap_select(const DeepCapSelectArgs& a, hipStream_t s);
+// The deep capped list scan: launch_deep_scan_list's work split, lists, slots and
+// carry (l; l.qf one of 1, 2 = kDeepCapScanQF), but workgroup b's list 1 + b holds the first k KEPT
+// keys of its tiles -- a key is kept when fewer than per_group (>= 1; pass min(per_group, k)) keys of
+// its group row_group[row] precede it in the (distance, row) order of the workgroup's tiles.  The
+// first k kept keys of the union of a slot's lists are the first k kept of carry + segment: what
+// launch_deep_cap_select without a bound (cap = (grid + 1) * k, out_keys = the carry) leaves.
+constexpr uint32_t kDeepCapScanQF = 2;  // (LDS: QF x 18 KB of keys beside 25 KB of hash and slot groups)
+struct DeepCapListArgs {
+    DeepListArgs l;
+    const uint32_t* row_group;  // [n], every entry checked by launch_group_check
+    uint32_t per_group;
+};
+hipError_t launch_deep_cap_scan_list(const DeepCapListArgs& a, uint32_t grid, hipStream_t s);
 // launch_collapse_finish for k <= kDeepMaxK (out_group is not nullable here).
 hipError_t launch_deep_cap_finish(const uint64_t* keys, const int32_t* qids, uint32_t nqf, uint32_t k, uint64_t offset,
                                   const uint32_t* row_group, uint64_t* out_idx, float* out_dist, uint32_t* out_group,

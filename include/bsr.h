@@ -759,7 +759,7 @@ int bsr_local_top_k_deep(bsr_index* ix, const float* queries, uint32_t n_queries
  * scan_ms, the rescore and the selection in rescore_ms.
  * A multi-rank masked deep search: as bsr_local_top_k_deep's (device lists merge on the GPU with
  * bsr_global_top_k).
- * Out of scope: row groups with deep k under a mask (bsr_local_top_k_deep_capped takes no mask). */
+ * Row groups with deep k under a mask: bsr_local_top_k_deep_capped_masked below. */
 int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
                                 const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                                 const uint32_t* query_mask, /* [n_queries], nullable with one mask */
@@ -808,7 +808,7 @@ int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_
  * ids) and device outputs, out_group included; bsr_allgather_bytes of the four outputs on device
  * buffers; bsr_global_top_k_capped(k_in = k, per_group) on the gathered device arrays, which merges
  * lists of this depth on the GPU.
- * Out of scope: allow masks (the follow-up: the masked deep search's list scan with groups); the
+ * Allow masks: bsr_local_top_k_deep_capped_masked below.  Out of scope: the
  * group search (bsr_local_top_groups) at deep k; a per-query per_group; raising
  * BSR_CAP_MAX_PER_GROUP; a collective entry point. */
 int bsr_local_top_k_deep_capped(bsr_index* ix, const float* queries, uint32_t n_queries,
@@ -817,6 +817,61 @@ int bsr_local_top_k_deep_capped(bsr_index* ix, const float* queries, uint32_t n_
                                 uint64_t* out_idx, float* out_dist,    /* [n_queries][k] */
                                 uint32_t* out_group /* [n_queries][k], nullable */,
                                 uint32_t* out_count /* [n_queries] */);
+
+/* ---- Masked deep capped search: bsr_local_top_k_deep_capped under allow masks --
+ * "the 1000 nearest chunks of tenant T, at most 3 per document", "the 1000 nearest distinct documents
+ * of tenant T".  row_group, row_group_len and n_groups are taken as bsr_local_top_k_deep_capped takes
+ * them; allow, allow_words, n_masks, query_mask and mode as bsr_local_top_k_deep_masked takes them.
+ * Every array is, independently, a host or a device pointer.
+ * The result is rules 1 to 5 of bsr_local_top_k_capped over the rows that are live and allowed by
+ * the query's mask, m = per_group: the first k kept rows as (global index, the reference's f32
+ * distance bits, group id in out_group, nullable), then (~0, +inf, ~0u); out_count[q] = min(k, sum
+ * over the groups of min(m, the group's allowed live rows)).  A mask that allows no live row gives
+ * count 0 and is not an error.  An all-ones mask is bsr_local_top_k_deep_capped byte for byte;
+ * row_group[i] = i is bsr_local_top_k_deep_masked(k) bit for bit; for k <= 256 the result is
+ * bsr_local_top_k_capped(k, fetch_k = 256, per_group, the masks)'s byte for byte; the result at k is
+ * a prefix of the result at any larger k.  1 <= k <= BSR_DEEP_MAX_K, not bounded by cfg.max_k;
+ * 1 <= per_group <= BSR_CAP_MAX_PER_GROUP; n_groups >= 1; n_masks >= 1.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; k = 0 or k > BSR_DEEP_MAX_K;
+ *      per_group = 0 or above BSR_CAP_MAX_PER_GROUP; n_groups = 0; min(per_group, k) * n_groups >
+ *      2^32 - 1; n_masks = 0; an unknown mode; a null query_mask with n_masks > 1; with n_queries > 0
+ *      a null queries pointer, a null out_idx / out_dist / out_count or a null allow;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. BSR_E_INVALID: allow_words != ceil(n / 64); row_group_len != n; a null row_group with rows;
+ *   4. n_queries = 0: BSR_OK;
+ *   5. BSR_E_INVALID, found on the device before anything is indexed with them: an entry of
+ *      query_mask >= n_masks; a row_group entry >= n_groups;
+ *   6. BSR_E_NONFINITE: a non-finite query, read from the batch's status words before any of the
+ *      caller's arrays, host or device, is written.
+ * How, per mask group: bsr_local_top_k_deep_masked's ladder with "the first k kept keys" wherever it
+ * keeps "the k smallest".  The list scan: the allowed live rows of the mask as a row list (in chunks
+ * of BSR_MASK_LIST_BUDGET bytes), scanned exactly by a kernel that holds keys only -- a full LDS
+ * buffer is sorted, the groups of its rows are read, and one wave walks it against an LDS hash of
+ * group counts, keeping the kept keys; the k-th kept key is the threshold of the rows that follow --
+ * and the workgroups' kept lists and the query's carry are merged by the same capped walk.  The
+ * filter rung (same condition and modes as bsr_local_top_k_deep_masked): the lists cut by the mask
+ * are an exact prefix of the query's order over its mask, walked as bsr_local_top_k_deep_capped
+ * walks it; a query it does not certify takes the list scan of its own mask.  Neither the
+ * full-shard scan nor the group tables run.  Never graph-replayed.
+ * bsr_search_stats: search_path = BSR_PATH_DEEP | BSR_PATH_CAP, plus BSR_PATH_MASK_FILTER and / or
+ * BSR_PATH_MASK_LIST, plus BSR_PATH_MASK_GROUPS when a query_mask was given; never
+ * BSR_PATH_CAP_SCAN or BSR_PATH_DEEP_SCAN.  n_exact_direct, n_fallback, n_emitted and n_candidates
+ * are bsr_local_top_k_deep_masked's.
+ * A multi-rank masked deep capped search: this call on every rank with its own masks and row_group
+ * (global group ids) and device outputs, bsr_allgather_bytes of the four outputs,
+ * bsr_global_top_k_capped(k_in = k, per_group) on the gathered device arrays.
+ * Out of scope: bsr_local_top_k_capped's sparse-mask fallback through this list scan; the group
+ * search at deep k; a per-query per_group; a collective entry point. */
+int bsr_local_top_k_deep_capped_masked(bsr_index* ix, const float* queries, uint32_t n_queries,
+                                       uint32_t k, uint32_t per_group,
+                                       const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                                       const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                       const uint32_t* query_mask, /* [n_queries], nullable with one mask */
+                                       uint32_t mode,              /* BSR_MASK_AUTO / _LIST / _FILTER */
+                                       uint64_t* out_idx, float* out_dist,    /* [n_queries][k] */
+                                       uint32_t* out_group /* [n_queries][k], nullable */,
+                                       uint32_t* out_count /* [n_queries] */);
 
 /* ---- Deep MMR search: bsr_local_top_k_mmr over up to BSR_DEEP_MAX_K exact
  * candidates -- "k different passages out of the 1000 nearest", without document ids and without
