@@ -73,6 +73,7 @@ BSR_DEEP_MAX_K = 1024           # the largest k of bsr_local_top_k_deep (include
 BSR_DEEP_MMR_MAX_PICKS = 256    # the largest k of bsr_local_top_k_deep_mmr (include/bsr.h)
 BSR_GROUPS_MAX_ROWS = 64        # the largest group_size of a group search (include/bsr.h)
 BSR_GROUPS_MAX_SLOTS = 4096     # ... and the largest k * group_size
+BSR_DEEP_GROUPS_MAX_SLOTS = 8192  # ... of bsr_local_top_groups_deep
 BSR_SCORE_MAX_IDS = 4096        # the longest id list bsr_local_rerank_ids orders (include/bsr.h)
 BSR_CAP_MAX_PER_GROUP = 16      # the largest per_group of a capped search (include/bsr.h)
 BSR_RANGE_MAX_RESULTS = 4096  # result slots per query of a range search (include/bsr.h)
@@ -172,6 +173,8 @@ def lib() -> ctypes.CDLL:
                                                   _P, _P, _P]),
         "bsr_local_top_groups": (ctypes.c_int, [_P, _P, u32, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P,
                                                 _P, _P, _P, _P]),
+        "bsr_local_top_groups_deep": (ctypes.c_int, [_P, _P, u32, u32, u32, _P, u64, u32, _P, u64, u32, _P, u32, _P,
+                                                     _P, _P, _P, _P]),
         "bsr_local_score_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, _P, _P]),
         "bsr_local_rerank_ids": (ctypes.c_int, [_P, _P, u32, _P, u32, u32, _P, _P, _P]),
         "bsr_local_top_k_deep": (ctypes.c_int, [_P, _P, u32, u32, _P, _P, _P]),
@@ -206,7 +209,8 @@ def lib() -> ctypes.CDLL:
                 "bsr_local_range_search_masked", "bsr_local_top_k_mmr", "bsr_local_top_k_collapsed",
                 "bsr_local_top_k_capped", "bsr_global_top_k_capped", "bsr_local_score_ids", "bsr_local_rerank_ids",
                 "bsr_local_top_groups", "bsr_local_top_k_deep", "bsr_local_top_k_deep_masked",
-                "bsr_local_top_k_deep_capped", "bsr_local_top_k_deep_capped_masked", "bsr_local_top_k_deep_mmr", "bsr_index_last_mmr_pairs"}
+                "bsr_local_top_k_deep_capped", "bsr_local_top_k_deep_capped_masked", "bsr_local_top_k_deep_mmr", "bsr_index_last_mmr_pairs",
+                "bsr_local_top_groups_deep"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -1034,10 +1038,32 @@ class Index:
         return self._group_search(None, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids, allow_masks,
                                   query_mask, mask_mode, True, group_size)
 
+    def deep_group_search(self, queries, k: int, row_group, group_size: int, n_groups=None, allow_mask=None,
+                          allow_ids=None, allow_masks=None, query_mask=None, mask_mode="auto"):
+        """group_search for k up to BSR_DEEP_MAX_K (bsr_local_top_groups_deep), not bounded by max_k
+        and without a fetch_k -> group_search's five arrays.  k group_size <=
+        BSR_DEEP_GROUPS_MAX_SLOTS; the groups are deep_capped_search(per_group=1)'s, in its order.
+        Every other argument is group_search's."""
+        group_size = int(group_size)
+        if group_size < 0 or group_size > 0xFFFFFFFF:
+            raise BsrError(-1, f"group_size={group_size} is no 32-bit count")
+        return self._group_search(None, queries, k, row_group, n_groups, None, allow_mask, allow_ids, allow_masks,
+                                  query_mask, mask_mode, True, group_size, deep=True)
+
+    def deep_group_search_device(self, queries, nq: int, k: int, group_size: int, row_group, n_groups: int, out_idx,
+                                 out_dist, out_count, out_group=None, out_rows=None, allow_words=None,
+                                 query_mask=None, mask_mode="auto"):
+        """Zero-copy variant of deep_group_search on caller buffers: group_search_device's arguments
+        and shapes without fetch_k."""
+        tail = self._group_device_tail(row_group, n_groups, out_idx, out_dist, out_count, out_group, allow_words,
+                                       query_mask, mask_mode)
+        _check(lib().bsr_local_top_groups_deep(self._h, _ptr(queries), nq, k, int(group_size), *tail[:-1],
+                                               _ptr(out_rows), tail[-1]))
+
     def _group_search(self, per_group, queries, k, row_group, n_groups, fetch_k, allow_mask, allow_ids, allow_masks,
-                      query_mask, mask_mode, return_groups, group_size=None):
-        """collapsed_search (per_group None), capped_search and group_search (group_size) on host
-        arrays."""
+                      query_mask, mask_mode, return_groups, group_size=None, deep=False):
+        """collapsed_search (per_group None), capped_search, group_search (group_size) and
+        deep_group_search (deep: no fetch_k, k up to BSR_DEEP_MAX_K) on host arrays."""
         one = allow_mask is not None or allow_ids is not None
         if one and (allow_masks is not None or query_mask is not None):
             raise BsrError(-1, "give allow_mask / allow_ids or allow_masks with query_mask, not both")
@@ -1050,8 +1076,12 @@ class Index:
             raise BsrError(-6, f"query length {q.shape[-1]} != dim {self.dim}")
         nq = q.shape[0]
         k = int(k)
-        fk = min(self.max_k, max(4 * k, 32)) if fetch_k is None else int(fetch_k)
-        if k < 1 or k > fk or fk > self.max_k:
+        if deep and (k < 1 or k > BSR_DEEP_MAX_K or group_size < 1 or group_size > BSR_GROUPS_MAX_ROWS or
+                     k * group_size > BSR_DEEP_GROUPS_MAX_SLOTS):
+            raise BsrError(-1, f"k={k}, group_size={group_size} outside 1 <= k <= {BSR_DEEP_MAX_K}, 1 <= group_size "
+                               f"<= {BSR_GROUPS_MAX_ROWS}, k * group_size <= {BSR_DEEP_GROUPS_MAX_SLOTS}")
+        fk = k if deep else min(self.max_k, max(4 * k, 32)) if fetch_k is None else int(fetch_k)
+        if not deep and (k < 1 or k > fk or fk > self.max_k):
             raise BsrError(-1, f"k={k}, fetch_k={fk} outside 1 <= k <= fetch_k <= max_k={self.max_k}")
         rg, n_rg, ng = self._row_groups(row_group, n_groups)
         shape = (nq, k) if group_size is None else (nq, k, group_size)
@@ -1074,6 +1104,10 @@ class Index:
                 _ptr(oc))
         if group_size is not None:
             orows = np.empty((nq, k), np.uint32)
+            if deep:
+                _check(lib().bsr_local_top_groups_deep(self._h, _ptr(q), nq, k, group_size, *tail[:-1], _ptr(orows),
+                                                       tail[-1]))
+                return oi, od, orows, og, oc
             _check(lib().bsr_local_top_groups(self._h, _ptr(q), nq, k, group_size, fk, *tail[:-1], _ptr(orows),
                                               tail[-1]))
             return oi, od, orows, og, oc

@@ -86,6 +86,11 @@ int bsr_local_top_groups_impl(bsr_index* ix, const float* queries, uint32_t nq, 
                               const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
                               const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
                               uint32_t* out_group, uint32_t* out_rows, uint32_t* out_count);
+int bsr_local_top_groups_deep_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t group_size,
+                                   const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                   const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                   uint32_t* out_group, uint32_t* out_rows, uint32_t* out_count);
 int bsr_index_collect_profile_impl(bsr_index* ix);
 int bsr_copy_out_impl(bsr_index* ix, uint32_t nq, uint32_t k, uint64_t* out_idx, float* out_dist,
                       uint32_t* out_count);
@@ -512,6 +517,16 @@ int bsr_local_top_groups(bsr_index* ix, const float* queries, uint32_t n_queries
     BSR_GUARD(bsr_local_top_groups_impl(ix, queries, n_queries, k, group_size, fetch_k, row_group, row_group_len,
                                         n_groups, allow, allow_words, n_masks, query_mask, mode, out_idx, out_dist,
                                         out_group, out_rows, out_count));
+}
+
+int bsr_local_top_groups_deep(bsr_index* ix, const float* queries, uint32_t n_queries, uint32_t k,
+                              uint32_t group_size, const uint32_t* row_group, uint64_t row_group_len,
+                              uint32_t n_groups, const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                              const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                              uint32_t* out_group, uint32_t* out_rows, uint32_t* out_count) {
+    BSR_GUARD(bsr_local_top_groups_deep_impl(ix, queries, n_queries, k, group_size, row_group, row_group_len, n_groups,
+                                             allow, allow_words, n_masks, query_mask, mode, out_idx, out_dist,
+                                             out_group, out_rows, out_count));
 }
 
 // The device merge's limits (k_merge_lists: one wave per query, the concatenation in LDS).

@@ -3982,6 +3982,163 @@ int bsr_local_top_groups_impl(bsr_index* ix, const float* queries, uint32_t nq, 
     return BSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Deep group search (bsr_local_top_groups_deep): the deep capped search with
+// per_group = 1 names every query's k <= 1024 groups, the inverted list gives their rows, the plan
+// lays every query's rows out once, and the fill keeps the m best of each group under a budget the
+// host sets from the batch's item count.
+// ---------------------------------------------------------------------------------------
+static_assert(kDeepGroupsMaxSlots == BSR_DEEP_GROUPS_MAX_SLOTS, "the deep fill's limit is the ABI's");
+
+int bsr_index::top_groups_deep_device(const float* queries, uint32_t nq, uint32_t k, uint32_t group_size,
+                                      const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow,
+                                      uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask,
+                                      uint32_t mode, uint64_t* out_idx, float* out_dist, uint32_t* out_group,
+                                      uint32_t* out_rows, uint32_t* out_count) {
+    bsr_index* ix = this;
+    const uint32_t m = group_size;
+    BSR_HIP(hipSetDevice(device));
+    // Every buffer of the stage before the head search, the table of the split launch at its largest
+    // included: once the fill writes to the caller's arrays no allocation is left to fail.
+    const size_t nk = (size_t)nq * k, nkm = nk * m;
+    const bool out_dev = is_device_ptr(out_idx) && is_device_ptr(out_dist) && is_device_ptr(out_count) &&
+                         (!out_group || is_device_ptr(out_group)) && (!out_rows || is_device_ptr(out_rows));
+    BSR_TRY(tg_gcnt.ensure((size_t)n_groups * sizeof(uint32_t)));
+    BSR_TRY(tg_gpos.ensure((size_t)n_groups * sizeof(uint32_t)));
+    BSR_TRY(tg_list.ensure((size_t)n * sizeof(uint32_t)));
+    BSR_TRY(tg_plan.ensure((4 + (size_t)nq + (nk + nq) + nk) * sizeof(uint32_t)));
+    BSR_TRY(tg_table.ensure(nkm * sizeof(uint64_t)));
+    BSR_TRY(tg_hidx.ensure(nk * sizeof(uint64_t)));
+    BSR_TRY(tg_hdist.ensure(nk * sizeof(float)));
+    BSR_TRY(tg_hgroup.ensure(nk * sizeof(uint32_t)));
+    BSR_TRY(tg_hcnt.ensure((size_t)nq * sizeof(uint32_t)));
+    if (!out_dev) {
+        BSR_TRY(tg_idx.ensure(nkm * sizeof(uint64_t)));
+        BSR_TRY(tg_dist.ensure(nkm * sizeof(float)));
+        BSR_TRY(tg_rows.ensure(nk * sizeof(uint32_t)));
+        BSR_TRY(tg_group.ensure(nk * sizeof(uint32_t)));
+        BSR_TRY(tg_cnt.ensure((size_t)nq * sizeof(uint32_t)));
+    }
+    // 1. The heads: the deep collapsed search, unchanged, into the index's own arrays (it checks
+    // row_group and the masks, and waits; none of its errors can touch a caller array).
+    if (allow) {
+        const DeepCap cap{1, row_group, n_groups, tg_hgroup.as<uint32_t>()};
+        BSR_TRY(deep_search_device_masked(queries, nq, k, allow, allow_words, n_masks, query_mask, mode,
+                                          tg_hidx.as<uint64_t>(), tg_hdist.as<float>(), tg_hcnt.as<uint32_t>(), &cap));
+    } else {
+        BSR_TRY(deep_capped_search_device(queries, nq, k, 1, row_group, n_groups, tg_hidx.as<uint64_t>(),
+                                          tg_hdist.as<float>(), tg_hgroup.as<uint32_t>(), tg_hcnt.as<uint32_t>()));
+    }
+    stats.search_path = (stats.search_path & ~BSR_PATH_CAP) | BSR_PATH_GROUPS;
+    // (the head search's rescore time is taken now: the plan and the fill use the same events)
+    if (profiling(ix)) ev_collect(ev_rescore, prof.rescore_ms, prof.rescore_launches, 1);
+    // 2. The inverted list of the caller's row_group, where the head search left it on the device.
+    const uint32_t* const dgrp = is_device_ptr(row_group) ? row_group : col_grp.as<uint32_t>();
+    uint32_t* const plan = tg_plan.as<uint32_t>();
+    BSR_HIP(hipMemsetAsync(plan, 0, 4 * sizeof(uint32_t), stream));
+    if (n) {
+        BSR_HIP(hipMemsetAsync(tg_gcnt.p, 0, (size_t)n_groups * sizeof(uint32_t), stream));
+        BSR_HIP(launch_groups_invert(dgrp, n, n_groups, tg_gcnt.as<uint32_t>(), tg_gpos.as<uint32_t>(), plan + 3,
+                                     tg_list.as<uint32_t>(), stream));
+    }
+    // 3. The plan, and the call's one mid-call wait: the items of the batch and the largest count.
+    GroupsDeepArgs fa{};
+    fa.rows = rows.as<float>();
+    fa.ld = ld;
+    fa.dim = dim;
+    fa.offset = global_offset;
+    fa.na = na.as<float>();
+    fa.qf32 = qf32.as<float>();
+    fa.nb = nb.as<float>();
+    fa.dead = dead_bits();
+    // (the masks where the head search read them: the caller's device arrays or its copies)
+    fa.allow = !allow ? nullptr : is_device_ptr(allow) ? allow : mask_dev.as<uint64_t>();
+    fa.allow_words = allow_words;
+    fa.query_mask = !allow || !query_mask ? nullptr
+                    : is_device_ptr(query_mask) ? query_mask : grp_qmask.as<uint32_t>();
+    fa.gcnt = tg_gcnt.as<uint32_t>();
+    fa.gpos = tg_gpos.as<uint32_t>();
+    fa.glist = tg_list.as<uint32_t>();
+    fa.head_group = tg_hgroup.as<uint32_t>();
+    fa.head_cnt = tg_hcnt.as<uint32_t>();
+    fa.nq = nq;
+    fa.k = k;
+    fa.m = m;
+    fa.info = plan;
+    fa.items = plan + 4;
+    fa.pre = fa.items + nq;
+    fa.first = fa.pre + (nk + nq);
+    fa.table = tg_table.as<uint64_t>();
+    fa.out_idx = out_dev ? out_idx : tg_idx.as<uint64_t>();
+    fa.out_dist = out_dev ? out_dist : tg_dist.as<float>();
+    fa.out_rows = out_dev ? out_rows : tg_rows.as<uint32_t>();
+    fa.out_group = out_dev ? out_group : tg_group.as<uint32_t>();
+    fa.out_count = out_dev ? out_count : tg_cnt.as<uint32_t>();
+    ev_begin(ix, ev_rescore);
+    BSR_HIP(launch_groups_deep_plan(fa, stream));
+    uint32_t info[3] = {0, 0, 0};
+    BSR_HIP(hipMemcpyAsync(info, plan, sizeof info, hipMemcpyDeviceToHost, stream));
+    BSR_HIP(hipStreamSynchronize(stream));
+    const uint64_t total_items = (uint64_t)info[1] << 32 | info[0];
+    const uint32_t max_items = info[2];
+    const uint32_t split_items = (uint32_t)std::min<uint64_t>(
+        std::max<uint64_t>(1, env_bytes("BSR_GROUPS_SPLIT_ITEMS", 64)), 0xFFFFFFFFull);
+    fa.budget = groups_deep_budget(total_items, split_items);
+    // 4. The fill, straight into the caller's arrays when they are all on the device; the queries
+    // above the budget through the global table and the finish.
+    BSR_HIP(launch_groups_fill_deep(fa, stream));
+    if (max_items > fa.budget) {
+        BSR_HIP(hipMemsetAsync(tg_table.p, 0xff, nkm * sizeof(uint64_t), stream));
+        const uint32_t parts = (uint32_t)std::min<uint64_t>(((uint64_t)max_items + fa.budget - 1) / fa.budget, 1024u);
+        BSR_HIP(launch_groups_fill_deep_split(fa, parts, stream));
+        BSR_HIP(launch_groups_deep_finish(fa, stream));
+    }
+    ev_end(ix, ev_rescore);
+    if (!out_dev) {
+        BSR_HIP(hipMemcpyAsync(out_idx, fa.out_idx, nkm * sizeof(uint64_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_dist, fa.out_dist, nkm * sizeof(float), hipMemcpyDefault, stream));
+        if (out_rows) BSR_HIP(hipMemcpyAsync(out_rows, fa.out_rows, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        if (out_group) BSR_HIP(hipMemcpyAsync(out_group, fa.out_group, nk * sizeof(uint32_t), hipMemcpyDefault, stream));
+        BSR_HIP(hipMemcpyAsync(out_count, fa.out_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDefault, stream));
+    }
+    BSR_HIP(hipStreamSynchronize(stream));
+    return BSR_OK;
+}
+
+int bsr_local_top_groups_deep_impl(bsr_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t group_size,
+                                   const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                                   const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                                   const uint32_t* query_mask, uint32_t mode, uint64_t* out_idx, float* out_dist,
+                                   uint32_t* out_group, uint32_t* out_rows, uint32_t* out_count) {
+    if (!ix) return set_error(BSR_E_INVALID, "null index");
+    if (group_size == 0 || group_size > BSR_GROUPS_MAX_ROWS)
+        return set_error(BSR_E_INVALID, "group_size=%u outside 1 <= group_size <= %u", group_size, BSR_GROUPS_MAX_ROWS);
+    if ((uint64_t)k * group_size > BSR_DEEP_GROUPS_MAX_SLOTS)
+        return set_error(BSR_E_INVALID, "k * group_size = %u * %u exceeds %u", k, group_size,
+                         BSR_DEEP_GROUPS_MAX_SLOTS);
+    if (k == 0 || k > BSR_DEEP_MAX_K) return set_error(BSR_E_INVALID, "k=%u outside [1, %u]", k, BSR_DEEP_MAX_K);
+    if (n_groups == 0) return set_error(BSR_E_INVALID, "n_groups = 0");
+    if (!allow && (n_masks != 0 || query_mask))
+        return set_error(BSR_E_INVALID, "n_masks = %u or a query_mask without allow masks", n_masks);
+    if (allow && n_masks == 0) return set_error(BSR_E_INVALID, "n_masks = 0 with allow masks");
+    if (allow && !query_mask && n_masks > 1)
+        return set_error(BSR_E_INVALID, "null query_mask with n_masks = %u (legal only with one mask)", n_masks);
+    if (mode != BSR_MASK_AUTO && mode != BSR_MASK_LIST && mode != BSR_MASK_FILTER)
+        return set_error(BSR_E_INVALID, "unknown mask mode %u", mode);
+    if (nq && !queries) return set_error(BSR_E_INVALID, "null queries");
+    if (nq && (!out_idx || !out_dist || !out_count)) return set_error(BSR_E_INVALID, "null output");
+    if (!ix->loaded) return set_error(BSR_E_STATE, "index not loaded");
+    if (row_group_len != ix->n)
+        return set_error(BSR_E_INVALID, "row_group_len=%llu, the index holds %llu rows", (unsigned long long)row_group_len,
+                         (unsigned long long)ix->n);
+    if (ix->n && !row_group) return set_error(BSR_E_INVALID, "null row_group");
+    if (nq == 0) return BSR_OK;
+    BSR_TRY(ix->top_groups_deep_device(queries, nq, k, group_size, row_group, n_groups, allow, allow_words, n_masks,
+                                       query_mask, mode, out_idx, out_dist, out_group, out_rows, out_count));
+    collect_profile(ix);
+    return BSR_OK;
+}
+
 int bsr_index_collect_profile_impl(bsr_index* ix) {
     collect_profile(ix);
     return BSR_OK;

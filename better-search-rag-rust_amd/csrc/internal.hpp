@@ -381,6 +381,20 @@ struct bsr_index {
     bsr::DevBuf tg_hidx, tg_hdist, tg_hgroup, tg_hcnt;       // the collapsed search's result [nq][k], [nq]
     bsr::DevBuf tg_idx, tg_dist, tg_rows, tg_group, tg_cnt;  // the result [nq][k][m], [nq][k], [nq]
 
+    // Deep group search (bsr_local_top_groups_deep): the deep capped search with
+    // per_group = 1 (under masks the masked ladder with that cap) into tg_hidx / tg_hdist / tg_hgroup /
+    // tg_hcnt, the inverted list as above, the plan of every query's result groups, one readback of
+    // the batch's item sum and maximum, the fill under the budget they give, and for the queries above
+    // it the split fill into tg_table and the finish.  All launched directly, never captured; every
+    // buffer is sized before the head search.
+    int top_groups_deep_device(const float* queries, uint32_t nq, uint32_t k, uint32_t group_size,
+                               const uint32_t* row_group, uint32_t n_groups, const uint64_t* allow,
+                               uint64_t allow_words, uint32_t n_masks, const uint32_t* query_mask, uint32_t mode,
+                               uint64_t* out_idx, float* out_dist, uint32_t* out_group, uint32_t* out_rows,
+                               uint32_t* out_count);
+    bsr::DevBuf tg_plan;  // u32: [4] the batch's items (u64), their maximum, the offsets' cursor |
+                          //      items [nq] | pre [nq][k + 1] | first [nq][k]
+
     // Parallel search with a global emission threshold (P > 1), in two halves
     // around the all-gather of every rank's ks best sample keys:
     //   phase A: query prep, the sample pass, tau0 and the keys (smax [qpad][gt_ks]);

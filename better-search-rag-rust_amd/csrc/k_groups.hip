@@ -1,6 +1,7 @@
 // k_groups.hip -- group search (bsr_local_top_groups) on gfx950: the inverted list
 // of row_group, the fill that scores the rows of a query's result groups and keeps the m best of
-// each, and the finish of the queries split over several workgroups.
+// each, and the finish of the queries split over several workgroups; and the deep group search's
+// plan, fill and finish (bsr_local_top_groups_deep) for up to 1024 groups a query.
 //
 // Compiled like k_exact.hip (-ffp-contract=off, correctly rounded divide and sqrt: the walk is the
 // reference's arithmetic), and with the device feature packed-fp32-ops off (Makefile).
@@ -59,8 +60,8 @@ __global__ __launch_bounds__(256) void k_groups_scatter(const uint32_t* __restri
 
 // The table rows [k][m] of one query (any order inside a group, kKeyNone where a group has fewer
 // rows) -> its outputs: a wave per group, one entry per lane through wave_sort64.
-__device__ __forceinline__ void groups_emit(const GroupsFillArgs& a, uint32_t q, const unsigned long long* tab,
-                                            uint32_t cnt) {
+template <class Args>
+__device__ __forceinline__ void groups_emit(const Args& a, uint32_t q, const unsigned long long* tab, uint32_t cnt) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t k = a.k, m = a.m;
     for (uint32_t g = w; g < k; g += 4) {
@@ -182,6 +183,149 @@ __global__ __launch_bounds__(256) void k_groups_finish(GroupsFillArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
+// Deep group search (bsr_local_top_groups_deep): up to 1024 result groups a query.
+// The plan scans every query's group lengths once and leaves the prefix sums in global memory; the
+// host reads three words and sets the budget; the fill copies its query's plan and deals the items.
+// ------------------------------------------------------------------------------------
+// One workgroup per query, four result groups a thread: the lengths of the head groups, their sum
+// scanned over the wave by shuffles, one pass over the four wave totals.  pre[q][i] is the first
+// position of result group i in the concatenated row lists (pre[q][i] = the total for i >= cnt),
+// first[q][i] its first slot in glist.  A head group has a live row, so no length is zero; the
+// groups are distinct, so a total is at most n < 2^32.
+__global__ __launch_bounds__(256) void k_groups_deep_plan(GroupsDeepArgs a) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6, q = blockIdx.x, k = a.k;
+    const uint32_t cnt = a.head_cnt[q] < k ? a.head_cnt[q] : k;
+    uint32_t len[4], sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t i = 4 * t + j;
+        len[j] = 0;
+        if (i < cnt) {
+            const uint32_t g = a.head_group[(uint64_t)q * k + i];
+            len[j] = a.gcnt[g];
+            a.first[(uint64_t)q * k + i] = a.gpos[g] - len[j];
+        }
+        sum += len[j];
+    }
+    uint32_t inc = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)inc, d, kWave);
+        inc += lane >= (uint32_t)d ? v : 0u;
+    }
+    if (lane == 63) s_wave[w] = inc;
+    __syncthreads();
+    uint32_t base = inc - sum, total = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < 4; ++v) {
+        base += v < w ? s_wave[v] : 0u;
+        total += s_wave[v];
+    }
+    uint32_t* const pre = a.pre + (uint64_t)q * (k + 1);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t i = 4 * t + j;
+        if (i < k) pre[i] = base;
+        base += len[j];
+    }
+    if (t == 0) {
+        const uint32_t items = total / 64 + (total % 64 ? 1u : 0u);
+        pre[k] = total;
+        a.items[q] = items;
+        if (items) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(a.info), (unsigned long long)items);
+            atomicMax(a.info + 2, items);
+        }
+    }
+}
+
+// One workgroup of four waves per query (SPLIT: blockIdx.y's share of the items of a long query).
+// LDS: the waves' row stages and the query as k_groups_fill has them, the query's plan (pre, first)
+// copied from global memory, and -- not SPLIT -- the table [k][m] of TAB entries; SPLIT offers into
+// row q of the global table.  A query is short when it has at most `budget` items: the plain launch
+// answers the short queries and leaves the long ones (its workgroup exits), the SPLIT launch the
+// reverse; nothing is listed and nothing is read back between them.  The item loop is
+// k_groups_fill's: 64 consecutive positions an item from the LDS counter, the group by a binary
+// search over pre (at most 10 steps), the row from glist -- the only source of an address -- the
+// walk, and cap_insert into the group's m entries.
+template <int TAB, bool SPLIT>
+__global__ __launch_bounds__(256) void k_groups_fill_deep(GroupsDeepArgs a) {
+    constexpr int W = 4, STAGE = 64 * 68, QMAX = 1024, KMAX = (int)kDeepMaxK;
+    __shared__ __attribute__((aligned(16))) float lds_all[W * STAGE + QMAX];
+    __shared__ unsigned long long s_tab[TAB];
+    __shared__ uint32_t s_first[KMAX], s_pre[KMAX + 1], s_next;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t t = threadIdx.x;
+    float* const lds = lds_all + w * STAGE;
+    float* const ldq = lds_all + W * STAGE;
+    const uint32_t q = blockIdx.x;
+    const uint32_t k = a.k, m = a.m;
+    const uint32_t items = a.items[q];
+    if (SPLIT ? items <= a.budget : items > a.budget) return;  // (uniform over the workgroup)
+    uint32_t lo = 0, hi = items;
+    if (SPLIT) {
+        const uint32_t per = (items + gridDim.y - 1) / gridDim.y;
+        lo = blockIdx.y * per < items ? blockIdx.y * per : items;
+        hi = items - lo < per ? items : lo + per;
+        if (lo >= hi) return;  // (an empty share)
+    }
+    const uint32_t cnt = a.head_cnt[q] < k ? a.head_cnt[q] : k;
+    for (uint32_t i = t; i < cnt; i += 64 * W) s_first[i] = a.first[(uint64_t)q * k + i];
+    for (uint32_t i = t; i <= cnt; i += 64 * W) s_pre[i] = a.pre[(uint64_t)q * (k + 1) + i];
+    if (t == 0) s_next = lo;
+    if (!SPLIT)
+        for (uint32_t i = t; i < k * m; i += 64 * W) s_tab[i] = kKeyNone;
+    const uint32_t ld = a.ld;
+    const float* const qrow = a.qf32 + (uint64_t)q * ld;
+    const bool qlds = ld <= (uint32_t)QMAX;  // (longer rows read the query from global memory)
+    if (qlds)
+        for (uint32_t cc = t; cc < ld; cc += 64 * W) ldq[cc] = qrow[cc];
+    __syncthreads();
+    const uint32_t total = s_pre[cnt];
+    unsigned long long* const tab =
+        SPLIT ? reinterpret_cast<unsigned long long*>(a.table) + (uint64_t)q * k * m : s_tab;
+    const uint64_t mask = a.allow && a.query_mask ? a.query_mask[q] : 0u;
+    const uint32_t* const aw =
+        a.allow ? reinterpret_cast<const uint32_t*>(a.allow + mask * a.allow_words) : nullptr;
+    const float mag_b = a.nb[q];
+    for (;;) {
+        uint32_t it = 0;
+        if (lane == 0) it = atomicAdd(&s_next, 1u);
+        it = (uint32_t)__builtin_amdgcn_readfirstlane((int)it);
+        if (it >= hi) break;
+        const uint64_t p = (uint64_t)it * 64 + lane;
+        const bool inlist = p < total;
+        uint32_t g0 = 0, g1 = cnt;  // (the slot lies in [g0, g1); cnt >= 1 wherever an item exists)
+        while (g1 - g0 > 1) {
+            const uint32_t mid = (g0 + g1) >> 1;
+            if (s_pre[mid] <= p) g0 = mid;
+            else g1 = mid;
+        }
+        const uint32_t r = inlist ? a.glist[s_first[g0] + (uint32_t)(p - s_pre[g0])] : 0u;
+        bool live = row_live(a.dead, r, inlist);
+        if (live && aw) live = (aw[r >> 5] >> (r & 31)) & 1u;
+        if (!__ballot(live)) continue;  // (uniform over the wave)
+        const uint32_t myrow = live ? r : 0u;
+        float acc[1] = {-0.0f}, mx[1] = {0.0f};
+        wave_walk_rows(lds, a.rows, ld, a.dim, myrow, qlds ? ldq : qrow, lane, acc, mx);
+        const float d = finish_distance(acc[0], mx[0], a.na[myrow], mag_b);
+        if (live) cap_insert(tab + (uint64_t)g0 * m, m, dist_key(d, myrow));
+    }
+    if (SPLIT) return;
+    __syncthreads();
+    groups_emit(a, q, s_tab, cnt);  // (a wave per group: 256 groups a wave at k = 1024)
+}
+
+// One workgroup per query, the short ones exiting: row q of the global table through groups_emit.
+__global__ __launch_bounds__(256) void k_groups_deep_finish(GroupsDeepArgs a) {
+    const uint32_t q = blockIdx.x;
+    if (a.items[q] <= a.budget) return;
+    const uint32_t cnt = a.head_cnt[q] < a.k ? a.head_cnt[q] : a.k;
+    groups_emit(a, q, reinterpret_cast<const unsigned long long*>(a.table) + (uint64_t)q * a.k * a.m, cnt);
+}
+
+// ------------------------------------------------------------------------------------
 // Launchers
 // ------------------------------------------------------------------------------------
 static inline uint32_t grid_for(uint64_t work, uint32_t block, uint32_t cap = 65536) {
@@ -225,6 +369,56 @@ hipError_t launch_groups_finish(const GroupsFillArgs& a, uint32_t n_split, hipSt
     if (!n_split) return hipSuccess;
     if (!groups_shape_ok(a) || !a.table) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_groups_finish, dim3(n_split), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+static bool groups_deep_shape_ok(const GroupsDeepArgs& a) {
+    return a.k && a.k <= kDeepMaxK && a.m && a.m <= kGroupsMaxRows && a.k * a.m <= kDeepGroupsMaxSlots && a.pre &&
+           a.first && a.items && a.info;
+}
+
+// The budget B = max(split_items, the batch's items over four workgroups a compute unit): a large
+// batch keeps every ordinary query on one workgroup and a single long query still covers the chip.
+uint32_t groups_deep_budget(uint64_t total_items, uint32_t split_items) {
+    static const uint32_t cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+            n = 256;
+        (void)hipGetLastError();
+        return (uint32_t)n;
+    }();
+    const uint64_t share = (total_items + 4ull * cus - 1) / (4ull * cus);
+    const uint64_t b = share > split_items ? share : split_items;
+    return (uint32_t)(b > 0xFFFFFFFFull ? 0xFFFFFFFFull : b);
+}
+
+hipError_t launch_groups_deep_plan(const GroupsDeepArgs& a, hipStream_t s) {
+    if (!a.nq) return hipSuccess;
+    if (!groups_deep_shape_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_groups_deep_plan, dim3(a.nq), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_groups_fill_deep(const GroupsDeepArgs& a, hipStream_t s) {
+    if (!a.nq) return hipSuccess;
+    if (!groups_deep_shape_ok(a) || !a.budget) return hipErrorInvalidValue;
+    if (a.k * a.m <= 2048) hipLaunchKernelGGL((k_groups_fill_deep<2048, false>), dim3(a.nq), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_groups_fill_deep<(int)kDeepGroupsMaxSlots, false>), dim3(a.nq), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_groups_fill_deep_split(const GroupsDeepArgs& a, uint32_t parts, hipStream_t s) {
+    if (!a.nq) return hipSuccess;
+    if (!groups_deep_shape_ok(a) || !a.budget || !parts || parts > 1024u || !a.table) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_groups_fill_deep<1, true>), dim3(a.nq, parts), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_groups_deep_finish(const GroupsDeepArgs& a, hipStream_t s) {
+    if (!a.nq) return hipSuccess;
+    if (!groups_deep_shape_ok(a) || !a.budget || !a.table) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_groups_deep_finish, dim3(a.nq), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -986,6 +986,57 @@ hipError_t launch_groups_fill(const GroupsFillArgs& a, hipStream_t s);
 hipError_t launch_groups_fill_split(const GroupsFillArgs& a, uint32_t n_split, uint32_t parts, hipStream_t s);
 hipError_t launch_groups_finish(const GroupsFillArgs& a, uint32_t n_split, hipStream_t s);
 
+// ---- deep group search (bsr_local_top_groups_deep; k_groups.hip) ----------------
+// The fill for 1 <= k <= kDeepMaxK result groups a query, 1 <= m <= kGroupsMaxRows, k * m <=
+// kDeepGroupsMaxSlots; inputs and outputs as GroupsFillArgs has them (head_group / head_cnt: the deep
+// capped search's out_group / out_count at per_group = 1).  Four launches at most, one readback:
+//   launch_groups_deep_plan: pre[q][0 .. k] = the prefix sums of the rows of query q's result groups
+//     (pre[q][i] = their total for i >= head_cnt[q]), first[q][i] = group i's first slot in glist,
+//     items[q] = ceil(total / 64); info (u64 + u32, zero before): the sum of the items of the batch
+//     and their maximum.  The host reads info and sets budget = groups_deep_budget(sum, split_items);
+//   launch_groups_fill_deep: a workgroup per query; a query with at most `budget` items is answered
+//     from an LDS table, any other left alone;
+//   launch_groups_fill_deep_split (only when the maximum exceeds the budget): grid (nq, parts), parts
+//     <= 1024; workgroup (q, y) of a query above the budget takes the y-th share of its items and
+//     offers into row q of table [nq][k][m] (u64, all-ones before the launch);
+//   launch_groups_deep_finish: sorts row q of the table of every query above the budget and writes
+//     its outputs.
+constexpr uint32_t kDeepGroupsMaxSlots = 8192;  // BSR_DEEP_GROUPS_MAX_SLOTS
+struct GroupsDeepArgs {
+    const float* rows;          // f32 [n_pad][ld]
+    uint32_t ld, dim;
+    uint64_t offset;            // the global id of row 0
+    const float* na;            // row magnitudes (read, never recomputed)
+    const float* qf32;          // queries [qpad][ld]
+    const float* nb;            // query magnitudes
+    const uint64_t* dead;       // the bitset of deleted rows (nullable)
+    const uint64_t* allow;      // [n_masks][allow_words] (nullable)
+    uint64_t allow_words;
+    const uint32_t* query_mask; // [nq] (nullable: mask 0)
+    const uint32_t* gcnt;       // [n_groups]: launch_groups_invert's
+    const uint32_t* gpos;       // [n_groups]
+    const uint32_t* glist;      // [n]
+    const uint32_t* head_group; // [nq][k]
+    const uint32_t* head_cnt;   // [nq]
+    uint32_t nq, k, m;
+    uint32_t budget;            // items a query may have and stay on one workgroup (the fill launches)
+    uint32_t* pre;              // [nq][k + 1]
+    uint32_t* first;            // [nq][k]
+    uint32_t* items;            // [nq]
+    uint32_t* info;             // [3], 8-byte aligned: the batch's items (u64), the largest count
+    uint64_t* table;            // [nq][k][m] (the split launch and the finish)
+    uint64_t* out_idx;          // [nq][k][m]
+    float* out_dist;            // [nq][k][m]
+    uint32_t* out_rows;         // [nq][k], nullable
+    uint32_t* out_group;        // [nq][k], nullable
+    uint32_t* out_count;        // [nq]
+};
+uint32_t groups_deep_budget(uint64_t total_items, uint32_t split_items);
+hipError_t launch_groups_deep_plan(const GroupsDeepArgs& a, hipStream_t s);
+hipError_t launch_groups_fill_deep(const GroupsDeepArgs& a, hipStream_t s);
+hipError_t launch_groups_fill_deep_split(const GroupsDeepArgs& a, uint32_t parts, hipStream_t s);
+hipError_t launch_groups_deep_finish(const GroupsDeepArgs& a, hipStream_t s);
+
 uint32_t scan_grid_for(uint64_t n);
 
 }  // namespace bsr

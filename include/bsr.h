@@ -713,7 +713,7 @@ int bsr_local_rerank_ids(bsr_index* ix, const float* queries, uint32_t n_queries
  * A multi-rank deep search: this call on every rank with device outputs, bsr_allgather_bytes of the
  * three outputs on device buffers, bsr_global_top_k on the gathered device arrays (host arrays
  * merge on the host).
- * Out of scope: the group search (bsr_local_top_groups) with deep k; a parallel entry point
+ * The group search with deep k: bsr_local_top_groups_deep below.  Out of scope: a parallel entry point
  * that runs those collectives itself.  Allow masks: bsr_local_top_k_deep_masked below.  At most m
  * rows per group, or one row per group: bsr_local_top_k_deep_capped below. */
 #define BSR_DEEP_MAX_K 1024u
@@ -808,8 +808,8 @@ int bsr_local_top_k_deep_masked(bsr_index* ix, const float* queries, uint32_t n_
  * ids) and device outputs, out_group included; bsr_allgather_bytes of the four outputs on device
  * buffers; bsr_global_top_k_capped(k_in = k, per_group) on the gathered device arrays, which merges
  * lists of this depth on the GPU.
- * Allow masks: bsr_local_top_k_deep_capped_masked below.  Out of scope: the
- * group search (bsr_local_top_groups) at deep k; a per-query per_group; raising
+ * Allow masks: bsr_local_top_k_deep_capped_masked below.  The group search at deep k:
+ * bsr_local_top_groups_deep below.  Out of scope: a per-query per_group; raising
  * BSR_CAP_MAX_PER_GROUP; a collective entry point. */
 int bsr_local_top_k_deep_capped(bsr_index* ix, const float* queries, uint32_t n_queries,
                                 uint32_t k, uint32_t per_group,
@@ -861,8 +861,9 @@ int bsr_local_top_k_deep_capped(bsr_index* ix, const float* queries, uint32_t n_
  * A multi-rank masked deep capped search: this call on every rank with its own masks and row_group
  * (global group ids) and device outputs, bsr_allgather_bytes of the four outputs,
  * bsr_global_top_k_capped(k_in = k, per_group) on the gathered device arrays.
- * Out of scope: bsr_local_top_k_capped's sparse-mask fallback through this list scan; the group
- * search at deep k; a per-query per_group; a collective entry point. */
+ * The group search at deep k, with or without masks: bsr_local_top_groups_deep below.
+ * Out of scope: bsr_local_top_k_capped's sparse-mask fallback through this list scan; a per-query
+ * per_group; a collective entry point. */
 int bsr_local_top_k_deep_capped_masked(bsr_index* ix, const float* queries, uint32_t n_queries,
                                        uint32_t k, uint32_t per_group,
                                        const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
@@ -872,6 +873,64 @@ int bsr_local_top_k_deep_capped_masked(bsr_index* ix, const float* queries, uint
                                        uint64_t* out_idx, float* out_dist,    /* [n_queries][k] */
                                        uint32_t* out_group /* [n_queries][k], nullable */,
                                        uint32_t* out_count /* [n_queries] */);
+
+/* ---- Deep group search: bsr_local_top_groups for k up to BSR_DEEP_MAX_K -- "the
+ * 1000 nearest documents, three passages of each", with or without allow masks, in one call.
+ * row_group, row_group_len and n_groups are taken as bsr_local_top_k_deep_capped takes them.
+ * allow == NULL is the unmasked search: n_masks must then be 0 and query_mask NULL
+ * (bsr_local_top_k_mmr's convention); with allow, the mask arguments and mode are
+ * bsr_local_top_k_deep_masked's.  Every array is, independently, a host or a device pointer.  There is
+ * no fetch_k.
+ * The result is rules 1 to 4 of bsr_local_top_groups, word for word, over the rows that are live and
+ * allowed.  group_size = 1 is bsr_local_top_k_deep_capped with per_group = 1 (under masks
+ * bsr_local_top_k_deep_capped_masked) in idx, dist, group and count, bit for bit; slot [g][0] is that
+ * head for every group_size; for k <= 256 the five outputs are bsr_local_top_groups(k, group_size,
+ * fetch_k = 256, ...)'s byte for byte; row_group[i] = i gives bsr_local_top_k_deep(k) in the [g][0]
+ * slots with out_rows = 1; the result at k is the first k group slots of the result at any larger k.
+ * 1 <= k <= BSR_DEEP_MAX_K, not bounded by cfg.max_k; 1 <= group_size <= BSR_GROUPS_MAX_ROWS;
+ * k * group_size <= BSR_DEEP_GROUPS_MAX_SLOTS; n_groups >= 1.
+ * The checks, in this order; the caller's arrays are untouched on every error:
+ *   1. BSR_E_INVALID before any device is touched: a null index; group_size = 0 or above
+ *      BSR_GROUPS_MAX_ROWS; k * group_size above BSR_DEEP_GROUPS_MAX_SLOTS; k = 0 or k >
+ *      BSR_DEEP_MAX_K; n_groups = 0; n_masks != 0 or a query_mask without allow, n_masks = 0 with allow,
+ *      a null query_mask with n_masks > 1; an unknown mode; with n_queries > 0 a null queries pointer
+ *      or a null out_idx / out_dist / out_count;
+ *   2. BSR_E_STATE: the index is not loaded;
+ *   3. BSR_E_INVALID: row_group_len != n, or a null row_group with rows;
+ *   4. n_queries = 0: BSR_OK;
+ *   5. everything else as the head search reports it, before any of the caller's arrays is written:
+ *      allow_words != ceil(n / 64); an entry of query_mask >= n_masks; a row_group entry >= n_groups,
+ *      found on the device before anything is indexed with it; BSR_E_NONFINITE.
+ * An empty shard gives every count 0.
+ * How: the heads are bsr_local_top_k_deep_capped's with per_group = 1 (under masks the masked ladder),
+ * written into arrays of the index; the inverted list of row_group is built as bsr_local_top_groups
+ * builds it; one kernel lays out every query's result groups (prefix sums of their row counts, 64
+ * rows an item) and the host reads the batch's item count and the largest query's -- the call's one
+ * wait besides the head search's.  The fill gives a workgroup to every query with at most B =
+ * max(BSR_GROUPS_SPLIT_ITEMS, ceil(items of the batch / (4 * compute units))) items (an LDS table of
+ * k * group_size keys); a query above B is dealt over up to 1024 workgroups through a table of 8 * k *
+ * group_size bytes in device memory, then sorted and written by a finish kernel.  The footprint beside
+ * the head search's: bsr_local_top_groups' buffers at this k, and 4 * n_queries * (2 k + 2) bytes for
+ * the plan.  Every buffer is allocated before the head search.  Never graph-replayed; the plain
+ * search's graphs are left alone.
+ * bsr_search_stats: search_path is the head search's with BSR_PATH_CAP replaced by BSR_PATH_GROUPS:
+ * BSR_PATH_DEEP | BSR_PATH_GROUPS, plus the mask bits, plus BSR_PATH_CAP_SCAN when a query needed the
+ * group scan to find its groups; never BSR_PATH_CAP, BSR_PATH_COLLAPSE or BSR_PATH_DEEP_SCAN.  The
+ * other fields are the head search's.  BSR_FLAG_PROFILE: the plan and the fill in rescore_ms, added
+ * to the head search's.
+ * Out of scope: a multi-rank merge of group results; group ids or the inverted list stored on the
+ * index; a per-query group_size; group_size above 64; routing bsr_local_top_groups here; a collective
+ * entry point. */
+#define BSR_DEEP_GROUPS_MAX_SLOTS 8192u  /* k * group_size */
+int bsr_local_top_groups_deep(bsr_index* ix, const float* queries, uint32_t n_queries,
+                              uint32_t k, uint32_t group_size,
+                              const uint32_t* row_group, uint64_t row_group_len, uint32_t n_groups,
+                              const uint64_t* allow, uint64_t allow_words, uint32_t n_masks,
+                              const uint32_t* query_mask, uint32_t mode,
+                              uint64_t* out_idx, float* out_dist,   /* [n_queries][k][group_size] */
+                              uint32_t* out_group,                  /* [n_queries][k], nullable */
+                              uint32_t* out_rows,                   /* [n_queries][k], nullable */
+                              uint32_t* out_count);                 /* [n_queries] */
 
 /* ---- Deep MMR search: bsr_local_top_k_mmr over up to BSR_DEEP_MAX_K exact
  * candidates -- "k different passages out of the 1000 nearest", without document ids and without
